@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py — rendered rays/sec of the MatchNeRF hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line: metric, value (rays/s), unit, dtype,
+ms_per_step, higher_is_better and the run's shape (n_gpus, steps, warmup, scaling).  ``--dump-outputs DIR`` writes what the
+last timed step computed - rgb, depth, opacity of the frame(s) - as DIR/<name>.npy (float32; inputs are seeded, so two
+builds can be compared output for output).  ``--full`` adds everything else listed below.
 
 One "step" = one full pass of the hot path over one synthetic batch of BASELINE config[1]:
 ``MatchNeRF.forward(batch, mode='test')`` for a 3-view 512x640 DTU-shaped scene with 64
@@ -23,7 +28,8 @@ the shared source views and renders a DIFFERENT target view (weak scaling: BASEL
 "target views sharded across GPUs"), then one all_gather returns every rank's [327680,5] tile to
 all ranks.  value = all rays of all ranks / max-over-ranks time.
 
-Also in the JSON line (N = 1):
+With --full, per-kernel event timing inside the timed steps, the per-rank step times, `frame_bits` and the encoder-only
+time, and also in the JSON line (N = 1):
   roofline      the dominant kernel (fused decoder), SURVEY.md §8(d): ALGORITHMIC FLOPs per launch
                 (258,336 + 64 S per sample) / average launch duration measured with events on the launch
                 stream inside the timed region, against the ceiling of the matrix path IN USE (dense 16-bit
@@ -123,6 +129,23 @@ def make_batch(device, target_shift, height=H, width=W, n_views=V, **scene_kw):
         ext[0, -1, 0, 3] += 0.04 * target_shift  # slide the target along x (camera frame)
         sc["extrinsics"] = ext
     return sc, EasyDict({k: torch.from_numpy(v).to(device) for k, v in sc.items()})
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, full, n_rays):
+    """--dump-outputs: the last timed step's result as the arrays a caller of MatchNeRF.forward(mode='test') receives,
+    rgb [F, H*W, 3], depth [F, H*W, 1], opacity [F, H*W, 1] in float32 (F frames: one, or one per rank with --shard views).
+    Above DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded sample of rays."""
+    import numpy as np
+    frames = full.reshape(-1, n_rays, 5).cpu().numpy()
+    if frames.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (frames.shape[0] * 5 * frames.itemsize)
+        frames = frames[:, np.sort(np.random.default_rng(0).choice(n_rays, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, cols in (("rgb", slice(0, 3)), ("depth", slice(3, 4)), ("opacity", slice(4, 5))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(frames[..., cols], dtype=np.float32))
 
 
 def cpu_baseline(weights, scene, n_threads):
@@ -269,6 +292,10 @@ def respawn_under_launcher(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    if getattr(args, "full", False):
+        cmd.append("--full")
+    if getattr(args, "dump_outputs", None):
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if getattr(args, "shard", "views") != "views":
@@ -285,12 +312,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config[2] / config[4] timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel timing and roofline, the other decoder math paths, the one-launch form, the secondary "
+                         "workloads and the CPU baseline (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's rgb / depth / opacity as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the config[2] / config[4] timings")
     ap.add_argument("--shard", choices=["views", "rows"], default="views",
                     help="N > 1: 'views' = every rank renders its own target view (weak scaling, the default); 'rows' = ONE "
                          "frame per step, row bands sharded over the ranks (strong scaling, dist.render_frame_sharded)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_launcher(args))
@@ -322,26 +356,29 @@ def main():
 
     def step(timer=None):
         model.kernel_timer = timer
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timer is not None else None
+        if ev:
+            ev[0].record()
         with torch.no_grad():
             if rows_mode:  # strong scaling: one frame, this rank renders its band of rows; the gather is inside
                 out = mdist.render_frame_sharded(model, batch)
-                ev[1].record()
+                if ev:
+                    ev[1].record()
                 full = torch.cat([out.rgb[0], out.depth[0], out.opacity[0]], -1)
             else:
                 out = model(batch, mode="test")
                 tile = torch.cat([out.rgb[0], out.depth[0], out.opacity[0]], -1)  # [HW,5]
-                ev[1].record()
+                if ev:
+                    ev[1].record()
                 full = mdist.gather_tiles(tile)                                    # RCCL all_gather (N>1)
-        ev[2].record()
-        if timer is not None:
+        if ev:
+            ev[2].record()
             spans.append(ev)
         return full
 
     for _ in range(args.warmup):
         step()
-    timer = hip.KernelTimer()
+    timer = hip.KernelTimer() if args.full else None
     mdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -351,6 +388,25 @@ def main():
     mdist.barrier()
     elapsed = mdist.max_over_ranks(time.perf_counter() - t0, device)
     assert full.shape == ((1 if rows_mode else world) * n_rays, 5) and bool(torch.isfinite(full).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full, n_rays)
+    math = model.nerf_dec.math_for(S)
+    ms_per_step = elapsed / args.steps * 1e3
+    line = {
+        "metric": "rendered rays/sec (3-view, 64 samples/ray)",
+        "value": round((1 if rows_mode else world) * n_rays * args.steps / elapsed, 1), "unit": "rays/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "strong" if rows_mode else "weak", "vs_baseline": None,
+        "dtype": "f16" if math == "f16" else "f32",
+        "data": "synthetic",
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        return
+
     frame_bits = "%012x" % (int(full.contiguous().view(torch.int32).to(torch.int64).sum()) & 0xffffffffffff)
     # per-rank milliseconds per step (frame incl. encoder | of it the gather), collected on every rank
     mine = torch.tensor([sum(a.elapsed_time(c) for a, _, c in spans) / max(len(spans), 1),
@@ -372,7 +428,6 @@ def main():
     # secondary figures (N=1, outside the timed region): the same frame with the other decoder matrix paths, and the
     # largest RGB difference to the default path
     from matchnerf_amd.cond_nerf import decoder_math
-    math = model.nerf_dec.math_for(S)
     other_math = {}
     if world == 1:
         rgb_default = full[:, :3].clone()
@@ -467,8 +522,6 @@ def main():
         guarded("train_iteration, sample_intvs 128 (configs/train.yaml)", train_step_workload, device, 128)
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = (1 if rows_mode else world) * n_rays * args.steps / elapsed
         fused = "render_fused" in ksum
         dec = ksum["render_fused"] if fused else ksum["decoder"]
         cv_ms = None if fused else ksum["cost_volume"]["total_ms"] / args.steps
@@ -547,12 +600,7 @@ def main():
                                 # the two stages are serial on the same CUs: time per ray at each stage's bound adds up
                                 "serial_bound_rays_per_s": round(1.0 / (1.0 / mfma_bound + 1.0 / l1_bound), 1),
                                 "render_only_frac_of_serial_bound": round(render_rate * (1.0 / mfma_bound + 1.0 / l1_bound), 4)})
-        line = {
-            "metric": "rendered rays/sec (3-view, 64 samples/ray)", "value": round(value, 1), "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "strong" if rows_mode else "weak", "vs_baseline": None,
-            "dtype": "f16" if math == "f16" else "f32",
-            "data": "synthetic",
+        line.update({
             "config": {
                 "workload": "BASELINE config[1]: DTU-shape 3-view 512x640, 64 samples/ray, full frame "
                             "(327680 rays) per step incl. GMFlow encoder; fp32 parity mode",
@@ -616,7 +664,7 @@ def main():
                 "cost_volume": cv_entry,
                 "frame": frame_entry,
             },
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(weights, scene, min(os.cpu_count() or 1, CPU_THREADS_MAX))
         print(json.dumps(line), flush=True)

@@ -115,3 +115,31 @@ def test_bench_respawns_itself_under_the_launcher(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" or "HSA_ENABLE_IPC_MODE_LEGACY" in os.environ
     bench.respawn_under_launcher(argparse.Namespace(gpus=2, steps=1, warmup=0, no_cpu_baseline=True, shard="rows"))
     assert seen["cmd"][-3:] == ["--no-cpu-baseline", "--shard", "rows"]      # the strong-scaling mode reaches the ranks
+    bench.respawn_under_launcher(argparse.Namespace(gpus=2, steps=1, warmup=0, no_cpu_baseline=False, full=True,
+                                                    dump_outputs="out"))
+    assert seen["cmd"][-3:] == ["--full", "--dump-outputs", os.path.abspath("out")]  # so do --full and --dump-outputs
+
+
+def test_bench_dump_outputs_writes_the_frame_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: rgb / depth / opacity of every gathered frame as float32 .npy files; above the byte cap every array
+    keeps the same seeded sample of rays"""
+    import sys
+
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    n_rays = 7
+    full = torch.cat([_fake_render(0, n_rays), _fake_render(100, n_rays)])  # two frames of [rays, 5]
+    bench.dump_outputs(str(tmp_path / "a"), full, n_rays)
+    frames = full.reshape(2, n_rays, 5).numpy()
+    for name, cols in (("rgb", slice(0, 3)), ("depth", slice(3, 4)), ("opacity", slice(4, 5))):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, frames[..., cols])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 3 * 5 * 4)  # room for 3 of the 7 rays of each frame
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), full, n_rays)
+    rgb, opacity = np.load(tmp_path / "b" / "rgb.npy"), np.load(tmp_path / "b" / "opacity.npy")
+    assert rgb.shape == (2, 3, 3) and opacity.shape == (2, 3, 1)
+    rows = rgb[0, :, 0].astype(int)  # _fake_render: column 0 is the ray index
+    assert np.array_equal(rgb, frames[:, rows, :3]) and np.array_equal(opacity, frames[:, rows, 4:])
+    assert np.array_equal(rgb, np.load(tmp_path / "c" / "rgb.npy"))  # the same sample every time

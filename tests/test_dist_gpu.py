@@ -91,7 +91,7 @@ def test_bench_self_spawns_two_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -109,7 +109,7 @@ def _bench(*flags, gpus):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-secondary", *flags], env=env, capture_output=True, text=True, timeout=1500)
+                        "--full", "--no-cpu-baseline", "--no-secondary", *flags], env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -128,6 +128,44 @@ def test_bench_with_eight_ranks_on_one_gpu():
         assert len(j["config"]["per_rank_ms_per_step"]["ranks"]) == 8
     assert rows["config"]["frame_bits"] == one["config"]["frame_bits"]
     assert views["config"]["frame_bits"] != one["config"]["frame_bits"]  # eight different target poses
+
+
+def test_plain_bench_prints_the_headline_and_dumps_the_frame(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` without --full: the headline line alone, K timed steps, and the last step's
+    frame as float32 arrays - the same frame a --full run dumps and sums into its frame_bits."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(*flags):
+        p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--warmup", "1", *flags],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0])
+
+    def frame(d):
+        arrays = [np.load(tmp_path / d / f"{n}.npy") for n in ("rgb", "depth", "opacity")]
+        assert [a.shape for a in arrays] == [(1, 512 * 640, 3), (1, 512 * 640, 1), (1, 512 * 640, 1)]
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays)
+        return np.concatenate(arrays, -1)
+
+    plain = run("--steps", "3", "--dump-outputs", str(tmp_path / "plain"))
+    assert set(plain) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                          "scaling", "vs_baseline", "dtype", "data"}
+    assert plain["steps"] == 3 and plain["unit"] == "rays/s" and plain["higher_is_better"] and plain["dtype"] == "f32"
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 - 512 * 640) < 1e-3 * 512 * 640
+    full = run("--steps", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(tmp_path / "full"))
+    assert "roofline" in full and "config" in full
+    a, b = frame("plain"), frame("full")
+    assert np.array_equal(a.view(np.int32), b.view(np.int32))
+    bits = "%012x" % (int(a.reshape(-1, 5).view(np.int32).astype(np.int64).sum()) & 0xffffffffffff)
+    assert bits == full["config"]["frame_bits"]
 
 
 def _nccl_one_rank_worker(port, q):

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/exp/gpu_call.sh TAG step [step ...]'      -> everything under gpurun_out/TAG/
 # steps:
 #   tests[=EXPR]        python -m pytest tests -m gpu -q [-k EXPR]            -> tests.log
-#   bench[=STEPS]       python bench.py --steps STEPS (default 10)            -> bench.json, key figures on stdout
+#   bench[=STEPS]       python bench.py --steps STEPS --full (default 10)     -> bench.json, key figures on stdout
 #   frames=C1,C2,..     tools/exp/frame_time.py per configuration (c2 c3 c5 s<N> demo); MNERF_LIB_VARIANTS="a b" runs every
 #                       configuration with libmnerf_hip.so and libmnerf_hip_<a>.so ... in turn (same-box A/B)  -> frames.log
 #   profile             tools/profile_round.sh TAG (kernel stats, bench trace, PMC passes, counter json files)
@@ -21,7 +21,7 @@ for step in "$@"; do
       timeout 1800 python -m pytest tests -m gpu -q ${arg:+-k "$arg"} > $O/tests.log 2>&1; echo "tests rc=$?" | tee -a $O/tests.log
       tail -4 $O/tests.log;;
     bench)
-      timeout 900 python bench.py --steps ${arg:-10} --warmup 2 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+      timeout 900 python bench.py --steps ${arg:-10} --warmup 2 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
       python - "$O/bench.json" <<'PY'
 import json, sys
 l = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
