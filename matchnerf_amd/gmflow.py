@@ -567,12 +567,36 @@ class GMFlow(nn.Module):
 
     def forward(self, imgs, attn_splits_list=None, wo_self_attn=False, **kwargs):
         """imgs [B,V,3,H,W] in [0,1] -> list over scales (1/8 raw, 1/4 up-sampled) of
-        pair-major channel-last maps [B, P, 2, h_s, w_s, 128] (gmflow.py:91-150)."""
+        pair-major channel-last maps [B, P, 2, h_s, w_s, 128] (gmflow.py:91-150).
+        The two stages are ``backbone_tokens`` (per view) and ``pair_maps`` (per view pair)."""
+        tok = self.backbone_tokens(imgs, attn_splits_list=attn_splits_list)
+        return self.pair_maps(tok, attn_splits_list=attn_splits_list, wo_self_attn=wo_self_attn)
+
+    @staticmethod
+    def _splits(attn_splits_list):
+        return attn_splits_list[0] if isinstance(attn_splits_list, (list, tuple)) else (attn_splits_list or 1)
+
+    @staticmethod
+    def _contiguous_range(sel, n, what):
+        """``sel`` (a step-1 range inside [0, n), or None = all) -> (first, count)"""
+        if sel is None:
+            return 0, n
+        if not isinstance(sel, range) or (len(sel) > 1 and sel.step != 1) or (len(sel) and (sel[0] < 0 or sel[-1] >= n)):
+            raise ValueError(f"{what}: expected a contiguous range inside [0, {n}), got {sel!r}")
+        return (sel[0], len(sel)) if len(sel) else (0, 0)
+
+    def backbone_tokens(self, imgs, views=None, attn_splits_list=None):
+        """First stage of ``forward``, per source view: imgs [B,V,3,H,W] in [0,1] -> channel-last tokens [B, n_v, h, w, 128] of
+        the views in ``views`` (a contiguous range of the V views; None = all) with the window position tile added, the IBRNet
+        756x1008 -> 768x1024 resize included.  The CNN takes one power-of-two operand gain per convolution over the images it
+        is given, so a subset may use another gain than the full pass; gains scale the fp16 split exactly except near the fp16
+        subnormal range."""
         b, v, c, hh, ww = imgs.shape
-        splits = attn_splits_list[0] if isinstance(attn_splits_list, (list, tuple)) else (attn_splits_list or 1)
-        x = imgs.reshape(b * v, c, hh, ww)
+        v0, n_v = self._contiguous_range(views, v, "backbone_tokens views")
+        splits = self._splits(attn_splits_list)
+        x = imgs.reshape(b * v, c, hh, ww) if n_v == v else imgs[:, v0:v0 + n_v].reshape(b * n_v, c, hh, ww)
         if hh == 756 and ww == 1008:  # IBRNet setting, gmflow.py:100-103
-            x = F.interpolate(x, size=(768, 1024), mode="bilinear", align_corners=True)
+            x = F.interpolate(x, size=(768, 1024), mode="bilinear", align_corners=True) if n_v else x.new_empty(0, c, 768, 1024)
         def _down8(n):  # three stride-2 convolutions (7x7 pad 3, 3x3 pad 1, 3x3 pad 1): ceil-like sizes
             for _ in range(3):
                 n = (n - 1) // 2 + 1
@@ -580,15 +604,30 @@ class GMFlow(nn.Module):
         h, w, ch = _down8(x.shape[2]), _down8(x.shape[3]), self.feature_channels
         if h % splits or w % splits:
             raise ValueError(f"feature map {h}x{w} is not divisible by attn_splits={splits}")
+        if n_v == 0:  # a rank without a share of the views
+            return imgs.new_empty(b, 0, h, w, ch)
         pe = sine_position_tokens(h // splits, w // splits, ch, x.device).repeat(splits, splits, 1).reshape(h * w, ch).contiguous()
-        # [BV,h,w,C] tokens with the window position tile added (by the backbone's last convolution at inference)
+        # [B n_v,h,w,C] tokens with the window position tile added (by the backbone's last convolution at inference)
         tok = self.backbone((x - self._mean) / self._std, tokens_plus=pe)
         if tuple(tok.shape[1:]) != (h, w, ch):
             raise ValueError(f"backbone output {tuple(tok.shape[1:])} != expected {(h, w, ch)} for a {hh}x{ww} input")
-        tok = tok.reshape(b, v, h * w, ch)
-        pairs = pair_list(v)
+        return tok.reshape(b, n_v, h, w, ch)
+
+    def pair_maps(self, tokens, pairs=None, attn_splits_list=None, wo_self_attn=False):
+        """Second stage of ``forward``, per view pair: tokens [B, V, h, w, 128] of ALL V views (``backbone_tokens``) -> [maps
+        [B, P_sub, 2, h, w, 128], up-sampled maps [B, P_sub, 2, 2h, 2w, 128]] of the pairs in ``pairs`` (a contiguous range over
+        ``pair_list(V)``; None = all), in ``pair_list`` order: the transformer and the up-sampler on those pairs alone."""
+        b, v, h, w, ch = tokens.shape
+        splits = self._splits(attn_splits_list)
+        pairs_all = pair_list(v)
+        p0, p_n = self._contiguous_range(pairs, len(pairs_all), "pair_maps pairs")
+        if p_n == 0:  # a rank without a share of the pairs
+            up = 2 ** self.featup_net.n_blocks
+            return [tokens.new_empty(b, 0, 2, h, w, ch), tokens.new_empty(b, 0, 2, up * h, up * w, ch)]
+        tok = tokens.reshape(b, v, h * w, ch)
         ia, ib = _pair_index_tensors(v, tok.device)
-        p_n = len(pairs)
+        if p_n != len(pairs_all):
+            ia, ib = ia[p0:p0 + p_n], ib[p0:p0 + p_n]  # slices of the cached device tensors: no host->device copy
         outs0, outs1 = [], []
         for bi in range(b):
             src = torch.cat([tok[bi, ia], tok[bi, ib]], 0).contiguous()       # [2P, hw, C]
