@@ -123,3 +123,21 @@ def decoder_torch(opt, dec, x, dirs, cond, n_views):
         sigma = torch.where(n_valid < 1, torch.zeros_like(sigma), sigma)
     hv = F.relu(dec.views_linears[0](torch.cat([dec.feature_linear(hcur), dirs[:, None].expand(-1, s_n, -1)], -1)))
     return torch.sigmoid(dec.rgb_linear(hv)), sigma
+
+
+class ReluKinks(torch.overrides.TorchFunctionMode):
+    """Records, per ray, the smallest |argument| of every F.relu evaluated while the mode is active (tensors shaped [R, ...]).
+    The backward kernels re-evaluate the network in fp32-grade arithmetic: where a ReLU argument lies within that error of zero
+    they may take the other side of the kink, a jump of the network's derivative rather than an error of a kernel.  With 65 536
+    rows and ~1 000 ReLU arguments per sample a few rays of every training-size batch do; the parity tests give those rays zero
+    upstream gradient (on both sides of the comparison)."""
+
+    def __init__(self, n_rays):
+        super().__init__()
+        self.margin = torch.full((n_rays,), float("inf"), dtype=torch.float64)
+
+    def __torch_function__(self, func, types, args=(), kwargs=None):
+        if func is F.relu:
+            z = args[0].detach()
+            self.margin = torch.minimum(self.margin, z.abs().reshape(z.shape[0], -1).amin(1).double().cpu())
+        return func(*args, **(kwargs or {}))

@@ -4,6 +4,7 @@ reference; it is dtype-generic and differentiable)."""
 import pytest
 import torch
 
+from gpu_helpers import ReluKinks
 from helpers import golden_case
 from oracle import matchnerf_oracle as O
 from test_model_gpu import build_model
@@ -11,7 +12,7 @@ from test_model_gpu import build_model
 pytestmark = pytest.mark.gpu
 
 
-def _case(name, n_rays, n_samples, seed, **decoder_opts):
+def _case(name, n_rays, n_samples, seed, kink_margin=0.0, **decoder_opts):
     from matchnerf_amd import hip
     g, cfg, sd, _ = golden_case(name)
     opt, model = build_model(g["meta"])
@@ -40,17 +41,30 @@ def _case(name, n_rays, n_samples, seed, **decoder_opts):
         from matchnerf_amd.cond_nerf import raytrans_table
         table = torch.from_numpy(raytrans_table(n_samples))
     params = {k: p.detach() for k, p in dec.named_parameters()}
-    g_cond, grads = hip.decoder_backward(opt, params, v, x.cuda(), dirs.cuda(), cond.cuda(), stride, g_rgb.cuda(), g_sig.cuda(),
-                                         raytrans_table=table)
-    torch.cuda.synchronize()
-
     for k, val in decoder_opts.items():  # the oracle's switches follow the module's options
         assert hasattr(cfg, k), k
         setattr(cfg, k, val)
     sd64 = {"nerf_dec." + k: p.detach().double().cpu().clone().requires_grad_(True) for k, p in dec.named_parameters()}
+    x64, dirs64 = x.double().reshape(n_rays, n_samples, 3), dirs.double()
+    if kink_margin > 0:  # rays within reach of a ReLU kink get zero upstream gradient (gpu_helpers.ReluKinks)
+        c64 = cond[:, :dc].double().reshape(n_rays, n_samples, dc)
+        with torch.no_grad(), ReluKinks(n_rays) as kinks:
+            O.decoder(cfg, sd64, x64, dirs64, c64, c64[..., -v:])
+        keep = (kinks.margin >= kink_margin).float()
+        print(f"rays within {kink_margin:.0e} of a ReLU kink: {int((keep == 0).sum())} of {n_rays}")
+        g_rgb = (g_rgb.reshape(n_rays, n_samples, 3) * keep[:, None, None]).reshape(n, 3)
+        g_sig = g_sig * keep[:, None]
+    g_cond, grads = hip.decoder_backward(opt, params, v, x.cuda(), dirs.cuda(), cond.cuda(), stride, g_rgb.cuda(), g_sig.cuda(),
+                                         raytrans_table=table)
+    torch.cuda.synchronize()
+
     cond_ref = cond[:, :dc].double().reshape(n_rays, n_samples, dc).clone().requires_grad_(True)
-    rgb_s, sigma = O.decoder(cfg, sd64, x.double().reshape(n_rays, n_samples, 3), dirs.double(), cond_ref, cond_ref[..., -v:])
-    (rgb_s * g_rgb.double().reshape(n_rays, n_samples, 3)).sum().add((sigma * g_sig.double()).sum()).backward()
+    g_rgb64, g_sig64 = g_rgb.double().reshape(n_rays, n_samples, 3), g_sig.double()
+    step = max(1, 16384 // n_samples)  # rays are independent: bounded float64 graphs at the training shapes, gradients accumulate
+    for r0 in range(0, n_rays, step):
+        r = slice(r0, r0 + step)
+        rgb_s, sigma = O.decoder(cfg, sd64, x64[r], dirs64[r], cond_ref[r], cond_ref[r][..., -v:])
+        (rgb_s * g_rgb64[r]).sum().add((sigma * g_sig64[r]).sum()).backward()
     worst = {}
     for k in params:
         p = sd64["nerf_dec." + k]
@@ -71,6 +85,23 @@ def _case(name, n_rays, n_samples, seed, **decoder_opts):
 ])
 def test_decoder_backward_matches_float64_autograd(name, n_rays, n_samples, opts):
     worst = _case(name, n_rays, n_samples, seed=n_samples, **opts)
+    bad = {k: v for k, v in worst.items() if not v < 2e-4}
+    print({k: f"{v:.1e}" for k, v in worst.items()})
+    assert len(worst) == 33 and not bad, bad
+
+
+@pytest.mark.parametrize("name,n_rays,n_samples,opts", [
+    ("c1_default", 1024, 64, {}),
+    ("c1_default", 1024, 128, {}),
+    ("c1_default", 1024, 128, {"raytrans_act": "ELU", "raytrans_posenc": True, "density_maskfill": True}),
+])
+def test_decoder_backward_at_training_shapes_matches_float64_autograd(name, n_rays, n_samples, opts):
+    """The training shapes (configs/train.yaml: 1 024 rays; 64 / 128 samples; the IBRNet recipe's options): 65 536 / 131 072 rows,
+    where colsum4_kernel's four-rows-in-flight loop (every bias and LayerNorm gradient) and the split-K weight-gradient reductions
+    run many iterations.  Same 2e-4 gate on all 33 tensors.  Rays with a ReLU argument within 2e-6 of its kink in the float64
+    forward get zero upstream gradient (gpu_helpers.ReluKinks): without that, the gradients of the layers up to the last ReLU moved
+    by up to 5e-3 against float64 and single rows of g_cond by 3e-2, while the layers behind it stayed at ~1e-6."""
+    worst = _case(name, n_rays, n_samples, seed=n_samples + 1, kink_margin=2e-6, **opts)
     bad = {k: v for k, v in worst.items() if not v < 2e-4}
     print({k: f"{v:.1e}" for k, v in worst.items()})
     assert len(worst) == 33 and not bad, bad
