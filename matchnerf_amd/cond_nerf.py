@@ -55,7 +55,7 @@ def decoder_stages(cond_stride, L_3D):
 
 
 def decoder_schedule(cond_stride, L_3D):
-    """Mirror of build_schedule() in csrc/decoder.hip -> (segments, total_floats);
+    """Mirror of build_schedule() in csrc/decoder_common.hpp -> (segments, total_floats);
     segment = (stage, first_step, n_steps, nmb, float_offset, padded_floats)."""
     segs, off = [], 0
     for name, t, m in decoder_stages(cond_stride, L_3D):

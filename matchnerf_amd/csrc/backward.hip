@@ -246,9 +246,7 @@ __global__ __launch_bounds__(256) void cost_volume_backward_kernel(mnerf_scene s
 // channel when it leaves the cell, instead of one per sample; the taps of a cell are loaded once per visit, not once per sample.
 // Same channel mapping as above (an atomic instruction of a slot covers one 64-byte line), same arithmetic per sample; what
 // differs is the order in which contributions reach a texel (they did not have a fixed order before either: float atomics).
-#ifndef CVB_WALK_WAVES
 #define CVB_WALK_WAVES 2
-#endif
 __global__ __launch_bounds__(256, CVB_WALK_WAVES) void cost_volume_backward_walk_kernel(mnerf_scene sc, mnerf_rays R, int cond_stride,
                                                                         const float* __restrict__ g_cond,
                                                                         float* __restrict__ g_feat0,

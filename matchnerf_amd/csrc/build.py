@@ -10,22 +10,23 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libmnerf_hip.so")
-SOURCES = ["api.cpp", "backward.hip", "composite.hip", "conv.hip", "conv_backward.hip", "cost_volume.hip", "cost_volume_mm.hip", "decoder.hip", "decoder_backward.hip", "decoder_fused", "encoder_backward.hip", "encoder_block.hip",
+SOURCES = ["api.cpp", "backward.hip", "composite.hip", "conv.hip", "conv_backward.hip", "cost_volume.hip", "cost_volume_mm.hip", "decoder.hip", "decoder_backward.hip", "decoder_fused.hip", "encoder_backward.hip", "encoder_block.hip",
            "geometry.hip", "instance_norm.hip", "qkv.hip", "render_chunk.hip", "window_attention.hip", "window_attention_backward.hip"]
-# objects that are a second compilation of another source: object name -> (source, extra flags).
-# decoder_fused: the one-launch ray chunk (decoder.hip, MNERF_DECODER_PART=1).  Its workgroups run the cost-volume walk on
-# SIMDs where another workgroup issues 16-bit 32x32x16 matrix instructions; packed-fp32 vector instructions lose results
-# in lanes 48-63 there, so that object is built without them: the walk's channel-pair arithmetic is
-# one instruction per channel (cv_walk.hpp) and the SLP vectoriser is off (EXTRA_FLAGS below).
-DERIVED = {"decoder_fused": ("decoder.hip", ["-DMNERF_DECODER_PART=1"])}
-# per-source extra flags.  cost_volume.hip: the same rule for the stand-alone kernel (it may share SIMDs with 16-bit MFMA
+# per-source extra flags.
+# decoder_fused.hip: the one-launch ray chunk.  Its workgroups run the cost-volume walk on SIMDs where another workgroup issues
+# 16-bit 32x32x16 matrix instructions; packed-fp32 vector instructions lose results in lanes 48-63 there, so
+# that object is built without them: the walk's channel-pair arithmetic is one instruction per channel (cv_walk.hpp) and the SLP
+# vectoriser is off.
+# cost_volume.hip: the same rule for the stand-alone kernel (it may share SIMDs with 16-bit MFMA
 # waves of ANY kernel on another stream; measured next to this library's decoder), and the same arithmetic as the walk
 # inside the one-launch form, so that the two forms stay bit-identical.
-# decoder.hip (both parts): the same flag — the two forms of the ray chunk are bit-identical only if their trunks are
+# decoder.hip: the same flag — the two forms of the ray chunk are bit-identical only if their trunks are
 # compiled alike, and the trunk's own packed multiplies sat next to the partner workgroup's matrix instructions too;
 # measured neutral (19.60 vs 19.75 ms per frame).
-EXTRA_FLAGS = {"cost_volume.hip": ["-fno-slp-vectorize"], "cost_volume_mm.hip": ["-fno-slp-vectorize"], "decoder.hip": ["-fno-slp-vectorize"]}
-DECODER_SOURCES = ["decoder.hip", "split_f16.hpp", "cv_walk.hpp", "common.hpp"]  # what decoder_kernel is compiled from
+EXTRA_FLAGS = {"cost_volume.hip": ["-fno-slp-vectorize"], "cost_volume_mm.hip": ["-fno-slp-vectorize"], "decoder.hip": ["-fno-slp-vectorize"],
+               "decoder_fused.hip": ["-fno-slp-vectorize"]}
+# what the decoder kernels are compiled from
+DECODER_SOURCES = ["decoder.hip", "decoder_fused.hip", "decoder_staged.hpp", "decoder_common.hpp", "split_f16.hpp", "cv_walk.hpp", "common.hpp"]
 # -amdgpu-use-amdgpu-trackers: the AMDGPU register-pressure trackers in the scheduler; the fused decoder spills 57 instead
 # of 108 vector registers with them (decoder 20.8 -> 20.15 ms per frame on MI355X), everything else is unchanged
 # -target-feature -packed-fp32-ops (ALL device code): the compiler may not select v_pk_{mul,fma,add}_f32.  On gfx950 a packed-fp32
@@ -40,23 +41,29 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
          "-amdgpu-use-amdgpu-trackers=1"] + NO_PACKED_F32
 
 
-def source_hash():
-    """sha256 over everything the decoder kernel is compiled from (its sources, the argument structs it takes from the
-    ABI header, the compiler flags): identifies the build that profile-derived numbers (profiles/current/decoder_counters.json)
-    belong to, so that bench.py can tell when they have gone stale.  (Other kernels' sources and the rest of the header
-    are left out: a change in the encoder does not change the decoder's counters.)"""
+def _hash(flags_of, sources, structs):
+    """sha256 over what a kernel is compiled from: the compiler flags (those of the source `flags_of`), the text of `sources` and
+    the argument structs it takes from the ABI header."""
     import hashlib
     import re
-    h = hashlib.sha256(" ".join(FLAGS + EXTRA_FLAGS.get("decoder.hip", [])).encode())
-    for name in sorted(DECODER_SOURCES):
+    h = hashlib.sha256(" ".join(FLAGS + EXTRA_FLAGS.get(flags_of, [])).encode())
+    for name in sorted(sources):
         with open(os.path.join(HERE, name), "rb") as f:
             h.update(name.encode() + b"\0" + f.read())
     with open(os.path.join(PKG, "..", "include", "mnerf.h")) as f:
         header = f.read()
-    for st in ("mnerf_view", "mnerf_rays", "mnerf_scene", "mnerf_decoder"):
+    for st in structs:
         m = re.search(r"typedef struct %s \{.*?\} %s;" % (st, st), header, re.S)
         h.update(m.group(0).encode())
     return h.hexdigest()[:16]
+
+
+def source_hash():
+    """sha256 over everything the decoder kernels are compiled from (their sources, the argument structs they take from the
+    ABI header, the compiler flags): identifies the build that profile-derived numbers (profiles/current/decoder_counters.json)
+    belong to, so that bench.py can tell when they have gone stale.  (Other kernels' sources and the rest of the header
+    are left out: a change in the encoder does not change the decoder's counters.)"""
+    return _hash("decoder.hip", DECODER_SOURCES, ("mnerf_view", "mnerf_rays", "mnerf_scene", "mnerf_decoder"))
 
 
 COST_VOLUME_SOURCES = ["cost_volume.hip", "cost_volume_mm.hip", "cv_walk.hpp", "common.hpp"]  # what cost_volume_lean_kernel is compiled from
@@ -64,18 +71,7 @@ COST_VOLUME_SOURCES = ["cost_volume.hip", "cost_volume_mm.hip", "cv_walk.hpp", "
 
 def cost_volume_source_hash():
     """The same for the stand-alone cost-volume kernel (profiles/current/cost_volume_counters.json)."""
-    import hashlib
-    import re
-    h = hashlib.sha256(" ".join(FLAGS + EXTRA_FLAGS.get("cost_volume.hip", [])).encode())
-    for name in sorted(COST_VOLUME_SOURCES):
-        with open(os.path.join(HERE, name), "rb") as f:
-            h.update(name.encode() + b"\0" + f.read())
-    with open(os.path.join(PKG, "..", "include", "mnerf.h")) as f:
-        header = f.read()
-    for st in ("mnerf_view", "mnerf_rays", "mnerf_scene"):
-        m = re.search(r"typedef struct %s \{.*?\} %s;" % (st, st), header, re.S)
-        h.update(m.group(0).encode())
-    return h.hexdigest()[:16]
+    return _hash("cost_volume.hip", COST_VOLUME_SOURCES, ("mnerf_view", "mnerf_rays", "mnerf_scene"))
 
 
 def _compile(cmd):
@@ -101,14 +97,11 @@ def build(force=False, verbose=True):
         hipcc = "hipcc"
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(HERE, h) for h in ("common.hpp", "cv_walk.hpp", "split_f16.hpp", "wa_common.hpp", "gemm_f32.hpp")] + [os.path.join(PKG, "..", "include", "mnerf.h")]
+    deps = [os.path.join(HERE, h) for h in sorted(os.listdir(HERE)) if h.endswith(".hpp")] + [os.path.join(PKG, "..", "include", "mnerf.h")]
     objs = []
     for src in SOURCES:
-        extra = []
         name = os.path.splitext(src)[0]
-        if src in DERIVED:
-            src, extra = DERIVED[src]
-        extra = extra + EXTRA_FLAGS.get(src, [])
+        extra = EXTRA_FLAGS.get(src, [])
         sp = os.path.join(HERE, src)
         if not os.path.exists(sp):
             raise FileNotFoundError(sp)

@@ -52,7 +52,7 @@ mnerf_tuning mnerf_tune();  // a snapshot (api.cpp: copied under the table lock)
 bool mnerf_once_per_device(std::atomic<unsigned long long>& mask);
 // argument checks of the scene / rays structs (cost_volume.hip)
 int mnerf_scene_check(const mnerf_scene* sc, const mnerf_rays* rays, const char* who);
-// fused ray-chunk form (decoder.hip), used by mnerf_render_chunk (render_chunk.hip)
+// fused ray-chunk form (decoder_fused.hip), used by mnerf_render_chunk (render_chunk.hip)
 bool mnerf_fused_render_applies(const mnerf_scene* sc, const mnerf_decoder* dec, const mnerf_rays* rays);
 bool mnerf_cost_volume_takes_pose_table(const mnerf_scene* sc);                 // cost_volume.hip
 bool mnerf_cost_volume_mm_applies(const mnerf_scene* sc, const mnerf_rays* rays);  // cost_volume_mm.hip

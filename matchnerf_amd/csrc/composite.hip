@@ -9,7 +9,7 @@
 // __shfl_up steps (5 DPP row/bank shifts + 1 cross-row on gfx950); rays with S > 64 are
 // walked in 64-sample blocks with a scalar carry.  HBM traffic is the compulsory
 // 5 floats/sample in + 5 floats/ray out, so this stand-alone form is bandwidth-bound; in the
-// fused ray-chunk kernel (decoder.hip) the same routine runs on LDS-resident samples.
+// fused ray-chunk kernels (decoder.hip, decoder_staged.hpp) the same routine runs on LDS-resident samples.
 #include "common.hpp"
 
 __device__ __forceinline__ float wave_incl_scan(float v, int lane) {

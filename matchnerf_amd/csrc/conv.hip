@@ -23,20 +23,8 @@
 #include "split_f16.hpp"
 
 #define CONV_NW 4
-#ifndef CONV_EXP
-#define CONV_EXP 0  // removal experiments (wrong results, meaningful times; tools/exp/conv_removal.sh): 1 no matrix instructions,
-#endif              // 2 no operand loads, 3 no operand split, 4 no weight requests / segment barriers, 5 no tap geometry
 #define CONV_BUF_BYTES 36864u  // one LDS weight buffer (36 KiB: six K16-steps x three 32-row blocks)
 
-#if CONV_EXP == 1
-__device__ __forceinline__ f32x16 conv_nomfma(f16x8 a, f16x8 b, f32x16 c) {
-  asm volatile("" : "+v"(a), "+v"(b));
-  return c;
-}
-#define CONV_MFMA conv_nomfma
-#else
-#define CONV_MFMA mfma16h
-#endif
 #ifdef CONV_TIMELINE
 // debug build (tools/exp/conv_timeline.py): s_memtime stamps of wave 0 of a few workgroups at the phase boundaries of every
 // iteration: [workgroup slot][iteration][point]  0 top | 1 operands arrived + split | 2 next loads issued | 3 matrix instructions
@@ -134,7 +122,6 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
   float vn[TPW][16];  // [tile][K16-step of the pair * 8 + j], as loaded: the padding mask is applied at the USE
   bool vok[TPW];      // (a select next to the load would make the wave wait for the data one iteration early)
   auto load_pair = [&]() {
-    if (CONV_EXP == 2) return;
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
       const float* src = P.in + toff[t] + (long long)(32 * cpair) * P.sc;
@@ -164,7 +151,7 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
     }
     if (++cpair == cpairs) {
       cpair = 0;
-      if (++tap < P.ksize * P.ksize && CONV_EXP != 5) tap_geometry();
+      if (++tap < P.ksize * P.ksize) tap_geometry();
     }
   };
   tap_geometry();
@@ -198,10 +185,6 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
           float v8[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) v8[j] = vok[t] ? vn[t][8 * u + j] : 0.0f;
-          if (CONV_EXP == 3) {
-            b[u][t].hi = __builtin_bit_cast(f16x8, (u32x4){__float_as_uint(v8[0]), __float_as_uint(v8[1]), __float_as_uint(v8[2]), __float_as_uint(v8[3])});
-            b[u][t].lo = __builtin_bit_cast(f16x8, (u32x4){__float_as_uint(v8[4]), __float_as_uint(v8[5]), __float_as_uint(v8[6]), __float_as_uint(v8[7])});
-          } else
           b[u][t] = split8h(v8, mult);
         }
       // The next weight segment is requested HERE, behind the wait for this iteration's operands and in front of the next
@@ -209,7 +192,7 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
       // waits for every request in flight - asked for at the top of the segment, the requests were waited for right away, once per
       // segment; in this place they are older than the loads the next wait is for and arrive before them.
       CONV_TL_STAMP(1);
-      if (CONV_EXP != 4 && it == 0 && seg + 1 < P.n_seg) stage(seg + 1);
+      if (it == 0 && seg + 1 < P.n_seg) stage(seg + 1);
       if (iter + 1 < n_iter) load_pair();
       CONV_TL_STAMP(2);
       lds_u32x4_cptr a = (lds_u32x4_cptr)(size_t)(cur + (unsigned)(2 * it * NMB) * H16_UNIT_BYTES) + lane;
@@ -221,15 +204,14 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
           const f16x8 ah = __builtin_bit_cast(f16x8, a[unit * 128]), al = __builtin_bit_cast(f16x8, a[unit * 128 + 64]);
           // the two pixel tiles alternate: no matrix instruction has the accumulator of its predecessor
 #pragma unroll
-          for (int t = 0; t < TPW; ++t) acc[t][m] = CONV_MFMA(ah, b[u][t].lo, acc[t][m]);
+          for (int t = 0; t < TPW; ++t) acc[t][m] = mfma16h(ah, b[u][t].lo, acc[t][m]);
 #pragma unroll
-          for (int t = 0; t < TPW; ++t) acc[t][m] = CONV_MFMA(al, b[u][t].hi, acc[t][m]);
+          for (int t = 0; t < TPW; ++t) acc[t][m] = mfma16h(al, b[u][t].hi, acc[t][m]);
 #pragma unroll
-          for (int t = 0; t < TPW; ++t) acc[t][m] = CONV_MFMA(ah, b[u][t].hi, acc[t][m]);
+          for (int t = 0; t < TPW; ++t) acc[t][m] = mfma16h(ah, b[u][t].hi, acc[t][m]);
         }
       CONV_TL_STAMP(3);
     }
-    if (CONV_EXP == 4) continue;
     segment_wait();   // this wave's pieces of the next segment (and its operand prefetch) have landed
 #ifdef CONV_TIMELINE
     --iter;

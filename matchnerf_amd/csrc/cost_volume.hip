@@ -56,17 +56,10 @@ __device__ __forceinline__ float group_reduce(float v, int lanes_per_group) {
   }
 }
 
-#ifndef CV_WAVES_PER_SIMD
 #define CV_WAVES_PER_SIMD 2
-#endif
-#ifdef CV_PROBE_DUP
-#define CV_DBG_PARAM , unsigned* __restrict__ dbg
-#else
-#define CV_DBG_PARAM
-#endif
 __global__ __launch_bounds__(256, CV_WAVES_PER_SIMD) void cost_volume_kernel(mnerf_scene sc, mnerf_rays R,
                                                           int cond_stride,
-                                                          float* __restrict__ cond CV_DBG_PARAM) {
+                                                          float* __restrict__ cond) {
   const int sub = threadIdx.x & 7;
   const int slot_in_wg = threadIdx.x >> 3;  // 32 sample slots per workgroup
   const int S = R.n_samples;
@@ -165,29 +158,6 @@ __global__ __launch_bounds__(256, CV_WAVES_PER_SIMD) void cost_volume_kernel(mne
       const Bilin b = bilin_setup(u, w_, R.height, R.width);
       const float4* img = reinterpret_cast<const float4*>(sc.images) + (size_t)v * R.height * R.width;
       const float4 t00 = img[b.o00], t01 = img[b.o01], t10 = img[b.o10], t11 = img[b.o11];
-#ifdef CV_PROBE_DUP
-      {  // race probe: the same four taps loaded a second time (opaque addresses); any difference is recorded
-        int o00 = b.o00, o01 = b.o01, o10 = b.o10, o11 = b.o11;
-        asm volatile("" : "+v"(o00), "+v"(o01), "+v"(o10), "+v"(o11));
-        const float4 r00 = img[o00], r01 = img[o01], r10 = img[o10], r11 = img[o11];
-        const bool d0 = t00.x != r00.x || t00.y != r00.y || t00.z != r00.z, d1 = t01.x != r01.x || t01.y != r01.y || t01.z != r01.z,
-                   d2 = t10.x != r10.x || t10.y != r10.y || t10.z != r10.z, d3 = t11.x != r11.x || t11.y != r11.y || t11.z != r11.z;
-        if (dbg && (d0 || d1 || d2 || d3)) {
-          const unsigned k = atomicAdd(dbg, 1u);
-          if (k < 64) {
-            unsigned* o = dbg + 16 + k * 40;
-            o[0] = threadIdx.x & 63, o[1] = (unsigned)ray, o[2] = (unsigned)j, o[3] = (unsigned)v;
-            o[4] = (d0 ? 1u : 0u) | (d1 ? 2u : 0u) | (d2 ? 4u : 0u) | (d3 ? 8u : 0u);
-            o[5] = (unsigned)o00, o[6] = (unsigned)o01, o[7] = (unsigned)o10, o[8] = (unsigned)o11;
-            const float f[24] = {t00.x, t00.y, t00.z, t01.x, t01.y, t01.z, t10.x, t10.y, t10.z, t11.x, t11.y, t11.z,
-                                 r00.x, r00.y, r00.z, r01.x, r01.y, r01.z, r10.x, r10.y, r10.z, r11.x, r11.y, r11.z};
-            for (int q = 0; q < 24; ++q) o[9 + q] = __float_as_uint(f[q]);
-            o[33] = __float_as_uint(b.w00), o[34] = __float_as_uint(b.w01), o[35] = __float_as_uint(b.w10), o[36] = __float_as_uint(b.w11);
-            o[37] = blockIdx.x, o[38] = (unsigned)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-          }
-        }
-      }
-#endif
       const float gx = u * 2.0f - 1.0f, gy = w_ * 2.0f - 1.0f;
       const float m = (gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f) ? 1.0f : 0.0f;
       if (live) {
@@ -205,21 +175,12 @@ __global__ __launch_bounds__(256, CV_WAVES_PER_SIMD) void cost_volume_kernel(mne
   }
 }
 
-// padding of a slot's LDS areas (floats): the stride becomes = 8 (projections) / 4 (cosine sums) mod 32
-// MEASURED (round 4, same box, two runs each): padded 9.78-9.91 ms per frame, unpadded 9.57-9.59 - the conflicts the counters
-// show are not on the kernel's critical path, and the padding costs more than it buys.  Off by default (-DCVW_PAD=1 to try).
-#if defined(CVW_PAD) && CVW_PAD
-#define CVW_PAD_UV(n) ((40 - ((n) & 31)) & 31)
-#define CVW_PAD_CS(n) ((36 - ((n) & 31)) & 31)
-#define CVW_PAD_REC 1
-#else
-#define CVW_PAD_UV(n) 0
-#define CVW_PAD_CS(n) 0
-#define CVW_PAD_REC 0
-#endif
+// LDS floats of the walk's slots.  The slots' areas are NOT padded against bank conflicts: padding them so that the stride becomes
+// = 8 (projections) / 4 (cosine sums) mod 32 measured slower (round 4: 9.78-9.91 against 9.57-9.59 ms per frame) - the conflicts
+// the counters show are not on the kernel's critical path.
 __host__ __device__ inline size_t cvw_lean_lds_floats(int nslot, int seg, int views_kept, int cs_pad) {
   const int uv = seg * views_kept * 2, cs = seg * cs_pad;
-  return (size_t)nslot * ((uv + CVW_PAD_UV(uv)) + (seg * 4 + CVW_PAD_REC) * 4 + (cs + CVW_PAD_CS(cs)));
+  return (size_t)nslot * (uv + seg * 4 * 4 + cs);
 }
 
 // ============================================================================ segment walk (stand-alone kernel)
@@ -238,14 +199,13 @@ __global__ __launch_bounds__(256, (CPL == 16 ? 2 : CVW_WAVES)) void cost_volume_
   const int sumG = sc.n_group[0] + (sc.n_scales > 1 ? sc.n_group[1] : 0);
   const int cs_stride = (sumG + 3) & ~3;                            // cosine sums per segment sample in LDS
   // LDS per slot: projections [js][view](u,v) | walk records [js][view a|b][idx|weights] (float4) | cosine sums [js][cs]
-  // (experiment, CVW_PAD=1: every slot's three areas padded so that the SAME offset in different slots falls into different
-  // LDS banks - the slots of a wave read their walk records / projections / cosine sums at the same offsets in one instruction,
-  // and slot strides of 96, 256 and 192 floats are all = 0 mod 32: the 4.6 conflict cycles per LDS instruction of round 3's
-  // PMC.  Measured slower, see CVW_PAD_* above.)
-  const int uv_str = CVW_SEG * V * 2 + CVW_PAD_UV(CVW_SEG * V * 2), cs_str = CVW_SEG * cs_stride + CVW_PAD_CS(CVW_SEG * cs_stride);
+  // (the slots of a wave read their walk records / projections / cosine sums at the same offsets in one instruction, and slot
+  // strides of 96, 256 and 192 floats are all = 0 mod 32: the 4.6 conflict cycles per LDS instruction of round 3's PMC.  Padding
+  // the areas apart measured slower, see cvw_lean_lds_floats.)
+  const int uv_str = CVW_SEG * V * 2, cs_str = CVW_SEG * cs_stride;
   float* uv_lds = cvw_smem + (size_t)slot * uv_str;
-  float4* wrec_lds = reinterpret_cast<float4*>(cvw_smem + (size_t)NSLOT * uv_str) + (size_t)slot * (CVW_SEG * 4 + CVW_PAD_REC);
-  float* cs_lds = cvw_smem + (size_t)NSLOT * (uv_str + (CVW_SEG * 4 + CVW_PAD_REC) * 4) + slot * cs_str;
+  float4* wrec_lds = reinterpret_cast<float4*>(cvw_smem + (size_t)NSLOT * uv_str) + (size_t)slot * (CVW_SEG * 4);
+  float* cs_lds = cvw_smem + (size_t)NSLOT * (uv_str + CVW_SEG * 4 * 4) + slot * cs_str;
   const int S = R.n_samples;
   const int n_seg = (S + CVW_SEG - 1) / CVW_SEG;
 
@@ -540,6 +500,19 @@ static void cv_pick_kernel(const mnerf_scene* scene, int sumG, int* variant_out,
   *variant_out = variant, *uvpair_out = uvpair;
 }
 
+// One instance of the segment walk.  Its dynamic-LDS cap is set once per device to the most the launch's own check admits (a
+// CU's 160 KiB; the kernel has no static LDS): the cap is only a launch-time check, what a launch uses is its `lds`.
+template <int CPL, bool UVPAIR, bool POSES>
+static void launch_lean(unsigned wgs, size_t lds, void* stream, const mnerf_scene* scene, const mnerf_rays* rays, int cond_stride,
+                        float* cond, int pair_begin, int pair_end) {
+  static std::atomic<unsigned long long> attr_set{0};
+  if (mnerf_once_per_device(attr_set))
+    (void)hipFuncSetAttribute((const void*)cost_volume_lean_kernel<CPL, UVPAIR, POSES>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+  hipLaunchKernelGGL((cost_volume_lean_kernel<CPL, UVPAIR, POSES>), dim3(wgs), dim3(256), lds, (hipStream_t)stream, *scene, *rays,
+                     cond_stride, cond, pair_begin, pair_end);
+}
+
 // the pose-table instance of the cost volume is the 16-lane walk with all views' projections resident (<= 5 views)
 bool mnerf_cost_volume_takes_pose_table(const mnerf_scene* scene) {
   int sumG = 0, variant;
@@ -578,14 +551,9 @@ extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* ray
                 "(cv_variant 3, <= 5 source views; mnerf_render_takes_pose_table tells)");
   if (variant == 5) {
     const size_t lds = cvt_lds_bytes(scene->n_views, sumG);
-    static std::atomic<int> tile_lds_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::atomic<int>& seen = tile_lds_set[dev & 63];
-    if ((int)lds > seen.load(std::memory_order_relaxed)) {
-      (void)hipFuncSetAttribute((const void*)cost_volume_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      seen.store((int)lds, std::memory_order_relaxed);
-    }
+    static std::atomic<unsigned long long> attr_set{0};
+    if (mnerf_once_per_device(attr_set))  // the cap is what cv_pick_kernel admits: half a CU's LDS
+      (void)hipFuncSetAttribute((const void*)cost_volume_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     long long wgs = ((long long)rays->n_rays + 15) / 16;
     int cap = 512;  // two resident workgroups per CU, one contiguous run of ray blocks each
     if (mnerf_tune().cv_grid > 0) cap = mnerf_tune().cv_grid;
@@ -606,21 +574,6 @@ extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* ray
     const int cs_pad = (sumG + 3) & ~3;
     const size_t lds = cvw_lean_lds_floats(nslot, CVW_SEG, uvpair ? 2 : scene->n_views, cs_pad) * sizeof(float);
     MNERF_REQUIRE(lds <= 160 * 1024, MNERF_E_UNSUPPORTED, "mnerf_cost_volume: %d views need %zu B of LDS", scene->n_views, lds);
-    // the LDS attribute is per device and only ever raised: largest request seen per (variant, device)
-    static std::atomic<int> lean_lds_set[3][64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int which = variant == 4 ? 1 : (uvpair ? 2 : 0);
-    std::atomic<int>& seen = lean_lds_set[which][dev & 63];
-    if ((int)lds > seen.load(std::memory_order_relaxed)) {
-      if (which == 1)
-        (void)hipFuncSetAttribute((const void*)cost_volume_lean_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      else if (which == 2)
-        (void)hipFuncSetAttribute((const void*)cost_volume_lean_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      else
-        (void)hipFuncSetAttribute((const void*)cost_volume_lean_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      seen.store((int)lds, std::memory_order_relaxed);
-    }
     long long wgs = ((long long)rays->n_rays + nslot - 1) / nslot;
     // 16-lane walk: ONE ray block per workgroup at every launch size.  A capped grid (4 096 until round 4) gave the workgroups
     // 1 or 2 blocks each whenever the launch was not a multiple of the cap, and the hardware's round-robin placement put the
@@ -630,10 +583,9 @@ extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* ray
     if (mnerf_tune().cv_grid > 0) cap = mnerf_tune().cv_grid;
     if (wgs > cap) wgs = cap;
     const int n_pairs = scene->n_views * (scene->n_views - 1) / 2;
-    if (which == 1)
-      hipLaunchKernelGGL(cost_volume_lean_kernel<16>, dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream,
-                         *scene, *rays, cond_stride, cond, 0, n_pairs);
-    else if (which == 2) {
+    if (variant == 4)
+      launch_lean<16, false, false>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, 0, n_pairs);
+    else if (uvpair) {
       // Many views: one launch per BLOCK of view pairs over all rays, so that the maps a launch gathers from fit the 256 MiB
       // Infinity Cache (cv_walk.hpp "PAIR BLOCKS"; 8 pairs x 2 sides x 13.1 MB at 512x640 = 210 MB).  Same stream: the blocks
       // run in order, each continues the cosine sums the previous one left in the rows.  MNERF_CV_PAIR_BLOCK: pairs per
@@ -641,30 +593,14 @@ extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* ray
       const int pb = mnerf_tune().cv_pair_block;
       const int blk = pb > 0 ? pb : (pb < 0 ? 8 : n_pairs);  // (-1 = default: 8 pairs per launch of the walk)
       for (int p0 = 0; p0 < n_pairs; p0 += blk)
-        hipLaunchKernelGGL((cost_volume_lean_kernel<8, true>), dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream,
-                           *scene, *rays, cond_stride, cond, p0, p0 + blk < n_pairs ? p0 + blk : n_pairs);
-    } else if (poses) {
-      static std::atomic<int> pose_lds_set[64];
-      std::atomic<int>& pseen = pose_lds_set[dev & 63];
-      if ((int)lds > pseen.load(std::memory_order_relaxed)) {
-        (void)hipFuncSetAttribute((const void*)cost_volume_lean_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        pseen.store((int)lds, std::memory_order_relaxed);
-      }
-      hipLaunchKernelGGL((cost_volume_lean_kernel<8, false, true>), dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream,
-                         *scene, *rays, cond_stride, cond, 0, n_pairs);
-    } else
-      hipLaunchKernelGGL(cost_volume_lean_kernel<8>, dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream,
-                         *scene, *rays, cond_stride, cond, 0, n_pairs);
+        launch_lean<8, true, false>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, p0, p0 + blk < n_pairs ? p0 + blk : n_pairs);
+    } else if (poses)
+      launch_lean<8, false, true>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, 0, n_pairs);
+    else
+      launch_lean<8, false, false>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, 0, n_pairs);
   } else {
-#ifdef CV_PROBE_DUP
-    unsigned* dbg = nullptr;
-    if (const char* e = getenv("MNERF_CVDBG_PTR")) dbg = (unsigned*)strtoull(e, nullptr, 0);
-    hipLaunchKernelGGL(cost_volume_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       *scene, *rays, cond_stride, cond, dbg);
-#else
     hipLaunchKernelGGL(cost_volume_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        *scene, *rays, cond_stride, cond);
-#endif
   }
   return mnerf_check_launch("mnerf_cost_volume");
 }

@@ -274,21 +274,11 @@ __device__ __forceinline__ void cvm_weights(const CvmTap& t, int p, int xb, int 
   bl = __builtin_bit_cast(cvm_h8, Lo);
 }
 
-#if CVM_EXP == 5
-__device__ __forceinline__ cvm_f16 cvm_mfma(cvm_h8 a, cvm_h8 b, cvm_f16 c) {
-  c[0] += (float)a[0] * (float)b[0], c[5] += (float)a[2] * (float)b[3], c[9] += (float)a[4] * (float)b[5], c[14] += (float)a[6] * (float)b[7];
-  return c;
-}
-#else
 __device__ __forceinline__ cvm_f16 cvm_mfma(cvm_h8 a, cvm_h8 b, cvm_f16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-#endif
 
 // A operands of a chunk for this lane (lanes 0-31: row pair p, lanes 32-63: row pair p + 1): + 1024 column + 512 (hi | lo) +
 // 128 channel tile.  Wave-uniform part (scalar registers) + the lane's offset inside the chunk (one register per side)
 __device__ __forceinline__ const char* cvm_chunk_base(const CvmSide& s, int p, int xb) {
-#if CVM_EXP == 6
-  return s.map + (size_t)((unsigned)((p & 1) * s.rs + (xb & 3)) * (unsigned)CVM_COL_BYTES);
-#endif
   return s.map + (size_t)((unsigned)(p * s.rs + xb) * (unsigned)CVM_COL_BYTES);
 }
 __device__ __forceinline__ unsigned cvm_lane_off(int rs, int n, int half) {
@@ -370,9 +360,6 @@ __device__ __forceinline__ void cvm_dots(const cvm_f16& fa, const cvm_f16& fb, f
 #pragma unroll
   for (int g2 = 0; g2 < 2; ++g2) {
     const int r0 = 8 * g2;
-#if CVM_EXP == 4
-    dot[g2] = fa[r0] + fb[r0 + 1], na[g2] = fa[r0 + 2], nb[g2] = fb[r0 + 3];
-#else
     float d = fa[r0] * fb[r0], a = fa[r0] * fa[r0], b = fb[r0] * fb[r0];
 #pragma unroll
     for (int r = 1; r < 8; ++r) {
@@ -381,7 +368,6 @@ __device__ __forceinline__ void cvm_dots(const cvm_f16& fa, const cvm_f16& fb, f
       b = __builtin_fmaf(fb[r0 + r], fb[r0 + r], b);
     }
     dot[g2] = d, na[g2] = a, nb[g2] = b;
-#endif
   }
 }
 
@@ -505,18 +491,8 @@ __host__ __device__ inline size_t cvm_wave_lds_bytes(int n_views, int n_scales, 
   return (size_t)n_views * 32 * 8 + items * (32 * 16 + 32 * 4 + 16) + (stage_rows ? (size_t)32 * cond_stride * 4 : 0);
 }
 
-#ifndef CVM_WAVES_PER_SIMD
 #define CVM_WAVES_PER_SIMD 2
-#endif
-#ifndef CVM_WG_WAVES
 #define CVM_WG_WAVES 4  // waves per workgroup: wave w runs on SIMD w % 4, so waves w and w + 4 share a SIMD
-#endif
-#ifndef CVM_EXP
-#define CVM_EXP 0  // timing experiments (tools/exp): 1 no row write-out, 2 no colour taps, 3 no units, 4 no dot products, 5 no matrix instructions, 6 cached operands, 8 no direct row writes (many views)
-#endif
-#ifndef CVM_PRIO
-#define CVM_PRIO 0
-#endif
 // -DCVM_STATS (tools/exp/cvmm_stats.py): per-phase s_memtime sums of every wave, added into the buffer MNERF_CVDBG_PTR names
 #ifdef CVM_STATS
 #define CVM_DBG_PARAM , unsigned long long* __restrict__ dbg
@@ -547,12 +523,6 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
   const cvm_u4* lut = reinterpret_cast<const cvm_u4*>(cvm_smem);
   cvm_lut_init(reinterpret_cast<unsigned*>(cvm_smem));
   __syncthreads();
-#if CVM_PRIO
-  // The two waves of a SIMD run the same program and start together; with equal priority the arbiter alternates between them
-  // and they stay in phase - both in their matrix runs, then both in their dot products - so neither pipe overlaps the other.
-  // A fixed priority for the second team lets it run as if alone and the first team fill whichever pipe it leaves free.
-  if (wave >= CVM_WG_WAVES / 2) __builtin_amdgcn_s_setprio(3);
-#endif
   char* wl = cvm_smem + CVM_LUT_BYTES + (size_t)wave * cvm_wave_lds_bytes(V, NS, cond_stride, grid.stage_rows);
   float2* uv = reinterpret_cast<float2*>(wl);                                     // [V][32]
   cvm_u4* tapw = reinterpret_cast<cvm_u4*>(wl + (size_t)V * 256);                 // [items][32]
@@ -575,11 +545,7 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
   const int pix = min(py, H - 1) * W + min(px, W - 1);
   const int ray_geo = pix - R.ray_begin;                                           // make_ray: pixel = ray_begin + ray
   const int ray = max(0, min(ray_geo, R.n_rays - 1));                              // rows / stratified offsets: a ray of the launch
-#if CVM_EXP == 8  // no direct row writes (many views)
-  const bool row_wr = grid.stage_rows;
-#else
   const bool row_wr = grid.stage_rows || (px < W && py < H && ray_geo >= 0 && ray_geo < R.n_rays);  // direct rows: live rays only
-#endif
   const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
   const int G0 = sc.n_group[0], G1 = NS > 1 ? sc.n_group[1] : 0;
   const int sumG = G0 + G1;
@@ -609,11 +575,7 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
       if (row_wr && first_block) {  // (a later pair block only needs the projections)
         const Bilin b = bilin_setup(u, w_, H, W);
         const float4* img = reinterpret_cast<const float4*>(sc.images) + (size_t)v * H * W;
-#if CVM_EXP == 2
-        const float4 t00 = make_float4(u, w_, z, 0.f), t01 = t00, t10 = t00, t11 = t00;
-#else
         const float4 t00 = img[b.o00], t01 = img[b.o01], t10 = img[b.o10], t11 = img[b.o11];
-#endif
         const float gx = u * 2.0f - 1.0f, gy = w_ * 2.0f - 1.0f;
         const float m = (gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f) ? 1.0f : 0.0f;
         out[sumG + 3 * v + 0] = bilin4(t00.x, t01.x, t10.x, t11.x, b);
@@ -734,11 +696,7 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) cvm_load_ct(ha[ct], la[ct], fa_, ct), cvm_load_ct(hb[ct], lb[ct], fb_, ct);
     }
-#if CVM_EXP == 3
-    const int n_units = 0;
-#else
     const int n_units = (grid.pair_end - grid.pair_begin) * NS;
-#endif
     // one unit; REQ: not the depth index's last one - the next unit's sides are looked up and their operands requested
     auto unit = [&](auto req_tag) {
       constexpr bool REQ = decltype(req_tag)::value;
@@ -790,22 +748,16 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
     // the 32 rows leave as 16-byte pieces, consecutive lanes on consecutive pieces of a row (a row is cond_stride / 4 pieces:
     // the scattered 4-byte stores of one value per lane cost the memory pipeline ~20 instructions of 32 partial lines each)
     cvw_handoff();
-    if (grid.stage_rows && CVM_EXP != 1) {
+    if (grid.stage_rows) {
       const int ppr = cond_stride >> 2;  // pieces per row (cond_stride is a multiple of 8)
       const int ppr_sh = (ppr & (ppr - 1)) == 0 ? __builtin_ctz(ppr) : -1;  // a power of two: shifts instead of a division
       for (int c = lane; c < 32 * ppr; c += 64) {
         const int r = ppr_sh >= 0 ? c >> ppr_sh : c / ppr, part = c - r * ppr;
         const int rpx = txi * 8 + (r & 7), rpy = (grid.tile_y0 + tyi) * 4 + (r >> 3);
         const int rpix = rpy * W + rpx;
-#if CVM_EXP == 7  // same bytes, one contiguous block per wave and depth index (is it the access pattern?)
-        if (rpx < W && rpy < H && rpix >= R.ray_begin && rpix < R.ray_begin + R.n_rays)
-          *reinterpret_cast<v4f*>(cond + (((size_t)tile * S + j) * 32) * cond_stride + 4 * c) =
-              *reinterpret_cast<const v4f*>(rows + r * cond_stride + 4 * part);
-#else
         if (rpx < W && rpy < H && rpix >= R.ray_begin && rpix < R.ray_begin + R.n_rays)
           *reinterpret_cast<v4f*>(cond + ((size_t)(rpix - R.ray_begin) * S + j) * cond_stride + 4 * part) =
               *reinterpret_cast<const v4f*>(rows + r * cond_stride + 4 * part);
-#endif
       }
     }
     CVM_T(6)
@@ -886,14 +838,9 @@ int mnerf_cost_volume_mm_launch(const mnerf_scene* scene, const mnerf_rays* rays
                   2 * (CVM_LUT_BYTES + CVM_WG_WAVES * cvm_wave_lds_bytes(scene->n_views, scene->n_scales, cond_stride, 0)) > 160 * 1024);
   const size_t lds = CVM_LUT_BYTES + CVM_WG_WAVES * cvm_wave_lds_bytes(scene->n_views, scene->n_scales, cond_stride, g.stage_rows);
   MNERF_REQUIRE(lds <= 160 * 1024, MNERF_E_UNSUPPORTED, "mnerf_cost_volume: %d views need %zu B of LDS", scene->n_views, lds);
-  static std::atomic<int> lds_set[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<int>& seen = lds_set[dev & 63];
-  if ((int)lds > seen.load(std::memory_order_relaxed)) {
-    (void)hipFuncSetAttribute((const void*)cost_volume_mm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    seen.store((int)lds, std::memory_order_relaxed);
-  }
+  static std::atomic<unsigned long long> attr_set{0};
+  if (mnerf_once_per_device(attr_set))  // the cap is what the check above admits (the kernel has no static LDS)
+    (void)hipFuncSetAttribute((const void*)cost_volume_mm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #ifdef CVM_STATS
   unsigned long long* dbg = nullptr;
   if (const char* e = getenv("MNERF_CVDBG_PTR")) dbg = (unsigned long long*)strtoull(e, nullptr, 0);

@@ -1,5 +1,5 @@
 // Shared device code of the cost volume (K1+K2): bilinear set-up and the register-quad segment walk.
-// Included by cost_volume.hip (stand-alone kernel, 16-sample walks, rows to global memory) and by decoder.hip
+// Included by cost_volume.hip (stand-alone kernel, 16-sample walks, rows to global memory) and by decoder_staged.hpp
 // (fused ray-chunk kernel: the workgroup produces the conditioning rows of its own tile in LDS, 8-sample walks).
 #pragma once
 #include "common.hpp"
@@ -76,12 +76,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // result in lanes 48-63 now and then while ANOTHER wave of the same SIMD issues v_mfma_f32_32x32x16_{f16,bf16} — the
 // one-launch ray chunk (walk and MFMA trunk in co-resident workgroups) and this kernel next to the decoder on a second
 // stream both produced a few wrong conditioning rows per launch, always in the last 16 lanes of a wave, one walk step at a
-// time; never next to the exact-f32 decoder, never alone, never in this form.  The packed form (CVW_PK=1, probe builds) is
+// time; never next to the exact-f32 decoder, never alone, never in this form.  The packed form is
 // not faster either: the kernel is bound by the texture-address unit (9.9 vs 10.1 ms per frame).
-#ifndef CVW_PK
-#define CVW_PK 0
-#endif
-#if !CVW_PK
 __device__ __forceinline__ float cvw_opaque(float x) {
   asm volatile("" : "+v"(x));
   return x;
@@ -90,10 +86,6 @@ __device__ __forceinline__ v2f pk_mul(v2f a, v2f b) { return v2f{cvw_opaque(a.x 
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) {
   return v2f{cvw_opaque(__builtin_fmaf(a.x, b.x, c.x)), cvw_opaque(__builtin_fmaf(a.y, b.y, c.y))};
 }
-#else
-__device__ __forceinline__ v2f pk_mul(v2f a, v2f b) { return a * b; }
-__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-#endif
 
 // pass-1 record of one (sample, view, scale).  The four taps of a quad are kept in four register
 // sets named by the PARITY of the texel's row and column (E/O), not by their position in the quad:
@@ -133,31 +125,15 @@ __device__ __forceinline__ TapRec tap_setup(float u, float v, int h, int w) {
   return tap_setup_xy(u, v, h, w, x0, y0);
 }
 
-#ifndef CVW_RELOAD_ANY
-#define CVW_RELOAD_ANY 0
-#endif
-#ifndef CVW_PROBE
-#define CVW_PROBE 0  // race probes (tools/exp/race_probe.py): 3 shuffles instead of DPP, 4 unconditional tap reloads,
-#endif               // 5 / 7 hard waits at the slot-local LDS hand-offs, 6 no LDS atomic
 // slot-local LDS hand-off between lanes of one wave
 __device__ __forceinline__ void cvw_handoff() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#if CVW_PROBE == 5 || CVW_PROBE == 7
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-#endif
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-#ifndef CVW_SEG
 #define CVW_SEG 16  // samples per walk of the stand-alone kernel (the fused ray-chunk kernel walks 8)
-#endif
 #define CVW_CS_MAX 16  // cosine sums per sample the walk kernel supports (sum of groups)
-#ifndef CVW_FAST_COS
-#define CVW_FAST_COS 0
-#endif
-#ifndef CVW_WAVES
 #define CVW_WAVES 4  // 128 VGPRs; LDS (40 KB/workgroup at 3 views) allows 4 workgroups per CU
-#endif
 
 template <int CPL>  // CPL = channels per lane (8 -> 16 lanes per sample, 16 -> 8 lanes per sample)
 struct PairQuad {
@@ -176,11 +152,6 @@ __device__ __forceinline__ void tap_load(v2f (&t)[CPL / 2], const float* __restr
     t[2 * k] = a.lo;
     t[2 * k + 1] = a.hi;
   }
-#ifdef CVW_DEBUG_WAIT
-  // probe build: every tap load is complete before anything else is issued (would hide a result consumed early)
-#pragma unroll
-  for (int k = 0; k < CPL / 2; ++k) asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[k]) : : "memory");
-#endif
 }
 
 // Tile form (cost_volume_tile_kernel): the texels a 16-ray x SEG-sample tile touches in the two maps of a (pair, scale) are
@@ -228,24 +199,6 @@ template <int CPL>
 __device__ __forceinline__ void quad_update(PairQuad<CPL>& q, const float* __restrict__ map, const float4 ix,
                                             unsigned lane_bytes) {
   const int i00 = __float_as_int(ix.x), i01 = __float_as_int(ix.y), i10 = __float_as_int(ix.z), i11 = __float_as_int(ix.w);
-#if CVW_PROBE == 4
-  tap_load<CPL>(q.t[0][0], map, i00, lane_bytes);
-  tap_load<CPL>(q.t[0][1], map, i01, lane_bytes);
-  tap_load<CPL>(q.t[1][0], map, i10, lane_bytes);
-  tap_load<CPL>(q.t[1][1], map, i11, lane_bytes);
-  return;
-#endif
-#if CVW_RELOAD_ANY
-  // A tap set is reloaded by the WHOLE wave as soon as ANY of its slots has crossed a texel boundary: the texture-address
-  // unit charges a load instruction 16 cycles whatever its lane mask (tools/exp/ta_mask.hip), and the four slots of a wave
-  // cross at different steps, so per-slot reloads are four quarter-full instructions where one full one does (the slots
-  // that had not moved re-read their texel from L1).
-  if (__builtin_amdgcn_ballot_w64(i00 != q.idx[0][0])) { tap_load<CPL>(q.t[0][0], map, i00, lane_bytes); q.idx[0][0] = i00; }
-  if (__builtin_amdgcn_ballot_w64(i01 != q.idx[0][1])) { tap_load<CPL>(q.t[0][1], map, i01, lane_bytes); q.idx[0][1] = i01; }
-  if (__builtin_amdgcn_ballot_w64(i10 != q.idx[1][0])) { tap_load<CPL>(q.t[1][0], map, i10, lane_bytes); q.idx[1][0] = i10; }
-  if (__builtin_amdgcn_ballot_w64(i11 != q.idx[1][1])) { tap_load<CPL>(q.t[1][1], map, i11, lane_bytes); q.idx[1][1] = i11; }
-  return;
-#endif
   if (i00 != q.idx[0][0]) { tap_load<CPL>(q.t[0][0], map, i00, lane_bytes); q.idx[0][0] = i00; }
   if (i01 != q.idx[0][1]) { tap_load<CPL>(q.t[0][1], map, i01, lane_bytes); q.idx[0][1] = i01; }
   if (i10 != q.idx[1][0]) { tap_load<CPL>(q.t[1][0], map, i10, lane_bytes); q.idx[1][0] = i10; }
@@ -271,11 +224,6 @@ __device__ __forceinline__ float dpp_add(float v) {
 // all-reduce over LPG adjacent lanes (LPG | 16, aligned): same pairing tree as the xor butterfly
 template <int LPG>
 __device__ __forceinline__ float dpp_group_sum(float v) {
-#if CVW_PROBE == 3
-#pragma unroll
-  for (int m = 1; m < LPG; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-#endif
   if (LPG >= 2) v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
   if (LPG >= 4) v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
   if (LPG >= 8) v = dpp_add<0x141>(v);  // row_half_mirror
@@ -335,20 +283,10 @@ __device__ __forceinline__ void lean_walk(const float* __restrict__ m0, const fl
       k_nb = nb;
     }
     if (u == LPG - 1) {
-#if CVW_FAST_COS
-      // 1-ulp hardware sqrt / rcp instead of the correctly rounded sequences: |error| <= ~3 ulp of a cosine
-      const float da = fmaxf(__builtin_amdgcn_sqrtf(k_na), 1e-8f), db = fmaxf(__builtin_amdgcn_sqrtf(k_nb), 1e-8f);
-      const float c = k_dot * __builtin_amdgcn_rcpf(da * db);
-#else
       const float da = fmaxf(sqrtf(k_na), 1e-8f), db = fmaxf(sqrtf(k_nb), 1e-8f);
       const float c = k_dot / (da * db);
-#endif
       const int js_mine = js - (LPG - 1) + (sub & (LPG - 1));
-#if CVW_PROBE == 6
-      cs_group[js_mine * cs_stride] += c;
-#else
       __hip_atomic_fetch_add(cs_group + js_mine * cs_stride, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
     }
   }
 }
@@ -487,10 +425,6 @@ __device__ __forceinline__ void cv_pass1(const mnerf_scene& sc, const mnerf_rays
       const Bilin b = bilin_setup(u, w_, R.height, R.width);
       const float4* img = reinterpret_cast<const float4*>(sc.images) + (size_t)v * R.height * R.width;
       float4 t00 = img[b.o00], t01 = img[b.o01], t10 = img[b.o10], t11 = img[b.o11];
-#if CVW_PROBE == 9
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 7" : "+v"(t00.x), "+v"(t00.y), "+v"(t00.z), "+v"(t01.x), "+v"(t01.y), "+v"(t01.z),
-                   "+v"(t10.x), "+v"(t10.y), "+v"(t10.z), "+v"(t11.x), "+v"(t11.y), "+v"(t11.z) : : "memory");
-#endif
       const float gx = u * 2.0f - 1.0f, gy = w_ * 2.0f - 1.0f;
       const float m = (gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f) ? 1.0f : 0.0f;
       if (live) {

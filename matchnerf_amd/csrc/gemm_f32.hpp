@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void gemm_f32_tile128_kernel(GemmArgs g) {
 // Every fp32 operand element is three bf16 terms (hi + mid + lo = the fp32 value exactly for |x| >= 2^-100: 3 x 8 significand bits;
 // below that the third term sinks into the subnormals and the value keeps >= 16 bits: tests/test_split_bf16_cpu.py), a product is
 // accumulated in fp32 from the six term products that are not below 2^-24 of it (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi;
-// the scheme of the decoder's "bf16x6" matrix path, decoder.hip) on v_mfma_f32_32x32x16_bf16: 16 K-elements per 32-cycle
+// the scheme of the decoder's "bf16x6" matrix path, decoder_common.hpp) on v_mfma_f32_32x32x16_bf16: 16 K-elements per 32-cycle
 // instruction against 2 for the exact-f32 one, i.e. 8/6 x 2 = 2.7 x its rate, with fp32's exponent range (no scaling, unlike the
 // split-fp16 form) and fp32-grade results (tests/test_gemm_gpu.py: error against float64 at the level of an fp32 FMA chain).
 // The operands are split ONCE per tile load — each element then serves 128 rows / columns of the tile — and wait in LDS as
@@ -449,12 +449,8 @@ __global__ __launch_bounds__(256) void gemm_h3_kernel(GemmArgs g, int a_vec, int
   }
 }
 
-#ifndef MNERF_GEMM_TILE128
 #define MNERF_GEMM_TILE128 1  // 0: every product through the 64 x 64 kernel (round 3)
-#endif
-#ifndef MNERF_GEMM_DEFAULT_MATH
 #define MNERF_GEMM_DEFAULT_MATH 1
-#endif
 // MNERF_GEMM_MATH (environment, read once): "bf16x6" (default) = split-bf16, "f16x3" = split-fp16 with row gains (round 6: half the
 // matrix instructions, but its pre-pass reads the operands a second time and these products are bound by operand fetch and split,
 // not by the matrix pipe: 35.6 against 34.5 ms per training iteration - kept selectable and tested, not the default), both on the

@@ -5,7 +5,7 @@
 //           on the caller's stream.  The default: measured 2x FASTER than the fused form on MI355X —
 //           the register-quad walk of the cost volume needs ~16 waves per CU to hide its load latency, which the
 //           stand-alone kernel has and four producer waves inside a 256-VGPR MFMA workgroup do not;
-//   fused   ONE launch of the ray-chunk kernel (decoder.hip, CVF = 1): every workgroup produces the conditioning rows
+//   fused   ONE launch of the ray-chunk kernel (decoder_fused.hip, CVF = 1): every workgroup produces the conditioning rows
 //           of its own tile in LDS and consumes them there; `workspace` is not touched.  mnerf_render_chunk_fused,
 //           or mnerf_render_chunk with MNERF_RENDER_FUSED=1 in the environment at load time, wherever the
 //           configuration fits (split-fp16 stream, S <= 128, <= 5 views: mnerf_render_chunk_is_fused).

@@ -120,9 +120,8 @@ __device__ __forceinline__ void glds16_sv4(const float* uniform_base, unsigned l
 
 // glds16_s for data read exactly once (the conditioning rows): non-temporal, so that the stream does not push the weight
 // segments and the register-spill scratch out of L2 (ping-pong decoder, MI355X: FETCH_SIZE 462 -> 212 MB per 65 536-ray launch,
-// L2 misses 40 M -> 17 M, 18.27 -> 17.93 ms per frame; -DMNERF_ROWS_TEMPORAL restores the plain form).
+// L2 misses 40 M -> 17 M, 18.27 -> 17.93 ms per frame).
 __device__ __forceinline__ void glds16_s_stream(const float* uniform_src, unsigned lane_off_bytes, unsigned lds_byte_addr) {
-#ifndef MNERF_ROWS_TEMPORAL
   unsigned keep;
   asm volatile(
       "s_nop 4\n\t"
@@ -134,9 +133,6 @@ __device__ __forceinline__ void glds16_s_stream(const float* uniform_src, unsign
       : "=&s"(keep)
       : "v"(lane_off_bytes), "s"(uniform_src), "s"(lds_byte_addr)
       : "memory");
-#else
-  glds16_s(uniform_src, lane_off_bytes, lds_byte_addr);
-#endif
 }
 
 __device__ __forceinline__ void segment_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -209,30 +205,17 @@ __device__ __forceinline__ float resid_hi(float v, float mult, unsigned hpk) {
 // v * mult (mult a power of two) -> fp16 hi (RNE) + fp16 lo of the exact fp32 residual: 6 VALU ops per pair of values
 // (2 x v_mul_f32, v_cvt_pk_f16_f32, 2 x v_fma_mix_f32, v_cvt_pk_f16_f32; 5 with v_pk_mul_f32 before packed fp32 was banned from
 // the library, build.py: NO_PACKED_F32).
-// -DMNERF_SPLIT_MIX: the same values (bit for bit, measured) from FOUR "mix" FMAs per pair that write one fp16 half each,
-//   hi.lo16 = f16(v0 * mult + 0)  v_fma_mixlo_f16      lo.lo16 = f16(v0 * mult - hi.lo)  v_fma_mixlo_f16
-//   hi.hi16 = f16(v1 * mult + 0)  v_fma_mixhi_f16      lo.hi16 = f16(v1 * mult - hi.hi)  v_fma_mixhi_f16
-// 1 000 fewer vector instructions per decoder tile - and SLOWER on MI355X: 18.99 vs 18.51 ms per frame (the half-writing forms
-// are read-modify-write on their destination and evidently cost more than one issue slot).  Kept as a build-time experiment.
+// (The same values from FOUR v_fma_mix{lo,hi}_f16 per pair, each writing one fp16 half, are 1 000 fewer vector instructions per
+// decoder tile and SLOWER on MI355X, 18.99 vs 18.51 ms per frame: the half-writing forms are read-modify-write on their destination.)
 __device__ __forceinline__ PartsH split8h(const float (&v)[8], float mult) {
   u32x4 H, L;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-#ifndef MNERF_SPLIT_MIX
     const f32x2 ab = {v[2 * i] * mult, v[2 * i + 1] * mult};
     const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(ab, f16x2));  // v_cvt_pk_f16_f32
     const f32x2 r = {resid_lo(v[2 * i], mult, h), resid_hi(v[2 * i + 1], mult, h)};
     H[i] = h;
     L[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-#else
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "=v"(h) : "v"(v[2 * i]), "v"(mult));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(h) : "v"(v[2 * i + 1]), "v"(mult));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(v[2 * i]), "v"(mult), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(v[2 * i + 1]), "v"(mult), "v"(h));
-    H[i] = h;
-    L[i] = l;
-#endif
   }
   PartsH p;
   p.hi = __builtin_bit_cast(f16x8, H);
@@ -243,13 +226,6 @@ __device__ __forceinline__ PartsH split8h(const float (&v)[8], float mult) {
 __device__ __forceinline__ f32x16 mfma16h(f16x8 a, f16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
-// Diagnostic build (-DMNERF_ONE_PRODUCT, tools/exp/one_product.sh; never shipped): the two cross products hi.lo and lo.hi are
-// skipped, i.e. plain fp16 operands with fp32 accumulation — how much of the kernel's time is the 3x split tax?
-#ifdef MNERF_ONE_PRODUCT
-#define MFMA16H_CROSS(a_, b_, c_) (c_)
-#else
-#define MFMA16H_CROSS(a_, b_, c_) mfma16h(a_, b_, c_)
-#endif
 
 // exponent em with 2^em * m in [2^14, 2^15) (m > 0; clamped so that every scale stays a normal fp32 number)
 __device__ __forceinline__ int gain_exp(float m) {
@@ -304,8 +280,8 @@ __device__ __forceinline__ void ksteps_h(f32x16 (&acc)[NMB], unsigned base_lds, 
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("" : "+v"(ch), "+v"(cl));  // ONE wait for both fragments, in front of the three dependent MFMAs (see ksteps_presplit2)
       const f16x8 ah = __builtin_bit_cast(f16x8, ch), al = __builtin_bit_cast(f16x8, cl);
-      acc[m] = MFMA16H_CROSS(ah, b.lo, acc[m]);
-      acc[m] = MFMA16H_CROSS(al, b.hi, acc[m]);
+      acc[m] = mfma16h(ah, b.lo, acc[m]);
+      acc[m] = mfma16h(al, b.hi, acc[m]);
       acc[m] = mfma16h(ah, b.hi, acc[m]);
       __builtin_amdgcn_sched_barrier(0);
       ch = nh;
@@ -330,8 +306,8 @@ __device__ __forceinline__ void ksteps_presplit(f32x16 (&acc)[NMB], unsigned bas
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("" : "+v"(ch), "+v"(cl));
       const f16x8 ah = __builtin_bit_cast(f16x8, ch), al = __builtin_bit_cast(f16x8, cl);
-      acc[m] = MFMA16H_CROSS(ah, b[u].lo, acc[m]);
-      acc[m] = MFMA16H_CROSS(al, b[u].hi, acc[m]);
+      acc[m] = mfma16h(ah, b[u].lo, acc[m]);
+      acc[m] = mfma16h(al, b[u].hi, acc[m]);
       acc[m] = mfma16h(ah, b[u].hi, acc[m]);
       __builtin_amdgcn_sched_barrier(0);
       ch = nh;
@@ -344,55 +320,7 @@ __device__ __forceinline__ void ksteps_presplit(f32x16 (&acc)[NMB], unsigned bas
 // across a segment boundary (units [0, NS0 NMB) at base0, the rest at base1): with one unit of look-ahead (96 cycles of
 // matrix work) every unit waited for its ds_read_b128 pair (measured: 4.4-5.3 k cycles for the 96 instructions of a layer
 // against 3.1 k of issue time).
-#ifndef MNERF_PP_DEPTH
 #define MNERF_PP_DEPTH 2  // units of look-ahead of the fragment reads (each unit in flight holds 8 registers)
-#endif
-#ifndef MNERF_PP_GROUP2
-#define MNERF_PP_GROUP2 0  // experiment: the fragments of TWO units requested together (4 ds_read_b128 every second unit): half as
-#endif                     // many interruptions of the matrix-instruction stream, each twice as long
-#if MNERF_PP_GROUP2
-template <int NMB, int NS0, int NS1>
-__device__ __forceinline__ void ksteps_presplit2(f32x16 (&acc)[NMB], unsigned base0_lds, unsigned base1_lds, int lane,
-                                                 const PartsH* b) {
-  constexpr int N0 = NS0 * NMB, N = (NS0 + NS1) * NMB, NP = (N + 1) / 2;
-  lds_u32x4_cptr a0 = (lds_u32x4_cptr)(size_t)base0_lds + lane;
-  lds_u32x4_cptr a1 = (lds_u32x4_cptr)(size_t)base1_lds + lane;
-  u32x4 fh[2][2], fl[2][2];  // [pair buffer][unit of the pair]
-  auto fetch = [&](int pr, int buf) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int i = 2 * pr + q;
-      if (i >= N) break;
-      if (i < N0) {
-        fh[buf][q] = a0[i * 128];
-        fl[buf][q] = a0[i * 128 + 64];
-      } else {
-        fh[buf][q] = a1[(i - N0) * 128];
-        fl[buf][q] = a1[(i - N0) * 128 + 64];
-      }
-    }
-  };
-  fetch(0, 0);
-#pragma unroll
-  for (int pr = 0; pr < NP; ++pr) {
-    if (pr + 1 < NP) fetch(pr + 1, (pr + 1) & 1);
-    __builtin_amdgcn_sched_barrier(0);
-    const int bf = pr & 1;
-    asm volatile("" : "+v"(fh[bf][0]), "+v"(fl[bf][0]), "+v"(fh[bf][1]), "+v"(fl[bf][1]));
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int i = 2 * pr + q;
-      if (i >= N) break;
-      const int u = i / NMB, m = i % NMB;
-      const f16x8 ah = __builtin_bit_cast(f16x8, fh[bf][q]), al = __builtin_bit_cast(f16x8, fl[bf][q]);
-      acc[m] = MFMA16H_CROSS(ah, b[u].lo, acc[m]);
-      acc[m] = MFMA16H_CROSS(al, b[u].hi, acc[m]);
-      acc[m] = mfma16h(ah, b[u].hi, acc[m]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-#else
 // `hook(i, lane_addr, lane_addr_base)` runs behind the three matrix instructions of unit i (i is a constant after unrolling): the
 // place where a wave can issue something else — a weight request — at the lowest cost (tools/exp/ubench/mfma_issue.hip: ~50
 // cycles per LDS-DMA request among matrix instructions against ~95 in a vector phase).  lane_addr = lane_addr_base + 16 lane is
@@ -435,8 +363,8 @@ __device__ __forceinline__ void ksteps_presplit2(f32x16 (&acc)[NMB], unsigned ba
     else asm volatile("" : "+v"(fh[i % NB]));
     const f16x8 ah = __builtin_bit_cast(f16x8, fh[i % NB]), al = __builtin_bit_cast(f16x8, NP == 3 ? fl[i % NB] : fh[i % NB]);
     if constexpr (NP == 3) {
-      acc[m] = MFMA16H_CROSS(ah, b[u].lo, acc[m]);
-      acc[m] = MFMA16H_CROSS(al, b[u].hi, acc[m]);
+      acc[m] = mfma16h(ah, b[u].lo, acc[m]);
+      acc[m] = mfma16h(al, b[u].hi, acc[m]);
     }
     acc[m] = mfma16h(ah, b[u].hi, acc[m]);
     __builtin_amdgcn_sched_barrier(0);
@@ -444,7 +372,6 @@ __device__ __forceinline__ void ksteps_presplit2(f32x16 (&acc)[NMB], unsigned ba
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-#endif  // MNERF_PP_GROUP2
 
 // The same again with the two output blocks of a pair (m, m+1) interleaved: a0 a1 a0 a1 a0 a1 instead of a0 a0 a0 a1 a1 a1,
 // so that no matrix instruction has the accumulator of its predecessor (every accumulator still receives its three products
@@ -519,8 +446,8 @@ __device__ __forceinline__ void ksteps_presplit2_dma(f32x16 (&acc)[NMB], unsigne
     __builtin_amdgcn_sched_barrier(0);
     const int u = i / NMB, m = i % NMB;
     const f16x8 ah = __builtin_bit_cast(f16x8, fh[i % 3]), al = __builtin_bit_cast(f16x8, fl[i % 3]);
-    acc[m] = MFMA16H_CROSS(ah, b[u].lo, acc[m]);
-    acc[m] = MFMA16H_CROSS(al, b[u].hi, acc[m]);
+    acc[m] = mfma16h(ah, b[u].lo, acc[m]);
+    acc[m] = mfma16h(al, b[u].hi, acc[m]);
     acc[m] = mfma16h(ah, b[u].hi, acc[m]);
     __builtin_amdgcn_sched_barrier(0);
     // pieces k with floor(k N / K) == i go out behind unit i

@@ -28,7 +28,7 @@
 
 #include "wa_common.hpp"
 
-// ---- LDS-DMA helpers (see decoder.hip: an asm global_load_lds is invisible to hipcc's
+// ---- LDS-DMA helpers (see decoder_common.hpp: an asm global_load_lds is invisible to hipcc's
 // wait-count bookkeeping, so the prefetch of tile t+1 is not drained in front of tile t's reads)
 __device__ __forceinline__ void wa_glds16(const float* gsrc, unsigned lds_byte_addr) {
   unsigned keep;
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_kernel(
 
 // ============================================================================ split-bf16 variant
 // Same flash-style loop with the products on v_mfma_f32_32x32x16_bf16: every fp32 operand is split into
-// three bf16 terms and a product is accumulated in fp32 from six terms (decoder.hip, "split-bf16 matrix
+// three bf16 terms and a product is accumulated in fp32 from six terms (decoder_common.hpp, "split-bf16 matrix
 // path": fp32-grade results at 16/6 of the f32 matrix rate).  Q is split once per workgroup and kept in
 // 96 VGPRs; K and V fragments are split as they are read from the fp32 LDS tiles; P is split straight
 // out of the score accumulator, whose layout makes registers 8t..8t+7 the operands of K16-step t.
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_bf16_kernel(
 
 // ============================================================================ split-fp16 variant
 // The same loop on v_mfma_f32_32x32x16_f16 with two range-managed fp16 terms per operand and three products per MAC
-// (split_f16.hpp; decoder.hip "split-fp16 matrix path"): half the matrix instructions of the split-bf16 variant and
+// (split_f16.hpp, "split-fp16 matrix path"): half the matrix instructions of the split-bf16 variant and
 // less than half of its operand-split VALU work.  NOT the default: the tile maxima have to be known before the first
 // product of a tile (read the whole tile, reduce across the wave, then split), which serialises a loop that is
 // latency-bound already — 229 us per call against 204 us for the split-bf16 variant at 64x80 tokens on MI355X.

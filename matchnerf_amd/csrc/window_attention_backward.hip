@@ -482,12 +482,8 @@ __device__ __forceinline__ WbsFrag<NT> wbs_split8(const float (&v)[8], float mul
   return f;
 }
 // acc += A . B from the term products that matter, smallest first
-#ifndef WBS_EXP
-#define WBS_EXP 0  // removal experiments (wrong results, meaningful times): tools/exp/wa_bwd_removal.sh
-#endif
 template <int NT>
 __device__ __forceinline__ f32x16 wbs_mfma(const WbsFrag<NT>& a, const WbsFrag<NT>& b, f32x16 acc) {
-  if (WBS_EXP == 1) return acc;
   if constexpr (NT == 3) {
 #define WB6_P(TA_, TB_) \
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wb6_bf16x8, a.t[TA_]), __builtin_bit_cast(wb6_bf16x8, b.t[TB_]), acc, 0, 0, 0)
@@ -572,7 +568,6 @@ __device__ __forceinline__ void wb6_fetch(Wb6TileRegs& r, const float* __restric
                                           int tid) {
   const int li = i0 + (tid >> 3), c = tid & 7;
   r.v[0] = r.v[1] = r.v[2] = r.v[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (WBS_EXP == 5) return;
   if (li < G.Lw) {
     int region;
     const int tok = win_token(G, wy, wx, li, region);
@@ -583,7 +578,6 @@ __device__ __forceinline__ void wb6_fetch(Wb6TileRegs& r, const float* __restric
 // registers -> R1 (split) and, if st, the fp32 staging tile (raw values: the gain is applied where they are split)
 template <int NT>
 __device__ __forceinline__ void wbs_store_r1(unsigned char* r1, float* st, const Wb6TileRegs& r, int tid, float mult) {
-  if (WBS_EXP == 3) return;
   const int row = tid >> 3, c = tid & 7;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -612,7 +606,6 @@ __device__ __forceinline__ void wb6_store_staging(float* st, const Wb6TileRegs& 
 // staging tile -> R2: thread t -> channel t & 127, K16-step t >> 7; both lane halves' fragments of that step
 template <int NT>
 __device__ __forceinline__ void wbs_build_r2(unsigned char* r2, const float* st, int tid, float mult) {
-  if (WBS_EXP == 2) return;
   const int ch = tid & 127, s = tid >> 7;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -804,7 +797,6 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dkv_split_kernel(WaBwdArgs A) {
         const float s = wb_score(s_[r], s_scale, A.do_shift && __float_as_int(info[r].w) != my_kreg, k_ok);
         const float pr = k_ok ? __builtin_amdgcn_exp2f(s - info[r].x) * info[r].y : 0.0f;
         x[r] = WHICH == 0 ? pr : pr * (dp[r] - info[r].z);
-        if (WBS_EXP == 4) x[r] = s_[r] + dp[r];
       }
       // dV^T[channel][key] += dO^T[channel][query] P[query][key]   |   dK^T[channel][key] += Q^T[channel][query] dS[query][key]
       wbs_chain_product<NT>(res, x_r2 + sb * L::R2_BYTES, x, n, half, x_gain);
@@ -975,7 +967,6 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dq_split_kernel(WaBwdArgs A) {
         const float s = wb_score(st[r], s_scale, A.do_shift && kinfo != my_qreg, kinfo >= 0);
         const float p = q_ok ? __builtin_amdgcn_exp2f(s - run_m) * inv_l : 0.0f;
         ds[r] = p * (dpt[r] - row_d);
-        if (WBS_EXP == 4) ds[r] = st[r] + dpt[r];
       }
       wbs_chain_product<NT>(dq, k_r2 + sb * L::R2_BYTES, ds, n, half, 1.0f);  // (ds already carries its gain)
     }

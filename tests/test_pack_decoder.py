@@ -1,5 +1,5 @@
 """Host logic of the decoder weight stream (no GPU): a numpy emulation of the kernel's MFMA
-dataflow (csrc/decoder.hip) consumes the packed stream exactly as the wavefront does — same
+dataflow (csrc/decoder_staged.hpp) consumes the packed stream exactly as the wavefront does — same
 segment schedule, same (lower | upper) half-wave operand rules — and must reproduce the
 oracle decoder.  This pins pack_wstream / decoder_schedule / pack_small without a GPU."""
 import numpy as np
@@ -40,7 +40,7 @@ def reg_order_operands(h, n_blocks):
 
 
 def enc_operands(x, L, legacy):
-    """x [3,N] -> operands of the 3L+2 positional-encoding steps (decoder.hip: enc_operand)."""
+    """x [3,N] -> operands of the 3L+2 positional-encoding steps (decoder_common.hpp: enc_operand)."""
     lo, hi = [], []
     fm = 1.0 if legacy else np.pi
     for t in range(3 * L):

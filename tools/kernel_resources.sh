@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/kernel_resources.sh matchnerf_amd/csrc/decoder.hip [extra hipcc flags]
+# usage: tools/kernel_resources.sh matchnerf_amd/csrc/decoder.hip [extra hipcc flags]   (decoder_fused.hip: the one-launch form)
 # One line per kernel: VGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, occupancy.
 src=$1; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-use-amdgpu-trackers=1 -c "$src" -o /dev/null "$@" \

@@ -4,7 +4,7 @@ those macros disappear, everything else passes through untouched.  Macro uses in
 them afterwards).
     python tools/unifdef_lite.py file.hip NAME=1 OTHER=0 UNDEFINED_ONE= > out
 Round 6 used it to take the measured-and-rejected experiment branches out of csrc/decoder.hip; the object code before and after
-is identical (the ISA of both parts was diffed)."""
+is identical (`tools/isa_scan.py --digest old.so new.so` compares every kernel's instruction stream)."""
 import re
 import sys
 
