@@ -36,6 +36,8 @@
  *   v9  mnerf_scene gained feat_op (appended: the offsets of the older fields are unchanged, sizeof grows by 8): the split-fp16
  *       OPERAND IMAGE of the feature maps that the matrix form of the cost volume reads (mnerf_cost_volume_operands,
  *       mnerf_cost_volume_operand_bytes).  NULL keeps the segment walk.
+ *   v10 no layout change of the older structs: the tail of a training iteration (matchnerf_amd/csrc/optim.hip) - mnerf_optim_row
+ *       and mnerf_optim_group - struct indices 8 and 9 -, mnerf_optim_row_blocks, mnerf_grad_sumsq, mnerf_adamw_step, mnerf_l2_loss.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define MNERF_ABI_VERSION 9
+#define MNERF_ABI_VERSION 10
 #define MNERF_MAX_VIEWS 16
 #define MNERF_FEAT_CH 128 /* channels of one pair-specific GMFlow feature map */
 /* floats per sample of a `cond` buffer: sum(cos_n_group) + 4 n_views + 1, rounded up to a multiple of 8.
@@ -576,6 +578,53 @@ int mnerf_qkv_backward(const float* w_q, const float* w_k, const float* w_v, con
 int mnerf_debug_gemm(const float* a, int64_t sa_i, int64_t sa_k, const float* b, int64_t sb_k, int64_t sb_j, float* c,
                      int64_t sc_i, const float* bias, int32_t I, int32_t J, int32_t K, int32_t mode, int32_t math,
                      void* stream);
+
+/* ABI v10 - the tail of a training iteration (coach.py:215-243 of the reference: the L2 loss, clip_grad_norm_ on the encoder and
+ * torch.optim.AdamW.step) as streaming kernels over ALL parameter tensors at once (matchnerf_amd/csrc/optim.hip).
+ *
+ * The tensors travel as a DEVICE table of rows, sorted by group; tensors without a gradient are not rows (torch skips them and does
+ * not advance their step).  A tensor is cut into chunks of MNERF_OPTIM_CHUNK elements, one workgroup per chunk: block_begin is the
+ * running sum of the rows' chunk counts (row 0: 0), n_blocks the total.  Pointers need 4-byte alignment only; a row whose four
+ * pointers are 16-byte aligned takes the vector path. */
+#define MNERF_OPTIM_CHUNK 4096
+#define MNERF_OPTIM_MAX_GROUPS 8
+typedef struct mnerf_optim_row {
+  float* param;
+  float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+  int32_t group;               /* index into the groups array */
+  int32_t block_begin;         /* first workgroup of this row */
+  double bias_correction1;     /* 1 - beta1^step of THIS tensor, formed on the host in double (lr / it is rounded once) */
+  float bias_correction2_sqrt; /* sqrt(1 - beta2^step) */
+  int32_t pad_;
+} mnerf_optim_row;
+/* Hyperparameters of one parameter group, BY VALUE (a host array; nothing is copied to the device but kernel arguments).
+ * n_blocks: workgroups of the group's rows.  max_norm <= 0: the group is not clipped. */
+typedef struct mnerf_optim_group {
+  double lr, beta1, beta2, eps, weight_decay, max_norm;
+  int32_t n_blocks;
+  int32_t pad_;
+} mnerf_optim_group;
+/* chunks of a tensor of numel elements (host only; -1 for numel <= 0) */
+int64_t mnerf_optim_row_blocks(int64_t numel);
+/* sumsq[g] = sum of grad^2 over the rows of group g, for every group.  Deterministic: every workgroup writes the sum of its chunk
+ * to workspace[block] (n_blocks floats), one workgroup per group adds them in a fixed order; no floating-point atomics, two calls on
+ * the same input give the same bits.  Two launches. */
+int mnerf_grad_sumsq(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const mnerf_optim_group* groups,
+                     int32_t n_groups, float* workspace, float* sumsq, void* stream);
+/* One launch: for every row, with c = min(1, max_norm / (sqrt(sumsq[group]) + 1e-6)) for a clipped group (read on the device) and
+ * 1 otherwise, the fp32 chain of torch.optim.AdamW:
+ *   grad *= c (written back when c < 1);  param *= 1 - lr weight_decay;  exp_avg += (1 - beta1) (grad - exp_avg);
+ *   exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) grad^2;
+ *   param -= (lr / bias_correction1) exp_avg / (sqrt(exp_avg_sq) / bias_correction2_sqrt + eps).
+ * sumsq: what mnerf_grad_sumsq wrote (may be NULL when no group clips). */
+int mnerf_adamw_step(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const mnerf_optim_group* groups,
+                     int32_t n_groups, const float* sumsq, void* stream);
+/* loss[0] = weight * mean((pred - target)^2) over n elements and, unless grad is NULL, grad[i] = 2 weight (pred[i] - target[i]) / n
+ * (coach.py:36-38, 257 and its autograd).  One launch of one workgroup, fixed summation order: bit-reproducible. */
+int mnerf_l2_loss(const float* pred, const float* target, int64_t n, float weight, float* loss, float* grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -256,12 +256,20 @@ class _ConvFn16(torch.autograd.Function):
 
 
 def conv2d(conv, x):
-    """``conv`` (an nn.Conv2d of a shape conv_backward.hip builds) applied to x [N,C,H,W] as one autograd node of HIP kernels; with
-    a ``_mnerf_train_pack`` on the module (gmflow: set per optimizer step) the split-fp16 kernels serve forward and data gradient"""
+    """``conv`` (an nn.Conv2d) applied to x [N,C,H,W] as one autograd node of HIP kernels; with a ``_mnerf_train_pack`` on the module
+    (gmflow: set per forward by the owning network) the split-fp16 kernels serve forward and data gradient.  A convolution the
+    kernels do not build (``conv2d_supported``), a non-fp32 operand, or the stem asked for the gradient of its input (the images:
+    mnerf_conv2d_backward_data has no c_in = 3) runs as torch's own op instead - per convolution, the rest of the network stays here.
+    A pack is only used for the weights it was made from: its (version, data_ptr) key is checked, a stale one (the module used
+    outside its owner's forward after an optimizer step) is ignored and the exact-f32 node takes the live weight."""
+    w = conv.weight
+    if (x.dtype != torch.float32 or w.dtype != torch.float32 or not conv2d_supported(conv)
+            or (conv.in_channels == 3 and x.requires_grad)):
+        return conv(x)
     pack = getattr(conv, "_mnerf_train_pack", None)
-    if pack is not None:
-        return _ConvFn16.apply(x, conv.weight, conv.bias, conv.stride[0], pack)
-    return _ConvFn.apply(x, conv.weight, conv.bias, conv.stride[0])
+    if pack is not None and (len(pack) < 5 or pack[4] == (int(w._version), int(w.data_ptr()))):
+        return _ConvFn16.apply(x, w, conv.bias, conv.stride[0], pack)
+    return _ConvFn.apply(x, w, conv.bias, conv.stride[0])
 
 
 def conv2d_supported(conv):
@@ -391,3 +399,33 @@ def render_ray_chunk(launch, feats):
     """Differentiable render of one chunk of rays of one batch element -> (rgb [R,3], depth [R,1], opacity [R,1])."""
     params = list(launch.dec_module.parameters())
     return _RayChunkFn.apply(launch, len(feats), *feats, *params)
+
+
+# ----------------------------------------------------------------------------- the loss
+
+
+class _L2LossFn(torch.autograd.Function):
+    """weight * mean((pred - target) ** 2) (coach.py:36-38, 257) and its gradient in ONE launch (csrc/optim.hip: mnerf_l2_loss);
+    fixed summation order, so two calls give the same bits.  The backward scales the stored gradient by the incoming one: one
+    more element-wise launch (the incoming gradient lives on the device; testing it for 1 would be a host round trip)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight):
+        loss, grad = hip.l2_loss(pred.contiguous(), target.contiguous(), weight, want_grad=ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.saved_tensors[0] * g if ctx.saved_tensors else None), None, None
+
+
+def l2_loss(pred, target, weight=1.0):
+    """``weight * ((pred - target) ** 2).mean()`` of two float32 CUDA tensors of one shape as one HIP launch; the gradient goes to
+    ``pred`` only (the target is data).  CPU tensors raise ``hip.MnerfError``."""
+    if target.requires_grad:
+        raise hip.MnerfError("l2_loss: the target is treated as data; detach it")
+    if pred.shape != target.shape:
+        target = target.expand_as(pred)
+    return _L2LossFn.apply(pred, target, float(weight))

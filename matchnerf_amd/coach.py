@@ -1,10 +1,14 @@
-"""Thin orchestration counterpart of the reference's Coach for INFERENCE (coach.py:27-146,
-368-529): build the network from the registry, restore a checkpoint per child, iterate test
-batches, call the hot path, report PSNR.  The training loop, TensorBoard, SSIM/LPIPS and the
-on-disk datasets are callers / data formats outside the hot path — a dataset is
-anything that yields batches with the reference's contract (images, extrinsics, intrinsics,
-near_fars[, depth, scene, view_ids]); ``synthetic`` is built in so the tool runs offline."""
+"""Orchestration counterpart of the reference's Coach (coach.py:27-529): build the network from the registry, restore a
+checkpoint per child, iterate batches, call the hot path, report PSNR - and, since ABI 10, the TRAINING loop (coach.py:87-300):
+parameter groups / scheduler of the reference's recipe, ``train_iteration`` = zero_grad, HIP forward, L2 loss, HIP backward,
+clip + AdamW (the loss is one launch and clip + step are three: optim.FusedAdamW; MNERF_FUSED_OPTIM=0: torch's ops), checkpoints in the reference's format, scalars to
+``<output_path>/scalars.jsonl`` (TensorBoard only where it can be imported).  A dataset is anything that yields batches with the
+reference's contract (images, extrinsics, intrinsics, near_fars[, depth, scene, view_ids]); ``synthetic`` is built in so the tools
+run offline.  One GPU: ``gpu_ids`` longer than one raises in ``setup_optimizer``."""
+import json
+import math
 import os
+import time
 
 import numpy as np
 import torch
@@ -14,11 +18,18 @@ from .edict import EasyDict as edict
 from .models import models_dict
 
 
+def fused_optim_enabled():
+    """``MNERF_FUSED_OPTIM`` (default 1): AdamW steps and the L2 loss of ``Coach`` run on csrc/optim.hip; 0 takes torch's
+    expression, ``clip_grad_norm_`` and foreach AdamW (measured: DESIGN.md section 4, tools/train_tail_time.py)"""
+    return os.environ.get("MNERF_FUSED_OPTIM", "1").lower() not in ("0", "off", "false", "no")
+
+
 class SyntheticScenes:
     """Seeded stand-in for a dataset (no DTU/LLFF/Blender data offline)."""
 
-    def __init__(self, name, cfg, n_src_views):
+    def __init__(self, name, cfg, n_src_views, shuffle=False):
         self.name = name
+        self.shuffle = shuffle  # training: a fresh order of the scenes every epoch (torch's generator)
         w, h = cfg.get("img_wh", [64, 64])
         self.kw = dict(height=h, width=w, n_src_views=n_src_views, wide=(name == "blender"),
                        near_far=(2.0, 6.0) if name == "blender" else (2.125, 4.525))
@@ -32,7 +43,7 @@ class SyntheticScenes:
         return self.n
 
     def __iter__(self):
-        for i in range(self.n):
+        for i in (torch.randperm(self.n).tolist() if self.shuffle else range(self.n)):
             sc = synthetic.make_scene(seed=100 + i, **self.kw)
             batch = {k: torch.from_numpy(v) for k, v in sc.items()}
             batch["scene"] = [f"synthetic{i}"]
@@ -45,44 +56,306 @@ class Coach:
         self.opts = opts
         self.n_src_views = opts.n_src_views
         self.device = opts.device
+        self.epoch_start = 0
+        self.iter_start = 0
 
     def build_networks(self):
         self.model = models_dict[self.opts.model](self.opts).to(self.opts.device)  # coach.py:77
 
     def restore_checkpoint(self):
+        """coach.py:127-146.  ``opts.resume``: model, optimizer, scheduler, epoch and iteration from <output_path>/models/latest.pth;
+        ``opts.load``: the model's children from that file.  Without either, a TRAINING run (``setup_optimizer`` has been called)
+        keeps the module's own initialisation plus the GMFlow weights of ``encoder.pretrain_weight`` if that file exists
+        (coach.py:78-81); an inference run gets seeded random weights, so that the tools run offline."""
         path = self.opts.load
-        if path and os.path.isfile(path):
+        training = hasattr(self, "optim")
+        latest = os.path.join(self.opts.output_path, "models", "latest.pth")
+        if getattr(self.opts, "resume", False) and training and os.path.isfile(latest):
+            state = {k: getattr(self, k) for k in ("optim", "sched") if getattr(self, k, None) is not None}
+            ep, it = checkpoint.restore_checkpoint(self.model, latest, self.opts.device, resume=True, optims_scheds=state)
+            self.epoch_start, self.iter_start = int(ep or 0), int(it or 0)
+            self.apply_clip_enc()  # the saved param_groups replaced the live ones
+            print(f"[coach] resuming from epoch {self.epoch_start} (iteration {self.iter_start})")
+        elif path and os.path.isfile(path):
             checkpoint.restore_checkpoint(self.model, path, self.opts.device)
+        elif training:
+            if getattr(self.opts, "resume", False):
+                print(f"[coach] no checkpoint at {latest!r}: training starts from scratch")
+            pre = self.opts.encoder.pretrain_weight
+            if pre and os.path.isfile(pre):
+                checkpoint.load_gmflow_checkpoint(self.model.feat_enc, pre, self.opts.device,
+                                                  gmflow_n_blocks=self.opts.encoder.num_transformer_layers)
+                print(f"[coach] encoder initialised from {pre}")
         else:
             print(f"[coach] checkpoint {path!r} not found: using seeded random weights (offline run)")
             spec = synthetic.state_dict_spec(n_src_views=self.n_src_views)
             self.model.load_state_dict(synthetic.to_torch(synthetic.seeded_state_dict(spec, 1), self.opts.device))
 
+    def _loader(self, name, cfg, split):
+        """One entry of the options' data sections: the on-disk producer where ``root_dir`` exists, synthetic scenes otherwise."""
+        train = split == "train"
+        root, kind = cfg.get("root_dir"), cfg.get("dataset_name", name)
+        if root and os.path.isdir(root) and kind in datasets.datas_dict:  # coach.py:52-69: the on-disk producer
+            extra = {k: cfg[k] for k in ("meta_dir", "pairs_file") if cfg.get(k)}  # where the scan / pair lists live
+            ds = datasets.datas_dict[kind](root, split, n_views=self.n_src_views, img_wh=cfg.get("img_wh"),
+                                           max_len=cfg.get("max_len", -1), scene_list=cfg.get("scene_list"),
+                                           test_views_method=cfg.get("test_views_method", "nearest"),
+                                           nf_mode=cfg.get("nf_mode", "avg"), eval_mode=cfg.get("eval_mode", "mvsnerf"),
+                                           n_add_train_views=cfg.get("n_add_train_views", 2), **extra)
+            workers = cfg.get("num_workers", 0)
+            if split != "test":
+                workers = min(int(workers or 0), 16)
+            loader = torch.utils.data.DataLoader(ds, shuffle=train, num_workers=workers, batch_size=self.opts.batch_size,
+                                                 pin_memory=True)
+            loader.get_name = ds.get_name
+            return loader
+        return SyntheticScenes(name, cfg, self.n_src_views, shuffle=train)
+
     def load_dataset(self, splits=("test",), loaders=None):
-        """``loaders``: optional list of iterables of batches (objects with get_name()); otherwise
+        """``loaders``: optional list of iterables of batches (objects with get_name()) for the test split; otherwise
         every ``data_test`` entry whose ``root_dir`` exists is read from disk (datasets.py) and the others are served by the
-        synthetic generator at that entry's img_wh."""
-        if loaders is not None:
+        synthetic generator at that entry's img_wh.  ``"train"`` / ``"val"`` build ``train_loader`` / ``val_loader`` from
+        ``opts.data_train`` / ``opts.data_val`` the same way (training shuffles; at most 16 workers)."""
+        if loaders is not None:  # as before: given loaders ARE the test loaders, whatever `splits` says
             self.test_loaders = list(loaders)
-            return
-        self.test_loaders = []
-        for name, cfg in self.opts.data_test.items():
-            if cfg is None:
-                continue
-            root, kind = cfg.get("root_dir"), cfg.get("dataset_name", name)
-            if root and os.path.isdir(root) and kind in datasets.datas_dict:  # coach.py:52-69: the on-disk producer
-                extra = {k: cfg[k] for k in ("meta_dir", "pairs_file") if cfg.get(k)}  # where the scan / pair lists live
-                ds = datasets.datas_dict[kind](root, "test", n_views=self.n_src_views, img_wh=cfg.get("img_wh"),
-                                               max_len=cfg.get("max_len", -1), scene_list=cfg.get("scene_list"),
-                                               test_views_method=cfg.get("test_views_method", "nearest"),
-                                               nf_mode=cfg.get("nf_mode", "avg"), eval_mode=cfg.get("eval_mode", "mvsnerf"),
-                                               n_add_train_views=cfg.get("n_add_train_views", 2), **extra)
-                loader = torch.utils.data.DataLoader(ds, shuffle=False, num_workers=cfg.get("num_workers", 0),
-                                                     batch_size=self.opts.batch_size, pin_memory=True)
-                loader.get_name = ds.get_name
-                self.test_loaders.append(loader)
+        for split in splits:
+            if split == "test":
+                if loaders is not None:
+                    continue
+                self.test_loaders = [self._loader(name, cfg, "test") for name, cfg in self.opts.data_test.items()
+                                     if cfg is not None]
+            elif split in ("train", "val"):
+                cfg = getattr(self.opts, f"data_{split}", None)
+                if cfg:
+                    setattr(self, f"{split}_loader", self._loader(cfg.get("dataset_name", "synthetic"), cfg, split))
             else:
-                self.test_loaders.append(SyntheticScenes(name, cfg, self.n_src_views))
+                raise ValueError(f"load_dataset: unknown split {split!r}")
+
+    # ------------------------------------------------------------------ training (coach.py:87-300)
+
+    def setup_optimizer(self):
+        """coach.py:87-125: one parameter group per child at ``optim.lr_enc`` / ``optim.lr_dec`` (a rate <= 0 freezes that child:
+        per-scene fine-tuning), ``optim.algo`` passed through, ``optim.sched`` with OneCycleLR's extra arguments taken from the run.
+        AdamW runs on the fused HIP step (optim.FusedAdamW, ``clip_enc`` as the encoder group's ``max_norm``); with
+        ``MNERF_FUSED_OPTIM=0``, and for every other algorithm, the optimizer is ``torch.optim``'s, with ``clip_grad_norm_`` in ``train_iteration``."""
+        o = self.opts.optim
+        if len(self.opts.gpu_ids) > 1:
+            raise NotImplementedError(f"training runs on one GPU; gpu_ids = {list(self.opts.gpu_ids)}")
+        groups, rates = [], []
+        self._enc_group = None
+        for child, rate in ((self.model.feat_enc, o.lr_enc), (self.model.nerf_dec, o.lr_dec)):
+            if rate > 0:
+                if child is self.model.feat_enc:
+                    self._enc_group = len(groups)
+                groups.append(dict(params=list(child.parameters()), lr=rate))
+                rates.append(rate)
+            else:
+                child.requires_grad_(False)
+        kind = o.algo.type
+        kwargs = {k: v for k, v in o.algo.items() if k != "type"}
+        self.fused_optim = kind == "AdamW" and fused_optim_enabled()
+        if self.fused_optim:
+            from .optim import FusedAdamW
+            self.optim = FusedAdamW(groups, **kwargs)
+            self.apply_clip_enc()
+        else:
+            self.optim = getattr(torch.optim, kind)(groups, **kwargs)
+        print(f"[coach] {'fused HIP ' if self.fused_optim else ''}{kind} ({', '.join(f'{k}={v}' for k, v in kwargs.items())})")
+        self.sched_type, self.sched = None, None
+        if o.get("sched"):
+            self.sched_type = o.sched.type
+            kwargs = {k: v for k, v in o.sched.items() if k != "type"}
+            if self.sched_type == "OneCycleLR":
+                assert hasattr(self, "train_loader"), "load the training data first: OneCycleLR needs the number of steps"
+                kwargs.update(epochs=self.opts.max_epoch, steps_per_epoch=len(self.train_loader) // self.opts.batch_size,
+                              max_lr=rates)
+            self.sched = getattr(torch.optim.lr_scheduler, self.sched_type)(self.optim, **kwargs)
+
+    def apply_clip_enc(self):
+        """Fused path: ``optim.clip_enc`` travels as the encoder group's ``max_norm``.  ``load_state_dict`` replaces the groups by
+        the saved ones, and a state written by torch's AdamW or by the reference has no such key: set it again after a restore."""
+        if getattr(self, "fused_optim", False) and self._enc_group is not None:
+            self.optim.param_groups[self._enc_group]["max_norm"] = self.opts.optim.get("clip_enc")
+
+    def setup_visualizer(self):
+        """Scalars always go to <output_path>/scalars.jsonl; a TensorBoard writer is added when ``opts.tb`` is set AND the package
+        can be imported."""
+        self.tb = None
+        if getattr(self.opts, "tb", False):
+            try:
+                from torch.utils import tensorboard
+                self.tb = tensorboard.SummaryWriter(log_dir=self.opts.output_path, flush_secs=10)
+            except ImportError:
+                print("[coach] tensorboard is not installed: scalars go to scalars.jsonl only")
+
+    def log_scalars(self, scalars, step, split):
+        """{tag: value} -> one line per value in scalars.jsonl (+ TensorBoard)"""
+        with open(os.path.join(self.opts.output_path, "scalars.jsonl"), "a") as f:
+            for tag, value in scalars.items():
+                f.write(json.dumps({"step": int(step), "split": split, "tag": tag, "value": float(value)}) + "\n")
+                if getattr(self, "tb", None) is not None:
+                    self.tb.add_scalar(f"{split}/{tag}", float(value), int(step))
+
+    def _every(self, fraction):
+        """freq.*_it: a fraction of an epoch -> iterations (coach.py:160-162); <= 0 stays off"""
+        return math.ceil(fraction * len(self.train_loader)) if fraction and fraction > 0 else -1
+
+    def train_model(self):
+        assert hasattr(self, "optim") and hasattr(self, "train_loader"), "call load_dataset(['train', ...]) and setup_optimizer() first"
+        if not hasattr(self, "tb"):
+            self.setup_visualizer()
+        f = self.opts.freq
+        self.it, self.ep = self.iter_start, self.epoch_start
+        self.val_it, self.test_it, self.ckpt_it = self._every(f.val_it), self._every(f.test_it), self._every(f.ckpt_it)
+        self.timer = edict(start=time.time(), it_mean=None)
+        if getattr(self.opts, "sanity_check", False) and self.it == 0 and self.val_it > 0:
+            self.validate_model(first_only=True)
+        print(f"[coach] training: epochs {self.epoch_start}..{self.opts.max_epoch - 1}, {len(self.train_loader)} iterations each")
+        for self.ep in range(self.epoch_start, self.opts.max_epoch):
+            self.train_epoch()
+        if getattr(self, "tb", None) is not None:
+            self.tb.flush()
+            self.tb.close()
+        print(f"[coach] training done: {self.it} iterations")
+
+    def train_epoch(self):
+        f = self.opts.freq
+        self.model.train()
+        loss, n = None, len(self.train_loader)
+        for bi, batch in enumerate(self.train_loader):
+            if getattr(self.opts, "resume", False) and self.ep * n + bi < self.iter_start:
+                continue  # iterations the resumed run has already done
+            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+            loss = self.train_iteration(var)
+            if self.sched_type == "OneCycleLR":
+                self.sched.step()
+        if loss is not None and f.log_ep > 0 and (self.ep + 1) % f.log_ep == 0:
+            lr = self.get_cur_lrates()
+            timer = getattr(self, "timer", None)
+            print(f"[coach] epoch {self.ep + 1}: loss {float(loss.all.detach()):.5f}  lr enc {lr['enc']:.3e} dec {lr['dec']:.3e}"
+                  + (f"  {timer.it_mean * 1e3:.1f} ms / iteration" if timer is not None else ""))
+        if self.sched_type is not None and self.sched_type != "OneCycleLR":
+            self.sched.step()
+        if f.val_ep > 0 and (self.ep + 1) % f.val_ep == 0:
+            self.validate_model()
+        if hasattr(self, "test_loaders") and self.ep >= f.test_ep_start and f.test_ep > 0 and (self.ep + 1) % f.test_ep == 0:
+            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
+            self.model.train()
+        if f.ckpt_ep > 0 and (self.ep + 1) % f.ckpt_ep == 0:
+            self.save_checkpoint(ep=self.ep + 1, it=self.it, backup_ckpt=True)
+
+    def train_iteration(self, var):
+        """coach.py:215-243: zero_grad, mode='train' forward, loss, backward, clip, step - and the per-iteration bookkeeping."""
+        t0 = time.time()
+        clip = self.opts.optim.get("clip_enc")
+        if self.fused_optim and clip is not None and self._enc_group is not None:  # the fused step clips inside (max_norm)
+            if self.optim.param_groups[self._enc_group].get("max_norm") != clip:
+                raise RuntimeError("the encoder group of the fused optimizer has lost its max_norm (optim.clip_enc): "
+                                   "a load_state_dict() replaced the parameter groups; call Coach.apply_clip_enc()")
+        self.optim.zero_grad(set_to_none=True)
+        pred = self.model(var, mode="train")
+        loss = self.compute_loss(pred, var, mode="train")
+        loss.all = None
+        for k, w in self.opts.loss_weight.items():
+            if w is not None and k in loss:
+                term = loss[k] if w == 1 else w * loss[k]
+                loss.all = term if loss.all is None else loss.all + term
+        loss.all.backward()
+        if clip is not None and not self.fused_optim:
+            torch.nn.utils.clip_grad_norm_(self.model.feat_enc.parameters(), clip)
+        self.optim.step()
+
+        self.it += 1
+        if getattr(self, "timer", None) is not None:
+            dt = time.time() - t0
+            self.timer.it_mean = dt if self.timer.it_mean is None else 0.99 * self.timer.it_mean + 0.01 * dt
+        f = self.opts.freq
+        if f.scalar > 0 and self.it % f.scalar == 0:
+            scalars = {f"loss_{k}": float(v.detach()) for k, v in loss.items() if k != "all"}
+            scalars.update({f"lrate_{k}": v for k, v in self.get_cur_lrates().items()})
+            self.log_scalars(scalars, self.it, "train")
+        if getattr(self, "ckpt_it", -1) > 0 and self.it % self.ckpt_it == 0:
+            self.save_checkpoint(ep=self.ep, it=self.it, backup_ckpt=False)
+        if getattr(self, "val_it", -1) > 0 and self.it % self.val_it == 0:
+            self.validate_model()
+        if getattr(self, "test_it", -1) > 0 and self.it % self.test_it == 0 and hasattr(self, "test_loaders"):
+            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
+            self.model.train()
+        return loss
+
+    def compute_loss(self, pred, src, mode=None):
+        """coach.py:245-259: the L2 loss of the rendered colours against the target view's pixels (at ``pred.ray_idx`` when the
+        mode draws random rays) or against ``train_color``.  On the fused path it is one HIP launch (autograd.l2_loss)."""
+        loss = edict()
+        if "train_color" in src:
+            gt = src["train_color"]
+        else:
+            b, n_views, c = src.images.shape[:3]
+            assert n_views == self.n_src_views + 1, "the last view of a batch is the target view"
+            gt = src.images[:, -1].reshape(b, c, -1).permute(0, 2, 1)  # [B, H*W, 3]
+            if getattr(self.opts.nerf, f"rand_rays_{mode}", None) and mode == "train":
+                gt = gt[:, pred.ray_idx]
+        if self.opts.loss_weight.render is not None:
+            if getattr(self, "fused_optim", False):
+                from .autograd import l2_loss
+                loss.render = l2_loss(pred.rgb, gt.contiguous())
+            else:
+                loss.render = ((pred.rgb.contiguous() - gt) ** 2).mean()
+        return loss
+
+    def get_cur_lrates(self):
+        o = self.opts.optim
+        enc, dec = o.lr_enc, o.lr_dec
+        if getattr(self, "sched", None) is not None:
+            last = self.sched.get_last_lr()
+            if enc > 0:
+                enc = last[0]
+            if dec > 0:
+                dec = last[-1]
+        return dict(enc=enc, dec=dec)
+
+    def save_checkpoint(self, ep=0, it=0, backup_ckpt=True):
+        """coach.py:290-300: {model, optim, sched, epoch, iter} -> <output_path>/models/latest.pth (+ ep{E}_it{I}.pth without the
+        optimizer and scheduler state when ``backup_ckpt``)."""
+        ckpt = dict(model=self.model.state_dict(), optim=self.optim.state_dict())
+        if getattr(self, "sched", None) is not None:
+            ckpt["sched"] = self.sched.state_dict()
+        return checkpoint.save_checkpoint(self.opts.output_path, ckpt, ep=ep, it=it, backup_ckpt=backup_ckpt)
+
+    @torch.no_grad()
+    def validate_model(self, first_only=False):
+        """coach.py:316-366: every batch of ``val_loader`` rendered in mode='val'; mean PSNR / SSIM to the scalars, prediction | ground
+        truth strips to <output_path>/validation/."""
+        assert hasattr(self, "val_loader"), "load_dataset(['val']) first"
+        from PIL import Image
+        self.model.eval()
+        out_dir = os.path.join(self.opts.output_path, "validation")
+        os.makedirs(out_dir, exist_ok=True)
+        name = self.val_loader.get_name()
+        it = getattr(self, "it", 0)
+        psnrs, ssims = [], []
+        for bi, batch in enumerate(self.val_loader):
+            if first_only and bi > 0:
+                break
+            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+            gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
+            var = self.model(var, mode="val")
+            b, _, _, h, w = var.images.shape
+            pred = var.rgb.reshape(b, h, w, 3).cpu().numpy()
+            gt = var.images[:, -1].permute(0, 2, 3, 1).cpu().numpy()
+            for i in range(b):
+                mask = (gt_depth[i].cpu().numpy() == 0) if (gt_depth is not None and "dtu" in name) else None
+                tools = metrics.EvalTools(lpips_fn=None)
+                tools.set_inputs(pred[i], gt[i], mask)
+                psnrs.append(metrics.psnr(pred[i], gt[i], mask))
+                ssims.append(tools.get_metrics(["SSIM"])["SSIM"])
+                scene = batch["scene"][i] if "scene" in batch else f"{name}{bi}"
+                vis = (np.concatenate([pred[i], gt[i]], 1).clip(0, 1) * 255).astype("uint8")
+                Image.fromarray(vis).save(os.path.join(out_dir, f"{scene}_{bi:03d}_{i}_it{it}.jpg"))
+        self.log_scalars({"PSNR": np.mean(psnrs), "SSIM": np.mean(ssims)}, it, "val")
+        print(f"[coach] validation at iteration {it}: PSNR {np.mean(psnrs):.2f} over {len(psnrs)} images")
+        self.model.train()
+        return dict(PSNR=psnrs, SSIM=ssims)
 
     @torch.no_grad()
     def test_model(self, save_images=False, **kwargs):

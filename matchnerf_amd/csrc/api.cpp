@@ -32,6 +32,8 @@ extern "C" int64_t mnerf_struct_size(int32_t which) {
     case 5: return (int64_t)sizeof(mnerf_conv);
     case 6: return (int64_t)sizeof(mnerf_decoder_train);
     case 7: return (int64_t)sizeof(mnerf_encoder_layer_train);
+    case 8: return (int64_t)sizeof(mnerf_optim_row);
+    case 9: return (int64_t)sizeof(mnerf_optim_group);
     default: return -1;
   }
 }

@@ -45,7 +45,8 @@ def _train_hip(x):
     convolution of inference, csrc/conv.hip) - instead of torch's op chain (MIOpen convolutions, ATen norms).
     ``MNERF_TRAIN_CNN=torch`` restores that chain, ``=f32`` keeps every convolution on the exact-f32 kernels."""
     import os
-    return x.is_cuda and torch.is_grad_enabled() and os.environ.get("MNERF_TRAIN_CNN", "hip") != "torch"
+    return (x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+            and os.environ.get("MNERF_TRAIN_CNN", "hip") != "torch")
 
 
 def _train_packs(owner, convs, device):
@@ -68,7 +69,14 @@ def _train_packs(owner, convs, device):
     # fresh (zeroed) absmax regions for this forward / backward pair: one fill for all convolutions
     regs = hip.absmax_regions(2 * len(convs), device).reshape(len(convs), 2, -1)
     for i, (c, st) in enumerate(zip(convs, owner._train_streams)):
-        c._mnerf_train_pack = (st[0], st[1], st[2], regs[i])
+        c._mnerf_train_pack = (st[0], st[1], st[2], regs[i], (int(c.weight._version), int(c.weight.data_ptr())))
+
+
+def _drop_train_packs(convs):
+    """End of the owner's forward: the packs belong to THIS forward (the autograd nodes keep what their backward needs); a
+    convolution used on its own later must not find streams from before an optimizer step."""
+    for c in convs:
+        c._mnerf_train_pack = None
 
 
 def _conv_out(conv, x):
@@ -201,9 +209,11 @@ class CNNEncoder(nn.Module):
             return _hip_conv(self.conv2, x, amax)
         if _train_hip(x):
             from . import autograd as AG
-            _train_packs(self, [m for m in self.modules() if isinstance(m, nn.Conv2d)], x.device)
+            convs = [m for m in self.modules() if isinstance(m, nn.Conv2d)]
+            _train_packs(self, convs, x.device)
             x = AG.instance_norm(AG.conv2d(self.conv1, x), relu=True)
             x = AG.conv2d(self.conv2, self.layer3(self.layer2(self.layer1(x))))
+            _drop_train_packs(convs)
         else:
             x = F.relu(F.instance_norm(self.conv1(x)))
             x = self.conv2(self.layer3(self.layer2(self.layer1(x))))
@@ -507,6 +517,8 @@ class UpSampler(nn.Module):
                 right = AG.upsample_bilinear2x_add(right, conv(self.conv_l2rs[i + 1], left))
             else:
                 right = F.interpolate(right, scale_factor=2, mode="bilinear", align_corners=False) + conv(self.conv_l2rs[i + 1], left)
+        if _train_hip(x):
+            _drop_train_packs(list(self.conv_ls) + list(self.conv_l2rs))
         return right
 
 

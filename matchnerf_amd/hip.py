@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-MNERF_ABI_VERSION = 9
+MNERF_ABI_VERSION = 10
 MNERF_POSE_FLOATS = 24  # floats of one row of mnerf_rays.pose_table
 MNERF_OK, MNERF_E_NULL, MNERF_E_RANGE, MNERF_E_UNSUPPORTED, MNERF_E_ALIGN = 0, -1, -2, -3, -4  # include/mnerf.h
 MNERF_MAX_VIEWS = 16
@@ -31,7 +31,8 @@ EXPORTS = ("mnerf_abi_version", "mnerf_last_error", "mnerf_struct_size", "mnerf_
            "mnerf_render_chunk", "mnerf_render_chunk_fused", "mnerf_render_chunk_is_fused", "mnerf_render_takes_pose_table", "mnerf_window_attention",
            "mnerf_window_attention_presplit", "mnerf_window_attention_workspace_bytes", "mnerf_window_attention_backward", "mnerf_window_attention_backward_workspace_bytes", "mnerf_qkv_projection", "mnerf_qkv_wstream_floats", "mnerf_qkv_window_images", "mnerf_window_attention_images", "mnerf_instance_norm", "mnerf_instance_norm_backward", "mnerf_upsample_bilinear2x", "mnerf_upsample_bilinear2x_backward", "mnerf_conv2d", "mnerf_conv_wstream_floats", "mnerf_conv_stem", "mnerf_conv_stem_wstream_floats", "mnerf_absmax", "mnerf_conv2d_backward_data", "mnerf_conv2d_backward_weight", "mnerf_conv2d_backward_weight_workspace_bytes", "mnerf_conv2d_backward_weight_f16x3", "mnerf_conv2d_forward_f32", "mnerf_conv_stem_backward_weight", "mnerf_conv_stem_backward_weight_workspace_bytes", "mnerf_encoder_block", "mnerf_encoder_block_wstream_floats",
            "mnerf_encoder_layer_backward", "mnerf_encoder_layer_backward_workspace_bytes", "mnerf_qkv_backward", "mnerf_debug_gemm",
-           "mnerf_window_attention_presplit_stats", "mnerf_window_attention_backward_stats", "mnerf_encoder_block_save", "mnerf_encoder_layer_backward_saved")
+           "mnerf_window_attention_presplit_stats", "mnerf_window_attention_backward_stats", "mnerf_encoder_block_save", "mnerf_encoder_layer_backward_saved",
+           "mnerf_optim_row_blocks", "mnerf_grad_sumsq", "mnerf_adamw_step", "mnerf_l2_loss")
 
 
 class MnerfError(RuntimeError):
@@ -104,6 +105,22 @@ class ConvLayer(C.Structure):
     _fields_ = [("wstream", C.c_void_p), ("wstream_floats", C.c_int64), ("bias", C.c_void_p), ("c_in", C.c_int32),
                 ("c_out", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("ew", C.c_int32),
                 ("leaky_slope", C.c_float)]
+
+
+OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8  # MNERF_OPTIM_CHUNK, MNERF_OPTIM_MAX_GROUPS
+
+
+class OptimRow(C.Structure):
+    """struct mnerf_optim_row: one parameter tensor of the device table of mnerf_grad_sumsq / mnerf_adamw_step"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("group", C.c_int32), ("block_begin", C.c_int32), ("bias_correction1", C.c_double),
+                ("bias_correction2_sqrt", C.c_float), ("pad_", C.c_int32)]
+
+
+class OptimGroup(C.Structure):
+    """struct mnerf_optim_group: hyperparameters of one parameter group, by value"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("max_norm", C.c_double), ("n_blocks", C.c_int32), ("pad_", C.c_int32)]
 
 
 def lib_path():
@@ -230,10 +247,19 @@ def load():
     lib.mnerf_encoder_layer_backward.argtypes = [C.POINTER(EncoderLayerTrain), fp, fp, fp, fp, fp, i32, vp, vp]
     lib.mnerf_qkv_backward.restype = C.c_int
     lib.mnerf_qkv_backward.argtypes = [fp] * 13 + [i32, vp]
+    lib.mnerf_optim_row_blocks.restype = i64
+    lib.mnerf_optim_row_blocks.argtypes = [i64]
+    lib.mnerf_grad_sumsq.restype = C.c_int
+    lib.mnerf_grad_sumsq.argtypes = [vp, i32, i32, C.POINTER(OptimGroup), i32, fp, fp, vp]
+    lib.mnerf_adamw_step.restype = C.c_int
+    lib.mnerf_adamw_step.argtypes = [vp, i32, i32, C.POINTER(OptimGroup), i32, fp, vp]
+    lib.mnerf_l2_loss.restype = C.c_int
+    lib.mnerf_l2_loss.argtypes = [fp, fp, i64, C.c_float, fp, fp, vp]
     ver = lib.mnerf_abi_version()
     if ver != MNERF_ABI_VERSION:
         raise MnerfError(f"libmnerf_hip.so ABI {ver} != binding ABI {MNERF_ABI_VERSION}")
-    for which, st in enumerate((View, Rays, Scene, Decoder, EncoderLayer, ConvLayer, DecoderTrain, EncoderLayerTrain)):
+    for which, st in enumerate((View, Rays, Scene, Decoder, EncoderLayer, ConvLayer, DecoderTrain, EncoderLayerTrain, OptimRow,
+                                OptimGroup)):
         if lib.mnerf_struct_size(which) != C.sizeof(st):
             raise MnerfError(f"struct {st.__name__}: library says {lib.mnerf_struct_size(which)} bytes, "
                              f"ctypes mirror has {C.sizeof(st)}")
@@ -1134,3 +1160,56 @@ def encoder_block(attn, source, wstream, ln, ffn, ews, out=None, stream=None, sa
             return out, m1, z1, m2
         check(lib.mnerf_encoder_block(C.byref(blk), _ptr(attn), _ptr(source), _ptr(out), n, st), "mnerf_encoder_block")
     return out
+
+
+# ----------------------------------------------------------------------- the tail of a training iteration (csrc/optim.hip)
+
+
+def optim_groups(groups):
+    """[(lr, beta1, beta2, eps, weight_decay, max_norm, n_blocks), ...] -> the by-value array of mnerf_optim_group"""
+    if not 1 <= len(groups) <= OPTIM_MAX_GROUPS:
+        raise MnerfError(f"optim_groups: {len(groups)} parameter groups, the kernels take 1..{OPTIM_MAX_GROUPS}")
+    arr = (OptimGroup * len(groups))()
+    for a, (lr, b1, b2, eps, wd, max_norm, n_blocks) in zip(arr, groups):
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
+        a.max_norm, a.n_blocks = float(max_norm or 0.0), int(n_blocks)
+    return arr
+
+
+def grad_sumsq(rows, n_rows, n_blocks, groups, workspace, sumsq, stream=None):
+    """Sum of squared gradients per parameter group, deterministic (mnerf_grad_sumsq).  ``rows``: uint8 CUDA tensor holding n_rows
+    OptimRow records; ``groups``: from ``optim_groups``; ``workspace`` >= n_blocks floats; ``sumsq`` >= len(groups) floats."""
+    lib = load()
+    _f32c(workspace, "workspace"), _f32c(sumsq, "sumsq")
+    if rows.numel() < n_rows * C.sizeof(OptimRow) or workspace.numel() < n_blocks or sumsq.numel() < len(groups):
+        raise MnerfError("grad_sumsq: rows / workspace / sumsq too small for the table")
+    with _on(rows.device, stream) as st:
+        check(lib.mnerf_grad_sumsq(rows.data_ptr(), int(n_rows), int(n_blocks), groups, len(groups), _ptr(workspace), _ptr(sumsq), st),
+              "mnerf_grad_sumsq")
+    return sumsq
+
+
+def adamw_step(rows, n_rows, n_blocks, groups, sumsq=None, stream=None):
+    """Clip + AdamW over every row of the table in one launch (mnerf_adamw_step); ``sumsq`` from ``grad_sumsq`` when a group clips."""
+    lib = load()
+    if rows.numel() < n_rows * C.sizeof(OptimRow) or (sumsq is not None and sumsq.numel() < len(groups)):
+        raise MnerfError("adamw_step: rows / sumsq too small for the table")
+    with _on(rows.device, stream) as st:
+        check(lib.mnerf_adamw_step(rows.data_ptr(), int(n_rows), int(n_blocks), groups, len(groups), _ptr(sumsq), st),
+              "mnerf_adamw_step")
+
+
+def l2_loss(pred, target, weight=1.0, want_grad=True, stream=None):
+    """weight * mean((pred - target)^2) as a 0-d tensor and its gradient with respect to ``pred`` (or None), one launch, deterministic."""
+    import torch
+    lib = load()
+    if not pred.is_cuda:
+        raise MnerfError(f"l2_loss: the HIP kernels need CUDA tensors, got device {pred.device} (there is no CPU fallback)")
+    _f32c(pred, "pred"), _f32c(target, "target")
+    if pred.shape != target.shape or pred.numel() == 0 or pred.device != target.device:
+        raise MnerfError(f"l2_loss: pred {tuple(pred.shape)} on {pred.device} vs target {tuple(target.shape)} on {target.device}")
+    loss = torch.empty((), device=pred.device)
+    grad = torch.empty_like(pred) if want_grad else None
+    with _on(pred.device, stream) as st:
+        check(lib.mnerf_l2_loss(_ptr(pred), _ptr(target), pred.numel(), float(weight), _ptr(loss), _ptr(grad), st), "mnerf_l2_loss")
+    return loss, grad

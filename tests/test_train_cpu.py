@@ -1,0 +1,280 @@
+"""Host side of stand-alone training, without a GPU: Coach.setup_optimizer's parameter groups and scheduler, the checkpoint round
+trip of the training state, and FusedAdamW's state interop / refusal of CPU tensors."""
+import copy
+import os
+
+import pytest
+import torch
+
+from matchnerf_amd import hip, options
+from matchnerf_amd.coach import Coach
+from matchnerf_amd.edict import EasyDict
+
+
+class StubLoader:
+    """stands for a DataLoader: a length, a name and a few tiny batches"""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def get_name(self):
+        return "stub"
+
+    def __iter__(self):
+        for i in range(self.n):
+            g = torch.Generator().manual_seed(i)
+            yield {"images": torch.rand(1, 4, 3, 4, 4, generator=g)}
+
+
+def make_coach(tmp_path, monkeypatch, name, extra=(), n_train=7, build=True):
+    monkeypatch.chdir(tmp_path)
+    cmd = options.parse_arguments(["--yaml=train", f"--name={name}", "--cpu=true", "--max_epoch=3", "--tb=false",
+                                   f"--output_root={tmp_path}"] + list(extra))
+    opt = options.set(cmd, verbose=False)
+    assert opt.device == "cpu"
+    c = Coach(opt)
+    if build:
+        c.build_networks()
+    c.train_loader = StubLoader(n_train)
+    return c
+
+
+def test_setup_optimizer_groups_and_one_cycle_schedule(tmp_path, monkeypatch):
+    c = make_coach(tmp_path, monkeypatch, "groups")
+    c.setup_optimizer()
+    o = c.opts.optim
+    assert len(c.optim.param_groups) == 2
+    enc, dec = c.optim.param_groups
+    assert [id(p) for p in enc["params"]] == [id(p) for p in c.model.feat_enc.parameters()]
+    assert [id(p) for p in dec["params"]] == [id(p) for p in c.model.nerf_dec.parameters()]
+    assert enc["weight_decay"] == dec["weight_decay"] == o.algo.weight_decay == 1e-4
+    assert isinstance(c.optim, torch.optim.AdamW)
+    # the rates over all steps: those of a OneCycleLR built directly with the recipe
+    steps = c.opts.max_epoch * (len(c.train_loader) // c.opts.batch_size)
+    ps = [torch.nn.Parameter(torch.zeros(1)), torch.nn.Parameter(torch.zeros(1))]
+    ref_opt = torch.optim.AdamW([dict(params=[ps[0]], lr=o.lr_enc), dict(params=[ps[1]], lr=o.lr_dec)], weight_decay=1e-4)
+    ref = torch.optim.lr_scheduler.OneCycleLR(ref_opt, max_lr=[o.lr_enc, o.lr_dec], epochs=c.opts.max_epoch,
+                                              steps_per_epoch=len(c.train_loader) // c.opts.batch_size, pct_start=0.05,
+                                              cycle_momentum=False, anneal_strategy="cos")
+    assert c.sched_type == "OneCycleLR" and c.sched.total_steps == steps == 21
+    for i in range(steps):
+        assert [g["lr"] for g in c.optim.param_groups] == [g["lr"] for g in ref_opt.param_groups], i
+        assert c.get_cur_lrates() == dict(enc=ref.get_last_lr()[0], dec=ref.get_last_lr()[1])
+        if i + 1 < steps:
+            c.optim.step(), c.sched.step()
+            ref_opt.step(), ref.step()
+
+
+def test_fused_path_is_chosen_for_adamw_and_carries_the_clip(tmp_path, monkeypatch):
+    from matchnerf_amd.optim import FusedAdamW
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "1")
+    c = make_coach(tmp_path, monkeypatch, "fused")
+    c.setup_optimizer()
+    assert isinstance(c.optim, FusedAdamW) and c.fused_optim
+    assert c.optim.param_groups[0]["max_norm"] == c.opts.optim.clip_enc == 1.0
+    assert not c.optim.param_groups[1].get("max_norm")
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "0")
+    c.setup_optimizer()
+    assert type(c.optim) is torch.optim.AdamW and not c.fused_optim
+
+
+def test_zero_encoder_rate_freezes_the_encoder(tmp_path, monkeypatch):
+    c = make_coach(tmp_path, monkeypatch, "finetune", ["--optim.lr_enc=0"])
+    c.setup_optimizer()
+    assert len(c.optim.param_groups) == 1
+    assert c.optim.param_groups[0]["lr"] <= c.opts.optim.lr_dec
+    assert all(not p.requires_grad for p in c.model.feat_enc.parameters())
+    assert all(p.requires_grad for p in c.model.nerf_dec.parameters())
+    assert c.get_cur_lrates()["enc"] == 0
+
+
+def test_more_than_one_gpu_is_refused(tmp_path, monkeypatch):
+    c = make_coach(tmp_path, monkeypatch, "multi", ["--gpu_ids=0,1"])
+    with pytest.raises(NotImplementedError):
+        c.setup_optimizer()
+
+
+class StubModel(torch.nn.Module):
+    """two children with the model's names; 'renders' the target pixels at fixed rays from its parameters"""
+
+    def __init__(self, opts=None):
+        super().__init__()
+        torch.manual_seed(3)
+        self.feat_enc = torch.nn.Linear(3, 3)
+        self.nerf_dec = torch.nn.Linear(3, 3)
+
+    def forward(self, var, mode=None):
+        var.ray_idx = torch.tensor([1, 5, 7, 11])
+        px = var.images[:, 0].reshape(1, 3, -1).permute(0, 2, 1)[:, var.ray_idx]
+        var.rgb = self.nerf_dec(self.feat_enc(px))
+        return var
+
+
+def stub_coach(tmp_path, monkeypatch, extra=()):
+    from matchnerf_amd import models
+    monkeypatch.setitem(models.models_dict, "stub", StubModel)
+    c = make_coach(tmp_path, monkeypatch, "roundtrip", ["--model=stub", "--nerf.rand_rays_train=4", "--freq.scalar=1"] + list(extra),
+                   n_train=5)
+    c.setup_optimizer()
+    return c
+
+
+def test_checkpoint_round_trip_resumes_the_training_state(tmp_path, monkeypatch):
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "0")
+    c = stub_coach(tmp_path, monkeypatch)
+    assert type(c.optim) is torch.optim.AdamW
+    c.restore_checkpoint()  # nothing to load: the module keeps its own initialisation
+    c.it, c.ep = 0, 0
+    batches = list(c.train_loader)
+    losses = []
+    for b in batches[:2]:
+        losses.append(float(c.train_iteration(EasyDict(b)).all.detach()))
+        c.sched.step()
+    assert c.it == 2 and all(l > 0 for l in losses)
+    c.save_checkpoint(ep=0, it=c.it, backup_ckpt=True)
+    models_dir = os.path.join(c.opts.output_path, "models")
+    latest = torch.load(os.path.join(models_dir, "latest.pth"), weights_only=False)
+    assert set(latest) == {"model", "optim", "sched", "epoch", "iter"}
+    slim = torch.load(os.path.join(models_dir, "ep0_it2.pth"), weights_only=False)
+    assert set(slim) == {"model", "epoch", "iter"}
+    lines = open(os.path.join(c.opts.output_path, "scalars.jsonl")).read().splitlines()
+    assert len(lines) == 2 * 3  # loss_render, lrate_enc, lrate_dec per iteration
+
+    r = stub_coach(tmp_path, monkeypatch, ["--resume=true"])
+    r.restore_checkpoint()
+    assert (r.epoch_start, r.iter_start) == (0, 2)
+    for a, b in zip(c.model.parameters(), r.model.parameters()):
+        assert torch.equal(a, b)
+    sa, sb = c.optim.state_dict()["state"], r.optim.state_dict()["state"]
+    assert sa.keys() == sb.keys() and len(sa) == 4
+    for k in sa:
+        assert float(sa[k]["step"]) == float(sb[k]["step"]) == 2.0
+        assert torch.equal(sa[k]["exp_avg"], sb[k]["exp_avg"]) and torch.equal(sa[k]["exp_avg_sq"], sb[k]["exp_avg_sq"])
+    assert [g["lr"] for g in r.optim.param_groups] == [g["lr"] for g in c.optim.param_groups]
+    assert r.get_cur_lrates() == c.get_cur_lrates()
+    # and the third iteration of both runs is the same iteration
+    r.it, r.ep = r.iter_start, r.epoch_start
+    la = float(c.train_iteration(EasyDict(copy.deepcopy(batches[2]))).all.detach())
+    lb = float(r.train_iteration(EasyDict(copy.deepcopy(batches[2]))).all.detach())
+    assert la == lb
+    for a, b in zip(c.model.parameters(), r.model.parameters()):
+        assert torch.equal(a, b)
+
+
+def test_train_epoch_skips_the_iterations_a_resumed_run_has_done(tmp_path, monkeypatch):
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "0")
+    c = stub_coach(tmp_path, monkeypatch, ["--resume=true", "--freq.ckpt_ep=1", "--freq.val_it=-1", "--freq.val_ep=-1",
+                                           "--freq.ckpt_it=-1", "--freq.test_ep=-1"])
+    c.iter_start, c.epoch_start = 3, 0
+    c.it, c.ep, c.timer = 3, 0, None
+    c.val_it = c.test_it = c.ckpt_it = -1
+    c.train_epoch()
+    assert c.it == 5  # 5 batches, 3 of them done before
+    assert torch.load(os.path.join(c.opts.output_path, "models", "latest.pth"), weights_only=False)["iter"] == 5
+
+
+def test_inference_without_a_checkpoint_still_gets_seeded_weights(tmp_path, monkeypatch):
+    """Regression guard, not a test of the feature (it passes without it): test.py's behaviour must not change - no optimizer has
+    been set up, so restore_checkpoint() still falls back to the seeded weights."""
+    from matchnerf_amd import synthetic as syn
+    c = make_coach(tmp_path, monkeypatch, "infer")
+    c.restore_checkpoint()
+    want = syn.to_torch(syn.seeded_state_dict(syn.state_dict_spec(n_src_views=3), 1))
+    got = c.model.state_dict()
+    assert all(torch.equal(got[k], want[k]) for k in want)
+
+
+def test_fused_adamw_refuses_cpu_tensors_and_unsupported_variants():
+    from matchnerf_amd.optim import FusedAdamW
+    p = torch.nn.Parameter(torch.randn(5))
+    o = FusedAdamW([p], lr=1e-3)
+    o.step()  # no gradient anywhere: nothing to do, nothing launched
+    p.grad = torch.randn(5)
+    before = p.detach().clone()
+    with pytest.raises(hip.MnerfError):
+        o.step()
+    assert torch.equal(p.detach(), before) and len(o.state) == 0
+    for kw in (dict(amsgrad=True), dict(maximize=True), dict(capturable=True), dict(fused=True)):
+        with pytest.raises(ValueError):
+            FusedAdamW([p], **kw)
+    with pytest.raises(TypeError):
+        FusedAdamW([torch.nn.Parameter(torch.randn(5, dtype=torch.float64))])
+    o.param_groups[0]["amsgrad"] = True
+    with pytest.raises(ValueError):
+        o.step()
+
+
+def test_fused_adamw_state_dict_is_torchs():
+    from matchnerf_amd.optim import FusedAdamW
+    torch.manual_seed(0)
+    ps = [torch.nn.Parameter(torch.randn(4, 3)), torch.nn.Parameter(torch.randn(7))]
+    ref = torch.optim.AdamW([dict(params=ps[:1], lr=1e-3), dict(params=ps[1:], lr=2e-3)], weight_decay=1e-4)
+    for _ in range(3):
+        for p in ps:
+            p.grad = torch.randn_like(p)
+        ref.step()
+    sd = ref.state_dict()
+    qs = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    fused = FusedAdamW([dict(params=qs[:1], lr=5.0), dict(params=qs[1:], lr=5.0)], weight_decay=0.5)
+    fused.load_state_dict(copy.deepcopy(sd))
+    got = fused.state_dict()
+    assert got["param_groups"] == sd["param_groups"]
+    assert got["state"].keys() == sd["state"].keys()
+    for k, st in sd["state"].items():
+        assert set(got["state"][k]) == set(st) == {"step", "exp_avg", "exp_avg_sq"}
+        for name in st:
+            assert torch.equal(got["state"][k][name], st[name]) and got["state"][k][name].dtype == st[name].dtype
+    # and back: torch's AdamW takes a FusedAdamW state (the extra per-group `max_norm` key rides along)
+    fused.param_groups[0]["max_norm"] = 1.0
+    back = torch.optim.AdamW([dict(params=ps[:1]), dict(params=ps[1:])])
+    back.load_state_dict(fused.state_dict())
+    assert [g["lr"] for g in back.param_groups] == [1e-3, 2e-3]
+
+
+def test_optim_entry_points_check_their_arguments_on_the_host():
+    """mnerf_adamw_step / mnerf_grad_sumsq / mnerf_l2_loss refuse malformed calls before anything is launched (no GPU needed)"""
+    lib = hip.load()
+    groups = hip.optim_groups([(1e-3, 0.9, 0.999, 1e-8, 1e-2, 1.0, 3), (1e-3, 0.9, 0.999, 1e-8, 1e-2, None, 2)])
+    assert groups[0].max_norm == 1.0 and groups[1].max_norm == 0.0 and groups[1].n_blocks == 2
+    assert lib.mnerf_adamw_step(None, 2, 5, groups, 2, None, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_adamw_step(16, 2, 6, groups, 2, None, None) == hip.MNERF_E_RANGE and b"add up to 5" in lib.mnerf_last_error()
+    assert lib.mnerf_adamw_step(16, 2, 5, groups, 2, None, None) == hip.MNERF_E_NULL  # a clipping group needs the norms
+    assert lib.mnerf_adamw_step(20, 2, 5, groups, 2, 32, None) == hip.MNERF_E_ALIGN
+    assert lib.mnerf_grad_sumsq(16, 2, 5, groups, 2, None, None, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_grad_sumsq(16, 0, 5, groups, 2, 32, 32, None) == hip.MNERF_E_RANGE
+    assert lib.mnerf_l2_loss(None, None, 4, 1.0, None, None, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_l2_loss(16, 16, 0, 1.0, 16, None, None) == hip.MNERF_E_RANGE
+    assert lib.mnerf_optim_row_blocks(1) == 1 and lib.mnerf_optim_row_blocks(hip.OPTIM_CHUNK + 1) == 2 and lib.mnerf_optim_row_blocks(0) == -1
+    with pytest.raises(hip.MnerfError):
+        hip.optim_groups([(1e-3, 0.9, 0.999, 1e-8, 0, 0, 1)] * (hip.OPTIM_MAX_GROUPS + 1))
+    import ctypes
+    assert ctypes.sizeof(hip.OptimRow) == 64 == lib.mnerf_struct_size(8) and lib.mnerf_struct_size(9) == ctypes.sizeof(hip.OptimGroup)
+
+
+def test_resuming_a_torch_written_state_on_the_fused_path_keeps_the_clip(tmp_path, monkeypatch):
+    """load_state_dict replaces the parameter groups by the saved ones; a latest.pth from torch's AdamW (or the reference) has no
+    `max_norm`, so Coach puts optim.clip_enc back on the encoder group after the restore - and train_iteration refuses to run
+    a fused step whose encoder group has lost it."""
+    from matchnerf_amd.optim import FusedAdamW
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "0")
+    c = stub_coach(tmp_path, monkeypatch)
+    c.it, c.ep = 0, 0
+    c.train_iteration(EasyDict(next(iter(c.train_loader))))
+    c.save_checkpoint(ep=0, it=1)
+    saved = torch.load(os.path.join(c.opts.output_path, "models", "latest.pth"), weights_only=False)
+    assert all("max_norm" not in g for g in saved["optim"]["param_groups"])
+    monkeypatch.setenv("MNERF_FUSED_OPTIM", "1")
+    r = stub_coach(tmp_path, monkeypatch, ["--resume=true"])
+    assert isinstance(r.optim, FusedAdamW)
+    r.restore_checkpoint()
+    assert r.iter_start == 1 and r.optim.param_groups[0]["max_norm"] == r.opts.optim.clip_enc == 1.0
+    assert not r.optim.param_groups[1].get("max_norm")
+    # a bare load_state_dict() loses the key; the iteration says so instead of training without clipping
+    r.optim.load_state_dict(saved["optim"])
+    assert r.optim.param_groups[0].get("max_norm") is None
+    r.it, r.ep = 1, 0
+    with pytest.raises(RuntimeError, match="max_norm"):
+        r.train_iteration(EasyDict(next(iter(r.train_loader))))
