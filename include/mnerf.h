@@ -38,6 +38,8 @@
  *       mnerf_cost_volume_operand_bytes).  NULL keeps the segment walk.
  *   v10 no layout change of the older structs: the tail of a training iteration (matchnerf_amd/csrc/optim.hip) - mnerf_optim_row
  *       and mnerf_optim_group - struct indices 8 and 9 -, mnerf_optim_row_blocks, mnerf_grad_sumsq, mnerf_adamw_step, mnerf_l2_loss.
+ *   v11 no layout change: the gradient exchange of data-parallel training over the same row table - mnerf_grad_bucket_floats,
+ *       mnerf_grad_pack, mnerf_grad_unpack.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define MNERF_ABI_VERSION 10
+#define MNERF_ABI_VERSION 11
 #define MNERF_MAX_VIEWS 16
 #define MNERF_FEAT_CH 128 /* channels of one pair-specific GMFlow feature map */
 /* floats per sample of a `cond` buffer: sum(cos_n_group) + 4 n_views + 1, rounded up to a multiple of 8.
@@ -625,6 +627,21 @@ int mnerf_adamw_step(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_bloc
 /* loss[0] = weight * mean((pred - target)^2) over n elements and, unless grad is NULL, grad[i] = 2 weight (pred[i] - target[i]) / n
  * (coach.py:36-38, 257 and its autograd).  One launch of one workgroup, fixed summation order: bit-reproducible. */
 int mnerf_l2_loss(const float* pred, const float* target, int64_t n, float weight, float* loss, float* grad, void* stream);
+
+/* ABI v11 - data-parallel training: the gradients of all rows of the table above as ONE contiguous bucket, so that one collective
+ * sums them over the ranks.  Chunk b of the table (b = block_begin of its row + chunk within the row) lies at float offset
+ * b * MNERF_OPTIM_CHUNK - every row starts 16-byte aligned whatever its gradient's own alignment -, elements behind numel are
+ * zero, and one more chunk of MNERF_OPTIM_CHUNK side slots follows the n_blocks chunks (the iteration's loss rides there).
+ * Only grad, numel and block_begin of a row are read.  bucket: 16-byte aligned, mnerf_grad_bucket_floats(n_blocks) floats. */
+/* floats of the bucket of a table of n_blocks chunks: (n_blocks + 1) * MNERF_OPTIM_CHUNK (host only; -1 for n_blocks < 1) */
+int64_t mnerf_grad_bucket_floats(int64_t n_blocks);
+/* One launch: every gradient chunk into its slot, zeros behind numel; side[0, n_side) (device; NULL with n_side 0) into the side
+ * chunk, zeros behind it.  n_side <= MNERF_OPTIM_CHUNK. */
+int mnerf_grad_pack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const float* side, int32_t n_side,
+                    float* bucket, void* stream);
+/* One launch: grad = bucket * scale for every row (one fp32 multiply per element), side_out[0, n_side) = side slots * scale. */
+int mnerf_grad_unpack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const float* bucket, float scale,
+                      float* side_out, int32_t n_side, void* stream);
 
 #ifdef __cplusplus
 }

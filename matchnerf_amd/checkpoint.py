@@ -12,8 +12,11 @@ def child_state_dict(state_dict, key):
     return {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
 
 
-def restore_checkpoint(model, ckpt_path, device, resume=False, optims_scheds=None, log=print):
+def restore_checkpoint(model, ckpt_path, device, resume=False, optims_scheds=None, log=print, extra=None):
+    """``extra``: a dict that receives the file's other entries (``world_size`` of a data-parallel run)"""
     ckpt = torch.load(ckpt_path, map_location=device)
+    if extra is not None:
+        extra.update({k: v for k, v in ckpt.items() if k not in ("model", "optim", "sched", "epoch", "iter")})
     for name, child in model.named_children():
         sd = child_state_dict(ckpt["model"], name)
         if sd:

@@ -4,7 +4,16 @@ parameter groups / scheduler of the reference's recipe, ``train_iteration`` = ze
 clip + AdamW (the loss is one launch and clip + step are three: optim.FusedAdamW; MNERF_FUSED_OPTIM=0: torch's ops), checkpoints in the reference's format, scalars to
 ``<output_path>/scalars.jsonl`` (TensorBoard only where it can be imported).  A dataset is anything that yields batches with the
 reference's contract (images, extrinsics, intrinsics, near_fars[, depth, scene, view_ids]); ``synthetic`` is built in so the tools
-run offline.  One GPU: ``gpu_ids`` longer than one raises in ``setup_optimizer``."""
+run offline.
+
+Data-parallel training (train.py starts one process per GPU of ``gpu_ids``): every rank holds a full replica and runs the iteration
+above on its own ``batch_size`` scenes; between backward and clip + step the gradients of all ranks are summed and multiplied by fp32(1 / W)
+(optim.GradBucket: two HIP launches around ONE collective; the torch optimizers take optim.reduce_gradients_torch), then every rank
+clips and steps on identical values, so the replicas stay bit-identical with no later exchange.  The effective batch is W x
+``batch_size`` and the learning rates are NOT rescaled.  Rank r draws its rays and offsets from ``seed + r`` (dist.reseed), the order
+of the scenes comes from (seed, epoch) alone, rank 0's weights (and, on a resume, optimizer and scheduler state) are broadcast after
+``restore_checkpoint``, and only rank 0 writes checkpoints, scalars, images and prints.  ``gpu_ids`` longer than one WITHOUT a process
+group of that size still raises in ``setup_optimizer``: the in-process DataParallel form is not built."""
 import json
 import math
 import os
@@ -14,6 +23,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, datasets, metrics, synthetic
+from . import dist as mdist
 from .edict import EasyDict as edict
 from .models import models_dict
 
@@ -27,9 +37,13 @@ def fused_optim_enabled():
 class SyntheticScenes:
     """Seeded stand-in for a dataset (no DTU/LLFF/Blender data offline)."""
 
-    def __init__(self, name, cfg, n_src_views, shuffle=False):
+    def __init__(self, name, cfg, n_src_views, shuffle=False, rank=0, world=1, seed=None):
         self.name = name
         self.shuffle = shuffle  # training: a fresh order of the scenes every epoch (torch's generator)
+        # data-parallel training (``seed`` given): the order comes from a generator of its own seeded by seed + epoch - the same on
+        # every rank whatever the global generators hold -, rank r takes elements r, r + world, ... and the tail that does not
+        # divide is dropped, so every rank runs the same number of iterations (torch's DistributedSampler with drop_last)
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
         w, h = cfg.get("img_wh", [64, 64])
         self.kw = dict(height=h, width=w, n_src_views=n_src_views, wide=(name == "blender"),
                        near_far=(2.0, 6.0) if name == "blender" else (2.125, 4.525))
@@ -40,10 +54,21 @@ class SyntheticScenes:
         return self.name
 
     def __len__(self):
-        return self.n
+        return self.n // self.world
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def indices(self):
+        if self.seed is None:
+            return torch.randperm(self.n).tolist() if self.shuffle else list(range(self.n))
+        order = list(range(self.n))
+        if self.shuffle:
+            order = torch.randperm(self.n, generator=torch.Generator().manual_seed(int(self.seed) + self.epoch)).tolist()
+        return order[self.rank:(self.n // self.world) * self.world:self.world]
 
     def __iter__(self):
-        for i in (torch.randperm(self.n).tolist() if self.shuffle else range(self.n)):
+        for i in self.indices():
             sc = synthetic.make_scene(seed=100 + i, **self.kw)
             batch = {k: torch.from_numpy(v) for k, v in sc.items()}
             batch["scene"] = [f"synthetic{i}"]
@@ -58,6 +83,10 @@ class Coach:
         self.device = opts.device
         self.epoch_start = 0
         self.iter_start = 0
+        # data-parallel training: the process group train.py (or torchrun) has set up; MNERF_DIST_INIT_ALWAYS makes a one-rank
+        # group take the exchange too (tests, timing)
+        self.rank, self.world = mdist.rank_world()
+        self.distributed = mdist.group_active(always=bool(os.environ.get("MNERF_DIST_INIT_ALWAYS")))
 
     def build_networks(self):
         self.model = models_dict[self.opts.model](self.opts).to(self.opts.device)  # coach.py:77
@@ -72,24 +101,87 @@ class Coach:
         latest = os.path.join(self.opts.output_path, "models", "latest.pth")
         if getattr(self.opts, "resume", False) and training and os.path.isfile(latest):
             state = {k: getattr(self, k) for k in ("optim", "sched") if getattr(self, k, None) is not None}
-            ep, it = checkpoint.restore_checkpoint(self.model, latest, self.opts.device, resume=True, optims_scheds=state)
+            self._ckpt_extra = {}
+            ep, it = checkpoint.restore_checkpoint(self.model, latest, self.opts.device, resume=True, optims_scheds=state,
+                                                   log=self.say, extra=self._ckpt_extra)
             self.epoch_start, self.iter_start = int(ep or 0), int(it or 0)
             self.apply_clip_enc()  # the saved param_groups replaced the live ones
-            print(f"[coach] resuming from epoch {self.epoch_start} (iteration {self.iter_start})")
+            self.say(f"[coach] resuming from epoch {self.epoch_start} (iteration {self.iter_start})")
+            self._check_resumed_world(latest)
         elif path and os.path.isfile(path):
-            checkpoint.restore_checkpoint(self.model, path, self.opts.device)
+            checkpoint.restore_checkpoint(self.model, path, self.opts.device, log=self.say)
         elif training:
             if getattr(self.opts, "resume", False):
-                print(f"[coach] no checkpoint at {latest!r}: training starts from scratch")
+                self.say(f"[coach] no checkpoint at {latest!r}: training starts from scratch")
             pre = self.opts.encoder.pretrain_weight
             if pre and os.path.isfile(pre):
                 checkpoint.load_gmflow_checkpoint(self.model.feat_enc, pre, self.opts.device,
                                                   gmflow_n_blocks=self.opts.encoder.num_transformer_layers)
-                print(f"[coach] encoder initialised from {pre}")
+                self.say(f"[coach] encoder initialised from {pre}")
         else:
-            print(f"[coach] checkpoint {path!r} not found: using seeded random weights (offline run)")
+            self.say(f"[coach] checkpoint {path!r} not found: using seeded random weights (offline run)")
             spec = synthetic.state_dict_spec(n_src_views=self.n_src_views)
             self.model.load_state_dict(synthetic.to_torch(synthetic.seeded_state_dict(spec, 1), self.opts.device))
+        if training and self.distributed:
+            self.sync_replicas(resumed=bool(getattr(self.opts, "resume", False)))
+
+    def say(self, *args):
+        """print on rank 0 only"""
+        if self.rank == 0:
+            print(*args)
+
+    def _epoch_len(self, world):
+        """iterations of one epoch per rank at ``world`` ranks (what len(train_loader) is at the current world size)"""
+        if not hasattr(self, "_n_train"):  # a loader that was handed in: only its length per rank is known
+            return len(self.train_loader) * self.world // world
+        return math.ceil((self._n_train // world) / self._train_batch)
+
+    def _check_resumed_world(self, latest):
+        """The checkpoint records the world size it was written at (no key: one process).  `iter` counts optimizer steps and an
+        epoch has len(dataset) // W of them per rank, so a checkpoint written in the MIDDLE of an epoch only resumes at its own
+        world size; one written at an epoch boundary resumes at any (the new run starts that epoch from its first batch)."""
+        saved = int(self._ckpt_extra.get("world_size", 1))
+        if saved == self.world or not hasattr(self, "train_loader"):
+            return
+        if self.iter_start != self.epoch_start * self._epoch_len(saved):
+            raise RuntimeError(f"{latest} was written in the middle of epoch {self.epoch_start} (iteration {self.iter_start}) by a run "
+                               f"of world size {saved}; this run has world size {self.world}.  A mid-epoch checkpoint resumes only at "
+                               "the world size it was written at (resume with the same number of GPUs, or from an epoch-boundary "
+                               "checkpoint)")
+        self._skip_to = self.epoch_start * len(self.train_loader)  # nothing of epoch `epoch_start` has been done
+        if getattr(self, "sched_type", None) == "OneCycleLR":
+            # the saved schedule counts the OLD world size's steps per epoch (its total_steps would end early or never): a fresh
+            # one for this run's length, advanced to the same epoch
+            import warnings
+            for g in self.optim.param_groups:
+                g.pop("initial_lr", None)
+            self._make_sched()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")  # "lr_scheduler.step() before optimizer.step()": a fast-forward, not training
+                for _ in range(self.epoch_start * len(self.train_loader)):  # train_epoch steps it once per batch
+                    self.sched.step()
+
+    def sync_replicas(self, resumed=False):
+        """Rank 0's model state - and after a resume its optimizer / scheduler state and position - on every rank, so identical
+        replicas do not depend on every rank having read the same file or having initialised in the same order."""
+        tensors = list(self.model.state_dict().values())
+        with torch.no_grad():
+            for dtype in sorted({t.dtype for t in tensors}, key=str):
+                mdist.broadcast_tensors([t for t in tensors if t.dtype == dtype], src=0)
+        if resumed:
+            state = None
+            if self.rank == 0:
+                state = dict(optim=mdist.to_host(self.optim.state_dict()), sched=self.sched.state_dict() if self.sched is not None else None,
+                             epoch=self.epoch_start, iter=self.iter_start, skip_to=getattr(self, "_skip_to", None))
+            state = mdist.broadcast_object(state, src=0, device=self.opts.device)
+            if self.rank != 0:
+                self.optim.load_state_dict(state["optim"])
+                if self.sched is not None and state["sched"] is not None:
+                    self.sched.load_state_dict(state["sched"])
+                self.epoch_start, self.iter_start = state["epoch"], state["iter"]
+                if state["skip_to"] is not None:
+                    self._skip_to = state["skip_to"]
+                self.apply_clip_enc()
 
     def _loader(self, name, cfg, split):
         """One entry of the options' data sections: the on-disk producer where ``root_dir`` exists, synthetic scenes otherwise."""
@@ -105,11 +197,26 @@ class Coach:
             workers = cfg.get("num_workers", 0)
             if split != "test":
                 workers = min(int(workers or 0), 16)
-            loader = torch.utils.data.DataLoader(ds, shuffle=train, num_workers=workers, batch_size=self.opts.batch_size,
-                                                 pin_memory=True)
+            sampler = None
+            if train and self.distributed:  # the order from (seed, epoch) alone, the tail that does not divide dropped
+                sampler = torch.utils.data.DistributedSampler(ds, num_replicas=self.world, rank=self.rank, shuffle=True,
+                                                              seed=int(self.opts.seed or 0), drop_last=True)
+                self._train_sampler = sampler
+            if train:
+                self._n_train, self._train_batch = len(ds), self.opts.batch_size
+            loader = torch.utils.data.DataLoader(ds, shuffle=train and sampler is None, sampler=sampler, num_workers=workers,
+                                                 batch_size=self.opts.batch_size, pin_memory=True)
             loader.get_name = ds.get_name
             return loader
-        return SyntheticScenes(name, cfg, self.n_src_views, shuffle=train)
+        if train and self.distributed:
+            scenes = SyntheticScenes(name, cfg, self.n_src_views, shuffle=True, rank=self.rank, world=self.world,
+                                     seed=int(self.opts.seed or 0))
+            self._n_train, self._train_batch = scenes.n, 1
+            return scenes
+        scenes = SyntheticScenes(name, cfg, self.n_src_views, shuffle=train)
+        if train:
+            self._n_train, self._train_batch = scenes.n, 1
+        return scenes
 
     def load_dataset(self, splits=("test",), loaders=None):
         """``loaders``: optional list of iterables of batches (objects with get_name()) for the test split; otherwise
@@ -139,8 +246,11 @@ class Coach:
         AdamW runs on the fused HIP step (optim.FusedAdamW, ``clip_enc`` as the encoder group's ``max_norm``); with
         ``MNERF_FUSED_OPTIM=0``, and for every other algorithm, the optimizer is ``torch.optim``'s, with ``clip_grad_norm_`` in ``train_iteration``."""
         o = self.opts.optim
-        if len(self.opts.gpu_ids) > 1:
-            raise NotImplementedError(f"training runs on one GPU; gpu_ids = {list(self.opts.gpu_ids)}")
+        if len(self.opts.gpu_ids) > 1 and not (mdist.group_active(always=True) and self.world == len(self.opts.gpu_ids)):
+            raise NotImplementedError(f"gpu_ids = {list(self.opts.gpu_ids)} needs one process per GPU in a process group of that size "
+                                      f"(found {'world size ' + str(self.world) if mdist.group_active(always=True) else 'none'}): start "
+                                      "the run with `python train.py --gpu_ids=...`, which launches the ranks; the in-process "
+                                      "DataParallel form is not built")
         groups, rates = [], []
         self._enc_group = None
         for child, rate in ((self.model.feat_enc, o.lr_enc), (self.model.nerf_dec, o.lr_dec)):
@@ -160,7 +270,17 @@ class Coach:
             self.apply_clip_enc()
         else:
             self.optim = getattr(torch.optim, kind)(groups, **kwargs)
-        print(f"[coach] {'fused HIP ' if self.fused_optim else ''}{kind} ({', '.join(f'{k}={v}' for k, v in kwargs.items())})")
+        if self.distributed:
+            from . import optim as moptim
+            self._bucket = moptim.GradBucket() if self.fused_optim else None
+            self.say(f"[coach] data-parallel: {self.world} ranks, effective batch {self.world} x {self.opts.batch_size} scenes, "
+                     "learning rates not rescaled")
+        self.say(f"[coach] {'fused HIP ' if self.fused_optim else ''}{kind} ({', '.join(f'{k}={v}' for k, v in kwargs.items())})")
+        self._rates = rates
+        self._make_sched()
+
+    def _make_sched(self):
+        o = self.opts.optim
         self.sched_type, self.sched = None, None
         if o.get("sched"):
             self.sched_type = o.sched.type
@@ -168,7 +288,7 @@ class Coach:
             if self.sched_type == "OneCycleLR":
                 assert hasattr(self, "train_loader"), "load the training data first: OneCycleLR needs the number of steps"
                 kwargs.update(epochs=self.opts.max_epoch, steps_per_epoch=len(self.train_loader) // self.opts.batch_size,
-                              max_lr=rates)
+                              max_lr=self._rates)
             self.sched = getattr(torch.optim.lr_scheduler, self.sched_type)(self.optim, **kwargs)
 
     def apply_clip_enc(self):
@@ -181,7 +301,7 @@ class Coach:
         """Scalars always go to <output_path>/scalars.jsonl; a TensorBoard writer is added when ``opts.tb`` is set AND the package
         can be imported."""
         self.tb = None
-        if getattr(self.opts, "tb", False):
+        if getattr(self.opts, "tb", False) and self.rank == 0:
             try:
                 from torch.utils import tensorboard
                 self.tb = tensorboard.SummaryWriter(log_dir=self.opts.output_path, flush_secs=10)
@@ -189,7 +309,9 @@ class Coach:
                 print("[coach] tensorboard is not installed: scalars go to scalars.jsonl only")
 
     def log_scalars(self, scalars, step, split):
-        """{tag: value} -> one line per value in scalars.jsonl (+ TensorBoard)"""
+        """{tag: value} -> one line per value in scalars.jsonl (+ TensorBoard); rank 0 only"""
+        if self.rank != 0:
+            return
         with open(os.path.join(self.opts.output_path, "scalars.jsonl"), "a") as f:
             for tag, value in scalars.items():
                 f.write(json.dumps({"step": int(step), "split": split, "tag": tag, "value": float(value)}) + "\n")
@@ -209,40 +331,62 @@ class Coach:
         self.val_it, self.test_it, self.ckpt_it = self._every(f.val_it), self._every(f.test_it), self._every(f.ckpt_it)
         self.timer = edict(start=time.time(), it_mean=None)
         if getattr(self.opts, "sanity_check", False) and self.it == 0 and self.val_it > 0:
-            self.validate_model(first_only=True)
-        print(f"[coach] training: epochs {self.epoch_start}..{self.opts.max_epoch - 1}, {len(self.train_loader)} iterations each")
+            self.rank0_then_barrier(lambda: self.validate_model(first_only=True))
+        self.say(f"[coach] training: epochs {self.epoch_start}..{self.opts.max_epoch - 1}, {len(self.train_loader)} iterations each")
         for self.ep in range(self.epoch_start, self.opts.max_epoch):
             self.train_epoch()
         if getattr(self, "tb", None) is not None:
             self.tb.flush()
             self.tb.close()
-        print(f"[coach] training done: {self.it} iterations")
+        self.say(f"[coach] training done: {self.it} iterations")
 
     def train_epoch(self):
         f = self.opts.freq
         self.model.train()
-        loss, n = None, len(self.train_loader)
+        loss, n = None, len(self.train_loader)  # per rank: `it` counts optimizer steps
+        for owner in (self.train_loader, getattr(self, "_train_sampler", None)):
+            if hasattr(owner, "set_epoch"):
+                owner.set_epoch(self.ep)  # the same order on every rank, from (seed, epoch)
+        skip_to = getattr(self, "_skip_to", self.iter_start)
         for bi, batch in enumerate(self.train_loader):
-            if getattr(self.opts, "resume", False) and self.ep * n + bi < self.iter_start:
+            if getattr(self.opts, "resume", False) and self.ep * n + bi < skip_to:
                 continue  # iterations the resumed run has already done
             var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
             loss = self.train_iteration(var)
             if self.sched_type == "OneCycleLR":
                 self.sched.step()
-        if loss is not None and f.log_ep > 0 and (self.ep + 1) % f.log_ep == 0:
+        if loss is not None and f.log_ep > 0 and (self.ep + 1) % f.log_ep == 0 and self.rank == 0:
             lr = self.get_cur_lrates()
             timer = getattr(self, "timer", None)
-            print(f"[coach] epoch {self.ep + 1}: loss {float(loss.all.detach()):.5f}  lr enc {lr['enc']:.3e} dec {lr['dec']:.3e}"
+            shown = float(loss.all.detach()) if getattr(self, "_loss_mean", None) is None else float(self._loss_mean[0])  # mean over ranks
+            print(f"[coach] epoch {self.ep + 1}: loss {shown:.5f}  lr enc {lr['enc']:.3e} dec {lr['dec']:.3e}"
                   + (f"  {timer.it_mean * 1e3:.1f} ms / iteration" if timer is not None else ""))
         if self.sched_type is not None and self.sched_type != "OneCycleLR":
             self.sched.step()
         if f.val_ep > 0 and (self.ep + 1) % f.val_ep == 0:
-            self.validate_model()
+            self.rank0_then_barrier(self.validate_model)
         if hasattr(self, "test_loaders") and self.ep >= f.test_ep_start and f.test_ep > 0 and (self.ep + 1) % f.test_ep == 0:
-            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
+            self.rank0_then_barrier(lambda: self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False))))
             self.model.train()
         if f.ckpt_ep > 0 and (self.ep + 1) % f.ckpt_ep == 0:
-            self.save_checkpoint(ep=self.ep + 1, it=self.it, backup_ckpt=True)
+            self.rank0_then_barrier(lambda: self.save_checkpoint(ep=self.ep + 1, it=self.it, backup_ckpt=True))
+
+    def rank0_then_barrier(self, work):
+        """Checkpoints, validation, tests and image dumps are rank 0's alone (validation is not sharded); the other ranks wait at
+        a barrier before the next iteration, whose collective would otherwise wait for it."""
+        if self.rank == 0:
+            work()
+        if self.distributed:
+            mdist.barrier(always=True)
+
+    def exchange_gradients(self, side=None):
+        """Between backward and clip + step: every gradient becomes the mean over the ranks (sum, then times fp32(1 / W)), and the
+        ``side`` values (the iteration's loss) come back as their mean in the same collective."""
+        params = [p for g in self.optim.param_groups for p in g["params"]]
+        if getattr(self, "_bucket", None) is not None:
+            return self._bucket.reduce(params, side, always=True)
+        from .optim import reduce_gradients_torch
+        return reduce_gradients_torch(params, side, always=True)
 
     def train_iteration(self, var):
         """coach.py:215-243: zero_grad, mode='train' forward, loss, backward, clip, step - and the per-iteration bookkeeping."""
@@ -261,6 +405,10 @@ class Coach:
                 term = loss[k] if w == 1 else w * loss[k]
                 loss.all = term if loss.all is None else loss.all + term
         loss.all.backward()
+        mean = None
+        if self.distributed:  # slot 0: the loss; then its terms, in the order the scalars are logged
+            terms = [k for k in loss if k != "all"]
+            mean = self._loss_mean = self.exchange_gradients(torch.stack([loss.all.detach()] + [loss[k].detach() for k in terms]))
         if clip is not None and not self.fused_optim:
             torch.nn.utils.clip_grad_norm_(self.model.feat_enc.parameters(), clip)
         self.optim.step()
@@ -270,16 +418,19 @@ class Coach:
             dt = time.time() - t0
             self.timer.it_mean = dt if self.timer.it_mean is None else 0.99 * self.timer.it_mean + 0.01 * dt
         f = self.opts.freq
-        if f.scalar > 0 and self.it % f.scalar == 0:
-            scalars = {f"loss_{k}": float(v.detach()) for k, v in loss.items() if k != "all"}
+        if f.scalar > 0 and self.it % f.scalar == 0 and self.rank == 0:
+            if mean is not None:  # the mean over the ranks: it rode in the gradient bucket, no collective of its own
+                scalars = {f"loss_{k}": float(v) for k, v in zip(terms, mean[1:])}
+            else:
+                scalars = {f"loss_{k}": float(v.detach()) for k, v in loss.items() if k != "all"}
             scalars.update({f"lrate_{k}": v for k, v in self.get_cur_lrates().items()})
             self.log_scalars(scalars, self.it, "train")
         if getattr(self, "ckpt_it", -1) > 0 and self.it % self.ckpt_it == 0:
-            self.save_checkpoint(ep=self.ep, it=self.it, backup_ckpt=False)
+            self.rank0_then_barrier(lambda: self.save_checkpoint(ep=self.ep, it=self.it, backup_ckpt=False))
         if getattr(self, "val_it", -1) > 0 and self.it % self.val_it == 0:
-            self.validate_model()
+            self.rank0_then_barrier(self.validate_model)
         if getattr(self, "test_it", -1) > 0 and self.it % self.test_it == 0 and hasattr(self, "test_loaders"):
-            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
+            self.rank0_then_barrier(lambda: self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False))))
             self.model.train()
         return loss
 
@@ -316,8 +467,10 @@ class Coach:
 
     def save_checkpoint(self, ep=0, it=0, backup_ckpt=True):
         """coach.py:290-300: {model, optim, sched, epoch, iter} -> <output_path>/models/latest.pth (+ ep{E}_it{I}.pth without the
-        optimizer and scheduler state when ``backup_ckpt``)."""
+        optimizer and scheduler state when ``backup_ckpt``); a data-parallel run adds ``world_size``."""
         ckpt = dict(model=self.model.state_dict(), optim=self.optim.state_dict())
+        if self.world > 1:  # no key: written by one process
+            ckpt["world_size"] = self.world
         if getattr(self, "sched", None) is not None:
             ckpt["sched"] = self.sched.state_dict()
         return checkpoint.save_checkpoint(self.opts.output_path, ckpt, ep=ep, it=it, backup_ckpt=backup_ckpt)

@@ -11,6 +11,10 @@
 // are streaming passes: 16-byte accesses where the four pointers of a row allow it, a scalar path for rows that are only
 // 4-byte aligned and for the last numel % 4 elements.
 //
+// Data-parallel training adds two more streaming passes over the same table (ABI 11): grad_pack_kernel copies every gradient
+// chunk into one contiguous bucket (chunk b of the table at float offset b * OPT_CHUNK, zeros behind numel, one last chunk of
+// side slots), so that ONE collective sums the gradients of all ranks, and grad_unpack_kernel writes bucket * scale back.
+//
 // Reductions are deterministic: a workgroup reduces its chunk in a fixed shuffle / LDS order into one workspace slot, a
 // second kernel adds the slots of a group in a fixed order (in double).  No floating-point atomics.
 #include "common.hpp"
@@ -183,6 +187,80 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_step_kernel(const mnerf_opt
   }
 }
 
+// ---- data-parallel exchange: gradients -> bucket -> gradients.  Workgroup b < n_blocks owns bucket[b * OPT_CHUNK, +OPT_CHUNK):
+// the bucket side of a chunk is 16-byte aligned whatever the gradient's own alignment, so the bucket is always accessed as float4.
+// Workgroup n_blocks owns the chunk of side slots (the iteration's loss rides there: no collective of its own).
+__global__ __launch_bounds__(OPT_THREADS) void grad_pack_kernel(const mnerf_optim_row* __restrict__ rows, int n_rows, int n_blocks,
+                                                                const float* __restrict__ side, int n_side,
+                                                                float* __restrict__ bucket) {
+  float4* out4 = reinterpret_cast<float4*>(bucket + (int64_t)blockIdx.x * OPT_CHUNK);
+  const float* g;
+  int n;
+  if ((int)blockIdx.x < n_blocks) {
+    const int row = opt_find_row(rows, n_rows, (int)blockIdx.x);
+    const mnerf_optim_row r = rows[row];
+    const int64_t begin = (int64_t)((int)blockIdx.x - r.block_begin) * OPT_CHUNK;
+    const int64_t left = r.numel - begin;
+    n = (int)(left < OPT_CHUNK ? left : OPT_CHUNK);
+    g = r.grad + begin;
+  } else {  // the side chunk
+    g = side;
+    n = side ? n_side : 0;
+  }
+  const bool vec = (((uintptr_t)g) & 15u) == 0;
+#pragma unroll
+  for (int i = 0; i < OPT_CHUNK / 4 / OPT_THREADS; ++i) {
+    const int j = i * OPT_THREADS + (int)threadIdx.x;
+    const int e = j << 2;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // behind numel the bucket holds zeros: nothing uninitialised is summed
+    if (vec && e + 3 < n) {
+      v = reinterpret_cast<const float4*>(g)[j];
+    } else {  // a gradient that is only 4-byte aligned, and the last numel % 4 elements
+      if (e < n) v.x = g[e];
+      if (e + 1 < n) v.y = g[e + 1];
+      if (e + 2 < n) v.z = g[e + 2];
+      if (e + 3 < n) v.w = g[e + 3];
+    }
+    out4[j] = v;
+  }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void grad_unpack_kernel(const mnerf_optim_row* __restrict__ rows, int n_rows, int n_blocks,
+                                                                  const float* __restrict__ bucket, float scale,
+                                                                  float* __restrict__ side_out, int n_side) {
+  const float4* in4 = reinterpret_cast<const float4*>(bucket + (int64_t)blockIdx.x * OPT_CHUNK);
+  float* g;
+  int n;
+  if ((int)blockIdx.x < n_blocks) {
+    const int row = opt_find_row(rows, n_rows, (int)blockIdx.x);
+    const mnerf_optim_row r = rows[row];
+    const int64_t begin = (int64_t)((int)blockIdx.x - r.block_begin) * OPT_CHUNK;
+    const int64_t left = r.numel - begin;
+    n = (int)(left < OPT_CHUNK ? left : OPT_CHUNK);
+    g = r.grad + begin;
+  } else {
+    g = side_out;
+    n = n_side;
+  }
+  const bool vec = (((uintptr_t)g) & 15u) == 0;
+#pragma unroll
+  for (int i = 0; i < OPT_CHUNK / 4 / OPT_THREADS; ++i) {
+    const int j = i * OPT_THREADS + (int)threadIdx.x;
+    const int e = j << 2;
+    if (e >= n) continue;
+    float4 v = in4[j];
+    v.x *= scale, v.y *= scale, v.z *= scale, v.w *= scale;  // one fp32 multiply per element: torch's flat.mul_(scale)
+    if (vec && e + 3 < n) {
+      reinterpret_cast<float4*>(g)[j] = v;
+    } else {
+      g[e] = v.x;
+      if (e + 1 < n) g[e + 1] = v.y;
+      if (e + 2 < n) g[e + 2] = v.z;
+      if (e + 3 < n) g[e + 3] = v.w;
+    }
+  }
+}
+
 // ---- L2 loss: ONE workgroup (the loss of a training iteration has rand_rays_train x 3 terms), fixed-order sum
 constexpr int L2_THREADS = 1024;
 
@@ -258,6 +336,13 @@ int opt_table(const char* what, const mnerf_optim_row* rows, int32_t n_rows, int
   return MNERF_OK;
 }
 
+int opt_bucket(const char* what, const float* bucket, int32_t n_side) {
+  MNERF_REQUIRE(bucket != nullptr, MNERF_E_NULL, "%s: bucket is NULL", what);
+  MNERF_REQUIRE((((uintptr_t)bucket) & 15u) == 0, MNERF_E_ALIGN, "%s: bucket must be 16-byte aligned", what);
+  MNERF_REQUIRE(n_side >= 0 && n_side <= OPT_CHUNK, MNERF_E_RANGE, "%s: n_side %d outside [0, %d]", what, n_side, OPT_CHUNK);
+  return MNERF_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t mnerf_optim_row_blocks(int64_t numel) { return numel <= 0 ? -1 : (numel + OPT_CHUNK - 1) / OPT_CHUNK; }
@@ -293,4 +378,27 @@ extern "C" int mnerf_l2_loss(const float* pred, const float* target, int64_t n, 
   MNERF_REQUIRE(n >= 1, MNERF_E_RANGE, "mnerf_l2_loss: n = %lld", (long long)n);
   l2_loss_kernel<<<dim3(1), dim3(L2_THREADS), 0, (hipStream_t)stream>>>(pred, target, n, weight, loss, grad);
   return mnerf_check_launch("mnerf_l2_loss");
+}
+
+extern "C" int64_t mnerf_grad_bucket_floats(int64_t n_blocks) {
+  return n_blocks < 1 || n_blocks >= INT32_MAX ? -1 : (n_blocks + 1) * OPT_CHUNK;
+}
+
+extern "C" int mnerf_grad_pack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const float* side, int32_t n_side,
+                               float* bucket, void* stream) {
+  if (int rc = opt_table("mnerf_grad_pack", rows, n_rows, n_blocks)) return rc;
+  if (int rc = opt_bucket("mnerf_grad_pack", bucket, n_side)) return rc;
+  MNERF_REQUIRE(side != nullptr || n_side == 0, MNERF_E_NULL, "mnerf_grad_pack: side is NULL with n_side %d", n_side);
+  grad_pack_kernel<<<dim3(n_blocks + 1), dim3(OPT_THREADS), 0, (hipStream_t)stream>>>(rows, n_rows, n_blocks, side, n_side, bucket);
+  return mnerf_check_launch("mnerf_grad_pack");
+}
+
+extern "C" int mnerf_grad_unpack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const float* bucket, float scale,
+                                 float* side_out, int32_t n_side, void* stream) {
+  if (int rc = opt_table("mnerf_grad_unpack", rows, n_rows, n_blocks)) return rc;
+  if (int rc = opt_bucket("mnerf_grad_unpack", bucket, n_side)) return rc;
+  MNERF_REQUIRE(side_out != nullptr || n_side == 0, MNERF_E_NULL, "mnerf_grad_unpack: side_out is NULL with n_side %d", n_side);
+  const int grid = n_blocks + (n_side > 0 ? 1 : 0);
+  grad_unpack_kernel<<<dim3(grid), dim3(OPT_THREADS), 0, (hipStream_t)stream>>>(rows, n_rows, n_blocks, bucket, scale, side_out, n_side);
+  return mnerf_check_launch("mnerf_grad_unpack");
 }

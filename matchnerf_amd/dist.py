@@ -195,6 +195,61 @@ def render_views_sharded(model, batch, poses, mode="test", encoder="shared"):
     return edict(rgb=full[..., :3].contiguous(), depth=full[..., 3:4].contiguous(), opacity=full[..., 4:5].contiguous())
 
 
+def group_active(always=False):
+    """a process group exists and has more than one rank (``always``: one rank counts too)"""
+    return dist.is_initialized() and (dist.get_world_size() > 1 or always)
+
+
+def rank_world():
+    return (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+
+
+def reseed(seed, rank):
+    """Data-parallel training: rank r reseeds torch's CPU and device generators with ``seed + r`` once the options are processed,
+    so the ranks draw different rays and stratified offsets (the order of the scenes must NOT come from these generators)."""
+    torch.manual_seed(int(seed) + int(rank))
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(int(seed) + int(rank))
+
+
+def broadcast_tensors(tensors, src=0):
+    """Rank ``src``'s values of ``tensors`` (one dtype) into every rank's, in ONE broadcast of the flattened list; device tensors
+    are staged through the host over gloo."""
+    from torch._utils import _flatten_dense_tensors, _unflatten_dense_tensors
+    if not tensors or not dist.is_initialized():
+        return
+    flat = _flatten_dense_tensors([t.detach() for t in tensors])
+    if flat.is_cuda and dist.get_backend() == "gloo":
+        host = flat.cpu()
+        dist.broadcast(host, src=src)
+        flat = host.to(flat.device)
+    else:
+        dist.broadcast(flat, src=src)
+    if dist.get_rank() != src:
+        for t, v in zip(tensors, _unflatten_dense_tensors(flat, tensors)):
+            t.detach().copy_(v)
+
+
+def to_host(obj):
+    """a nested dict / list / tuple with its tensors on the CPU (what travels through broadcast_object must not name a device)"""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu()
+    if isinstance(obj, dict):
+        return {k: to_host(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(to_host(v) for v in obj)
+    return obj
+
+
+def broadcast_object(obj, src=0, device=None):
+    """``obj`` of rank ``src`` (anything torch can pickle) on every rank"""
+    if not dist.is_initialized():
+        return obj
+    box = [obj]
+    dist.broadcast_object_list(box, src=src, device=None if dist.get_backend() == "gloo" else device)
+    return box[0]
+
+
 def barrier(always=False):
     if dist.is_initialized() and (dist.get_world_size() > 1 or always):
         dist.barrier()

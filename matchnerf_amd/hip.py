@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-MNERF_ABI_VERSION = 10
+MNERF_ABI_VERSION = 11
 MNERF_POSE_FLOATS = 24  # floats of one row of mnerf_rays.pose_table
 MNERF_OK, MNERF_E_NULL, MNERF_E_RANGE, MNERF_E_UNSUPPORTED, MNERF_E_ALIGN = 0, -1, -2, -3, -4  # include/mnerf.h
 MNERF_MAX_VIEWS = 16
@@ -32,7 +32,8 @@ EXPORTS = ("mnerf_abi_version", "mnerf_last_error", "mnerf_struct_size", "mnerf_
            "mnerf_window_attention_presplit", "mnerf_window_attention_workspace_bytes", "mnerf_window_attention_backward", "mnerf_window_attention_backward_workspace_bytes", "mnerf_qkv_projection", "mnerf_qkv_wstream_floats", "mnerf_qkv_window_images", "mnerf_window_attention_images", "mnerf_instance_norm", "mnerf_instance_norm_backward", "mnerf_upsample_bilinear2x", "mnerf_upsample_bilinear2x_backward", "mnerf_conv2d", "mnerf_conv_wstream_floats", "mnerf_conv_stem", "mnerf_conv_stem_wstream_floats", "mnerf_absmax", "mnerf_conv2d_backward_data", "mnerf_conv2d_backward_weight", "mnerf_conv2d_backward_weight_workspace_bytes", "mnerf_conv2d_backward_weight_f16x3", "mnerf_conv2d_forward_f32", "mnerf_conv_stem_backward_weight", "mnerf_conv_stem_backward_weight_workspace_bytes", "mnerf_encoder_block", "mnerf_encoder_block_wstream_floats",
            "mnerf_encoder_layer_backward", "mnerf_encoder_layer_backward_workspace_bytes", "mnerf_qkv_backward", "mnerf_debug_gemm",
            "mnerf_window_attention_presplit_stats", "mnerf_window_attention_backward_stats", "mnerf_encoder_block_save", "mnerf_encoder_layer_backward_saved",
-           "mnerf_optim_row_blocks", "mnerf_grad_sumsq", "mnerf_adamw_step", "mnerf_l2_loss")
+           "mnerf_optim_row_blocks", "mnerf_grad_sumsq", "mnerf_adamw_step", "mnerf_l2_loss",
+           "mnerf_grad_bucket_floats", "mnerf_grad_pack", "mnerf_grad_unpack")
 
 
 class MnerfError(RuntimeError):
@@ -255,6 +256,12 @@ def load():
     lib.mnerf_adamw_step.argtypes = [vp, i32, i32, C.POINTER(OptimGroup), i32, fp, vp]
     lib.mnerf_l2_loss.restype = C.c_int
     lib.mnerf_l2_loss.argtypes = [fp, fp, i64, C.c_float, fp, fp, vp]
+    lib.mnerf_grad_bucket_floats.restype = i64
+    lib.mnerf_grad_bucket_floats.argtypes = [i64]
+    lib.mnerf_grad_pack.restype = C.c_int
+    lib.mnerf_grad_pack.argtypes = [vp, i32, i32, fp, i32, fp, vp]
+    lib.mnerf_grad_unpack.restype = C.c_int
+    lib.mnerf_grad_unpack.argtypes = [vp, i32, i32, fp, C.c_float, fp, i32, vp]
     ver = lib.mnerf_abi_version()
     if ver != MNERF_ABI_VERSION:
         raise MnerfError(f"libmnerf_hip.so ABI {ver} != binding ABI {MNERF_ABI_VERSION}")
@@ -1213,3 +1220,44 @@ def l2_loss(pred, target, weight=1.0, want_grad=True, stream=None):
     with _on(pred.device, stream) as st:
         check(lib.mnerf_l2_loss(_ptr(pred), _ptr(target), pred.numel(), float(weight), _ptr(loss), _ptr(grad), st), "mnerf_l2_loss")
     return loss, grad
+
+
+# ----------------------------------------------------------------------- the gradient exchange of data-parallel training
+
+
+def grad_bucket_floats(n_blocks):
+    """floats of the bucket of a row table of ``n_blocks`` chunks: the chunks plus one chunk of side slots (host only)"""
+    return (int(n_blocks) + 1) * OPTIM_CHUNK
+
+
+def grad_pack(rows, n_rows, n_blocks, bucket, side=None, stream=None):
+    """Every gradient of the table into its slot of ``bucket`` (float32 CUDA, >= grad_bucket_floats(n_blocks)), zeros behind each
+    tensor; ``side`` (float32 CUDA, at most OPTIM_CHUNK values, or None) into the side chunk.  One launch (mnerf_grad_pack)."""
+    lib = load()
+    _f32c(bucket, "bucket")
+    n_side = 0
+    if side is not None:
+        _f32c(side, "side")
+        n_side = side.numel()
+    if rows.numel() < n_rows * C.sizeof(OptimRow) or bucket.numel() < grad_bucket_floats(n_blocks) or n_side > OPTIM_CHUNK:
+        raise MnerfError("grad_pack: rows / bucket too small for the table, or more than OPTIM_CHUNK side values")
+    with _on(rows.device, stream) as st:
+        check(lib.mnerf_grad_pack(rows.data_ptr(), int(n_rows), int(n_blocks), _ptr(side), n_side, _ptr(bucket), st), "mnerf_grad_pack")
+    return bucket
+
+
+def grad_unpack(rows, n_rows, n_blocks, bucket, scale, side_out=None, stream=None):
+    """grad = bucket * scale for every row of the table, ``side_out`` (float32 CUDA or None) = the side slots * scale.  One launch
+    (mnerf_grad_unpack); ``scale`` is rounded to fp32 on the way in."""
+    lib = load()
+    _f32c(bucket, "bucket")
+    n_side = 0
+    if side_out is not None:
+        _f32c(side_out, "side_out")
+        n_side = side_out.numel()
+    if rows.numel() < n_rows * C.sizeof(OptimRow) or bucket.numel() < grad_bucket_floats(n_blocks) or n_side > OPTIM_CHUNK:
+        raise MnerfError("grad_unpack: rows / bucket too small for the table, or more than OPTIM_CHUNK side values")
+    with _on(rows.device, stream) as st:
+        check(lib.mnerf_grad_unpack(rows.data_ptr(), int(n_rows), int(n_blocks), _ptr(bucket), float(scale), _ptr(side_out), n_side, st),
+              "mnerf_grad_unpack")
+    return side_out
