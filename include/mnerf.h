@@ -40,6 +40,8 @@
  *       and mnerf_optim_group - struct indices 8 and 9 -, mnerf_optim_row_blocks, mnerf_grad_sumsq, mnerf_adamw_step, mnerf_l2_loss.
  *   v11 no layout change: the gradient exchange of data-parallel training over the same row table - mnerf_grad_bucket_floats,
  *       mnerf_grad_pack, mnerf_grad_unpack.
+ *   v12 no layout change: evaluation on the device (matchnerf_amd/csrc/metrics.hip) - mnerf_image_metrics,
+ *       mnerf_image_metrics_workspace_bytes.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -50,7 +52,7 @@
 extern "C" {
 #endif
 
-#define MNERF_ABI_VERSION 11
+#define MNERF_ABI_VERSION 12
 #define MNERF_MAX_VIEWS 16
 #define MNERF_FEAT_CH 128 /* channels of one pair-specific GMFlow feature map */
 /* floats per sample of a `cond` buffer: sum(cos_n_group) + 4 n_views + 1, rounded up to a multiple of 8.
@@ -642,6 +644,27 @@ int mnerf_grad_pack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_block
 /* One launch: grad = bucket * scale for every row (one fp32 multiply per element), side_out[0, n_side) = side slots * scale. */
 int mnerf_grad_unpack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blocks, const float* bucket, float scale,
                       float* side_out, int32_t n_side, void* stream);
+
+/* ABI v12 - evaluation on the device (misc/metrics.py:19-45 and the per-image host loop of coach.py:316-453 of the reference):
+ * PSNR and SSIM of n_images rendered frames against their ground truth, as `psnr` and `EvalTools.set_inputs` + `ssim` of
+ * matchnerf_amd/metrics.py compute them with data_range = 2.
+ *   pred          [n, H*W, 3] channel-last, contiguous: what the forward pass returns as rgb
+ *   gt            [n, 3, H, W] channel-first, image i at gt + i * gt_image_stride (floats; >= 3 H W): the target view of a
+ *                 [B, V, 3, H, W] batch passes without a copy
+ *   invalid_mask  [n, H, W] bytes, non-zero = the pixel is dropped, or NULL
+ * With a mask the mean squared error runs over the three channels of the kept pixels and SSIM over the whole image with the
+ * masked pixels set to 0 in both images (H, W >= 7); without one both use the crop [H/10, H - H/10) x [W/10, W - W/10)
+ * (H, W >= 10).  SSIM: 7x7 windows that lie inside the processed image, sample covariance (49/48), C1 = 0.02^2, C2 = 0.06^2, mean
+ * over windows and channels.  Inputs are fp32; products, sums and the SSIM expression are fp64.
+ *   out           [n, 4] doubles: PSNR in dB, SSIM, MSE, kept pixels.  No kept pixel: PSNR and MSE are NaN; MSE 0: PSNR +inf.
+ *   workspace     8-byte aligned, at least the bytes the helper below returns
+ * Deterministic: every workgroup writes its own workspace slots, one workgroup per image adds them in a fixed order; no
+ * floating-point atomics.  The four numbers of an image depend neither on the other images nor on n_images.  Two launches.
+ * Sizes below the limits: MNERF_E_RANGE. */
+/* host only; -1 for n_images < 1 or H, W < 7 */
+int64_t mnerf_image_metrics_workspace_bytes(int32_t n_images, int32_t height, int32_t width);
+int mnerf_image_metrics(const float* pred, const float* gt, int64_t gt_image_stride, const uint8_t* invalid_mask,
+                        int32_t n_images, int32_t height, int32_t width, void* workspace, double* out, void* stream);
 
 #ifdef __cplusplus
 }

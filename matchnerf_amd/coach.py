@@ -12,7 +12,8 @@ above on its own ``batch_size`` scenes; between backward and clip + step the gra
 clips and steps on identical values, so the replicas stay bit-identical with no later exchange.  The effective batch is W x
 ``batch_size`` and the learning rates are NOT rescaled.  Rank r draws its rays and offsets from ``seed + r`` (dist.reseed), the order
 of the scenes comes from (seed, epoch) alone, rank 0's weights (and, on a resume, optimizer and scheduler state) are broadcast after
-``restore_checkpoint``, and only rank 0 writes checkpoints, scalars, images and prints.  ``gpu_ids`` longer than one WITHOUT a process
+``restore_checkpoint``, and only rank 0 writes checkpoints, scalars and prints.  Validation and tests are sharded: batch bi of a
+loader is rendered and scored by rank bi % W (on the device: csrc/metrics.hip), rank 0 assembles the one-process report.  ``gpu_ids`` longer than one WITHOUT a process
 group of that size still raises in ``setup_optimizer``: the in-process DataParallel form is not built."""
 import json
 import math
@@ -364,16 +365,16 @@ class Coach:
         if self.sched_type is not None and self.sched_type != "OneCycleLR":
             self.sched.step()
         if f.val_ep > 0 and (self.ep + 1) % f.val_ep == 0:
-            self.rank0_then_barrier(self.validate_model)
+            self.validate_model()  # every rank: the evaluation is sharded
         if hasattr(self, "test_loaders") and self.ep >= f.test_ep_start and f.test_ep > 0 and (self.ep + 1) % f.test_ep == 0:
-            self.rank0_then_barrier(lambda: self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False))))
+            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
             self.model.train()
         if f.ckpt_ep > 0 and (self.ep + 1) % f.ckpt_ep == 0:
             self.rank0_then_barrier(lambda: self.save_checkpoint(ep=self.ep + 1, it=self.it, backup_ckpt=True))
 
     def rank0_then_barrier(self, work):
-        """Checkpoints, validation, tests and image dumps are rank 0's alone (validation is not sharded); the other ranks wait at
-        a barrier before the next iteration, whose collective would otherwise wait for it."""
+        """Checkpoints and the sanity check are rank 0's alone (validation and tests are sharded over the ranks: ``_evaluate``); the
+        other ranks wait at a barrier before the next iteration, whose collective would otherwise wait for it."""
         if self.rank == 0:
             work()
         if self.distributed:
@@ -428,9 +429,9 @@ class Coach:
         if getattr(self, "ckpt_it", -1) > 0 and self.it % self.ckpt_it == 0:
             self.rank0_then_barrier(lambda: self.save_checkpoint(ep=self.ep, it=self.it, backup_ckpt=False))
         if getattr(self, "val_it", -1) > 0 and self.it % self.val_it == 0:
-            self.rank0_then_barrier(self.validate_model)
+            self.validate_model()  # every rank: the evaluation is sharded
         if getattr(self, "test_it", -1) > 0 and self.it % self.test_it == 0 and hasattr(self, "test_loaders"):
-            self.rank0_then_barrier(lambda: self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False))))
+            self.test_model(save_images=bool(getattr(self.opts, "save_test_image", False)))
             self.model.train()
         return loss
 
@@ -475,10 +476,87 @@ class Coach:
             ckpt["sched"] = self.sched.state_dict()
         return checkpoint.save_checkpoint(self.opts.output_path, ckpt, ep=ep, it=it, backup_ckpt=backup_ckpt)
 
+    # ------------------------------------------------------------------ evaluation (coach.py:316-453)
+
+    def _eval_world(self):
+        """(rank, world) of a sharded evaluation: the process group's when it has more than one rank, else (0, 1)"""
+        return (self.rank, self.world) if mdist.group_active() else (0, 1)
+
+    def _own_batches(self, loader, rank, world):
+        """-> (global batch index, batch) of the batches of ``loader`` that belong to ``rank`` (metrics.batch_owner: bi % world).  An
+        on-disk DataLoader in its sequential order is rebuilt over a batch sampler of the rank's indices, so that no rank reads
+        another rank's files; every other loader is iterated and the other ranks' batches are skipped."""
+        if world == 1:
+            yield from enumerate(loader)
+            return
+        data = torch.utils.data
+        if isinstance(loader, data.DataLoader) and isinstance(loader.sampler, data.SequentialSampler) and loader.batch_size:
+            n, bs = len(loader.dataset), loader.batch_size
+            n_batches = (n + bs - 1) // bs if not loader.drop_last else n // bs
+            mine = metrics.rank_batches(n_batches, rank, world)
+            if not mine:
+                return
+            own = data.DataLoader(loader.dataset, batch_sampler=[list(range(bi * bs, min((bi + 1) * bs, n))) for bi in mine],
+                                  num_workers=loader.num_workers, pin_memory=loader.pin_memory)
+            yield from zip(mine, own)
+            return
+        for bi, batch in enumerate(loader):
+            if metrics.batch_owner(bi, world) == rank:
+                yield bi, batch
+
+    def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True):
+        """Render this rank's batches of ``loader`` in ``mode`` and score them -> rows float64 [n, 5] of ALL ranks' images in the
+        order one process evaluates them: (batch index, image within the batch, PSNR, SSIM, LPIPS or NaN).
+        On CUDA with ``metrics.device_metrics_enabled()`` PSNR / SSIM are rows of ``metrics.DeviceEval`` (csrc/metrics.hip) and reach
+        the host in ONE copy after the last batch; a frame goes to the host only for ``on_frame(batch, bi, i, pred, gt)`` (images to
+        write) or an LPIPS callable.  Otherwise every frame is scored on the host (``metrics.psnr`` / ``EvalTools``).
+        ``mask_of(gt_depth)`` -> the depth the invalid mask (depth == 0) comes from, or None for the 80 % centre crop.
+        With a process group of more than one rank (``shard``), the ranks' rows travel in one ragged ``dist.gather_blocks``."""
+        rank, world = self._eval_world() if shard else (0, 1)
+        on_device = str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled()
+        dev = metrics.DeviceEval() if on_device else None
+        host_rows, lpips_of = [], {}
+        for bi, batch in self._own_batches(loader, rank, world):
+            if first_only and bi > 0:
+                break
+            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+            gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
+            var = self.model(var, mode=mode)
+            b, _, _, h, w = var.images.shape
+            depth = mask_of(gt_depth)
+            frames = None
+            if dev is None or on_frame is not None or lpips_fn is not None:
+                frames = (var.rgb.reshape(b, h, w, 3).cpu().numpy(), var.images[:, -1].permute(0, 2, 3, 1).cpu().numpy())
+            if dev is not None:
+                dev.add(bi, var.rgb.reshape(b, h * w, 3).contiguous(), var.images[:, -1],
+                        None if depth is None else (depth.reshape(b, h, w) == 0))
+            for i in range(b if frames is not None else 0):
+                pred, gt = frames[0][i], frames[1][i]
+                mask = None if depth is None else (depth[i].cpu().numpy() == 0)
+                if dev is None or lpips_fn is not None:
+                    tools = metrics.EvalTools(lpips_fn=lpips_fn)
+                    tools.set_inputs(pred, gt, mask)
+                if dev is None:
+                    host_rows.append([bi, i, metrics.psnr(pred, gt, mask), tools.get_metrics(["SSIM"])["SSIM"], np.nan])
+                if lpips_fn is not None:
+                    lpips_of[(bi, i)] = tools.get_metrics(["LPIPS"])["LPIPS"]
+                if on_frame is not None:
+                    on_frame(batch, bi, i, pred, gt)
+        if dev is not None:
+            keys, got = dev.finish()  # the one copy of this loader
+            rows = np.concatenate([keys.astype(np.float64), got[:, :2], np.full((len(keys), 1), np.nan)], 1)
+        else:
+            rows = np.asarray(host_rows, np.float64).reshape(-1, 5)
+        for j in range(len(rows)):
+            rows[j, 4] = lpips_of.get((int(rows[j, 0]), int(rows[j, 1])), np.nan)
+        return metrics.gather_rows(rows, device=self.opts.device) if world > 1 else metrics.merge_rows(rows)
+
     @torch.no_grad()
     def validate_model(self, first_only=False):
         """coach.py:316-366: every batch of ``val_loader`` rendered in mode='val'; mean PSNR / SSIM to the scalars, prediction | ground
-        truth strips to <output_path>/validation/."""
+        truth strips to <output_path>/validation/.  In a data-parallel run every rank calls this: batch bi is rendered, scored and its
+        strip written by rank bi % W, rank 0 logs and prints the one-process report (``first_only``, the sanity check, is rank 0's
+        alone and runs no collective)."""
         assert hasattr(self, "val_loader"), "load_dataset(['val']) first"
         from PIL import Image
         self.model.eval()
@@ -486,34 +564,26 @@ class Coach:
         os.makedirs(out_dir, exist_ok=True)
         name = self.val_loader.get_name()
         it = getattr(self, "it", 0)
-        psnrs, ssims = [], []
-        for bi, batch in enumerate(self.val_loader):
-            if first_only and bi > 0:
-                break
-            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
-            gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
-            var = self.model(var, mode="val")
-            b, _, _, h, w = var.images.shape
-            pred = var.rgb.reshape(b, h, w, 3).cpu().numpy()
-            gt = var.images[:, -1].permute(0, 2, 3, 1).cpu().numpy()
-            for i in range(b):
-                mask = (gt_depth[i].cpu().numpy() == 0) if (gt_depth is not None and "dtu" in name) else None
-                tools = metrics.EvalTools(lpips_fn=None)
-                tools.set_inputs(pred[i], gt[i], mask)
-                psnrs.append(metrics.psnr(pred[i], gt[i], mask))
-                ssims.append(tools.get_metrics(["SSIM"])["SSIM"])
-                scene = batch["scene"][i] if "scene" in batch else f"{name}{bi}"
-                vis = (np.concatenate([pred[i], gt[i]], 1).clip(0, 1) * 255).astype("uint8")
-                Image.fromarray(vis).save(os.path.join(out_dir, f"{scene}_{bi:03d}_{i}_it{it}.jpg"))
+
+        def strip(batch, bi, i, pred, gt):
+            scene = batch["scene"][i] if "scene" in batch else f"{name}{bi}"
+            vis = (np.concatenate([pred, gt], 1).clip(0, 1) * 255).astype("uint8")
+            Image.fromarray(vis).save(os.path.join(out_dir, f"{scene}_{bi:03d}_{i}_it{it}.jpg"))
+
+        rows = self._evaluate(self.val_loader, "val", lambda d: d if (d is not None and "dtu" in name) else None, on_frame=strip,
+                              first_only=first_only, shard=not first_only)
+        psnrs, ssims = [float(v) for v in rows[:, 2]], [float(v) for v in rows[:, 3]]
         self.log_scalars({"PSNR": np.mean(psnrs), "SSIM": np.mean(ssims)}, it, "val")
-        print(f"[coach] validation at iteration {it}: PSNR {np.mean(psnrs):.2f} over {len(psnrs)} images")
+        self.say(f"[coach] validation at iteration {it}: PSNR {np.mean(psnrs):.2f} over {len(psnrs)} images")
         self.model.train()
         return dict(PSNR=psnrs, SSIM=ssims)
 
     @torch.no_grad()
     def test_model(self, save_images=False, **kwargs):
         """coach.py:368-453 -> {dataset: {image_id: psnr}}; the results file also lists SSIM and, when the two weight files of the
-        `lpips` package are on disk (metrics.load_lpips: $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN or torch hub's cache), LPIPS."""
+        `lpips` package are on disk (metrics.load_lpips: $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN or torch hub's cache), LPIPS.
+        With a process group of more than one rank every rank calls this and renders batch bi when bi % W is its rank; rank 0 alone
+        writes the results files and prints, every rank returns the one-process report and writes the images of its own share."""
         self.model.eval()
         try:
             lpips_fn = metrics.load_lpips(device=self.opts.device)
@@ -524,37 +594,26 @@ class Coach:
         report = {}
         for loader in self.test_loaders:
             name = loader.get_name()
-            report[name] = {}
-            ssims, lpipss = [], []
             self.model.nerf_setbg_opaque = (name == "blender")  # coach.py:382-383
-            for bi, batch in enumerate(loader):
-                var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
-                gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
-                var = self.model(var, mode="test")
-                b, _, _, h, w = var.images.shape
-                pred = var.rgb.reshape(b, h, w, 3).cpu().numpy()
-                gt = var.images[:, -1].permute(0, 2, 3, 1).cpu().numpy()
-                for i in range(b):
-                    mask = None if gt_depth is None else (gt_depth[i].cpu().numpy() == 0)
-                    report[name][f"{name}_{bi:03d}_{i}"] = metrics.psnr(pred[i], gt[i], mask)
-                    tools = metrics.EvalTools(lpips_fn=lpips_fn)
-                    tools.set_inputs(pred[i], gt[i], mask)
-                    got = tools.get_metrics(["SSIM"] + (["LPIPS"] if lpips_fn else []))
-                    ssims.append(got["SSIM"])
-                    lpipss.append(got.get("LPIPS"))
-                    if save_images:
-                        from PIL import Image
-                        vis = np.concatenate([pred[i], gt[i]], 1)
-                        Image.fromarray((vis.clip(0, 1) * 255).astype("uint8")).save(
-                            os.path.join(out_root, f"{name}_{bi:03d}_{i}.png"))
+
+            def save(batch, bi, i, pred, gt, name=name):
+                from PIL import Image
+                vis = np.concatenate([pred, gt], 1)
+                Image.fromarray((vis.clip(0, 1) * 255).astype("uint8")).save(os.path.join(out_root, f"{name}_{bi:03d}_{i}.png"))
+
+            rows = self._evaluate(loader, "test", lambda d: d, on_frame=save if save_images else None, lpips_fn=lpips_fn)
             self.model.nerf_setbg_opaque = False
+            report[name] = {f"{name}_{int(r[0]):03d}_{int(r[1])}": float(r[2]) for r in rows}
+            ssims = [float(r[3]) for r in rows]
+            lpipss = [float(r[4]) if lpips_fn else None for r in rows]
             vals = list(report[name].values())
-            with open(os.path.join(out_root, f"0results_{name}.txt"), "w") as f:
-                for (k, v), sv, lv in zip(report[name].items(), ssims, lpipss):
-                    f.write(f"{k}: PSNR {v:.4f} SSIM {sv:.4f}" + (f" LPIPS {lv:.4f}" if lv is not None else "") + "\n")
-                f.write(f"mean PSNR {np.mean(vals):.4f} SSIM {np.mean(ssims):.4f}" +
-                        (f" LPIPS {np.mean(lpipss):.4f}" if lpips_fn else "") + "\n")
-            print(f"[coach] {name}: mean PSNR {np.mean(vals):.2f} over {len(vals)} images")
+            if self.rank == 0:
+                with open(os.path.join(out_root, f"0results_{name}.txt"), "w") as f:
+                    for (k, v), sv, lv in zip(report[name].items(), ssims, lpipss):
+                        f.write(f"{k}: PSNR {v:.4f} SSIM {sv:.4f}" + (f" LPIPS {lv:.4f}" if lv is not None else "") + "\n")
+                    f.write(f"mean PSNR {np.mean(vals):.4f} SSIM {np.mean(ssims):.4f}" +
+                            (f" LPIPS {np.mean(lpipss):.4f}" if lpips_fn else "") + "\n")
+            self.say(f"[coach] {name}: mean PSNR {np.mean(vals):.2f} over {len(vals)} images")
         return report
 
     @torch.no_grad()

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-MNERF_ABI_VERSION = 11
+MNERF_ABI_VERSION = 12
 MNERF_POSE_FLOATS = 24  # floats of one row of mnerf_rays.pose_table
 MNERF_OK, MNERF_E_NULL, MNERF_E_RANGE, MNERF_E_UNSUPPORTED, MNERF_E_ALIGN = 0, -1, -2, -3, -4  # include/mnerf.h
 MNERF_MAX_VIEWS = 16
@@ -33,7 +33,8 @@ EXPORTS = ("mnerf_abi_version", "mnerf_last_error", "mnerf_struct_size", "mnerf_
            "mnerf_encoder_layer_backward", "mnerf_encoder_layer_backward_workspace_bytes", "mnerf_qkv_backward", "mnerf_debug_gemm",
            "mnerf_window_attention_presplit_stats", "mnerf_window_attention_backward_stats", "mnerf_encoder_block_save", "mnerf_encoder_layer_backward_saved",
            "mnerf_optim_row_blocks", "mnerf_grad_sumsq", "mnerf_adamw_step", "mnerf_l2_loss",
-           "mnerf_grad_bucket_floats", "mnerf_grad_pack", "mnerf_grad_unpack")
+           "mnerf_grad_bucket_floats", "mnerf_grad_pack", "mnerf_grad_unpack",
+           "mnerf_image_metrics_workspace_bytes", "mnerf_image_metrics")
 
 
 class MnerfError(RuntimeError):
@@ -262,6 +263,10 @@ def load():
     lib.mnerf_grad_pack.argtypes = [vp, i32, i32, fp, i32, fp, vp]
     lib.mnerf_grad_unpack.restype = C.c_int
     lib.mnerf_grad_unpack.argtypes = [vp, i32, i32, fp, C.c_float, fp, i32, vp]
+    lib.mnerf_image_metrics_workspace_bytes.restype = i64
+    lib.mnerf_image_metrics_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.mnerf_image_metrics.restype = C.c_int
+    lib.mnerf_image_metrics.argtypes = [fp, fp, i64, vp, i32, i32, i32, vp, vp, vp]
     ver = lib.mnerf_abi_version()
     if ver != MNERF_ABI_VERSION:
         raise MnerfError(f"libmnerf_hip.so ABI {ver} != binding ABI {MNERF_ABI_VERSION}")
@@ -1261,3 +1266,60 @@ def grad_unpack(rows, n_rows, n_blocks, bucket, scale, side_out=None, stream=Non
         check(lib.mnerf_grad_unpack(rows.data_ptr(), int(n_rows), int(n_blocks), _ptr(bucket), float(scale), _ptr(side_out), n_side, st),
               "mnerf_grad_unpack")
     return side_out
+
+
+# ----------------------------------------------------------------------- evaluation on the device (csrc/metrics.hip)
+
+
+def image_metrics(pred, gt, invalid_mask=None, stream=None):
+    """PSNR / SSIM of a batch of frames as ``metrics.psnr`` and ``metrics.EvalTools`` + ``metrics.ssim`` define them, on the device
+    (mnerf_image_metrics; two launches, deterministic, fp64 arithmetic).  ``pred`` [B, H*W, 3] contiguous float32 CUDA (the rgb of
+    a forward pass), ``gt`` [B, 3, H, W] float32 CUDA with contiguous images and any batch stride (``images[:, -1]`` passes without a
+    copy), ``invalid_mask`` [B, H, W] bool / uint8 (non-zero = the pixel is dropped) or None for the 80 % centre crop.
+    -> float64 CUDA tensor [B, 4]: PSNR in dB, SSIM, MSE, kept pixels.  Everything is checked here, before any launch."""
+    import torch
+    lib = load()
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MnerfError(f"image_metrics: {name} must be a CUDA tensor, got {getattr(t, 'device', type(t))} (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise MnerfError(f"image_metrics: {name} must be float32, got {t.dtype}")
+    if gt.dim() != 4 or gt.shape[1] != 3:
+        raise MnerfError(f"image_metrics: gt must be [B, 3, H, W], got {tuple(gt.shape)}")
+    b, _, h, w = gt.shape
+    if tuple(pred.shape) != (b, h * w, 3) or pred.device != gt.device:
+        raise MnerfError(f"image_metrics: pred {tuple(pred.shape)} on {pred.device} does not match gt {tuple(gt.shape)} on {gt.device}: "
+                         f"expected [{b}, {h * w}, 3]")
+    if not pred.is_contiguous():
+        raise MnerfError("image_metrics: pred must be contiguous")
+    if b < 1 or b > 65535:
+        raise MnerfError(f"image_metrics: {b} images, the kernel takes 1..65535")
+    if gt.stride()[1:] != (h * w, w, 1):
+        raise MnerfError(f"image_metrics: every image of gt must be contiguous, got strides {gt.stride()}")
+    gt_stride = gt.stride(0) if b > 1 else 3 * h * w
+    if gt_stride < 3 * h * w:
+        raise MnerfError(f"image_metrics: gt's images overlap (batch stride {gt_stride})")
+    least = 10 if invalid_mask is None else 7
+    if h < least or w < least:
+        raise MnerfError(f"image_metrics: {h} x {w} images, the smallest is {least} x {least} "
+                         + ("without a mask (the 80 % crop must hold a 7 x 7 window)" if invalid_mask is None else "with a mask (one 7 x 7 window)"))
+    if invalid_mask is not None:
+        if not torch.is_tensor(invalid_mask) or invalid_mask.device != pred.device or invalid_mask.dtype not in (torch.bool, torch.uint8):
+            raise MnerfError("image_metrics: invalid_mask must be a bool or uint8 tensor on pred's device")
+        if tuple(invalid_mask.shape) != (b, h, w):
+            raise MnerfError(f"image_metrics: invalid_mask {tuple(invalid_mask.shape)}, expected [{b}, {h}, {w}]")
+        invalid_mask = invalid_mask.contiguous()
+        if invalid_mask.dtype == torch.bool:
+            invalid_mask = invalid_mask.view(torch.uint8)  # one byte per element, 0 / 1
+    n_bytes = lib.mnerf_image_metrics_workspace_bytes(b, h, w)
+    if n_bytes <= 0:
+        raise MnerfError(f"image_metrics: no workspace size for {b} images of {h} x {w}")
+    with _on(pred.device, stream) as st:
+        workspace = torch.empty(n_bytes // 8, dtype=torch.float64, device=pred.device)
+        out = torch.empty((b, 4), dtype=torch.float64, device=pred.device)
+        check(lib.mnerf_image_metrics(_ptr(pred), _ptr(gt), int(gt_stride), _ptr(invalid_mask), b, h, w, _ptr(workspace), _ptr(out), st),
+              "mnerf_image_metrics")
+        if stream is not None:  # the caching allocator must not hand the buffers on before this stream is through with them
+            workspace.record_stream(stream)
+            out.record_stream(stream)
+    return out

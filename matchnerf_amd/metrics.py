@@ -98,6 +98,76 @@ class EvalTools:
         return out
 
 
+# ----------------------------------------------------------------------------- evaluation on the device (csrc/metrics.hip)
+
+
+def device_metrics_enabled():
+    """``MNERF_DEVICE_METRICS`` (default 1): on CUDA, ``Coach.test_model`` / ``validate_model`` take PSNR and SSIM from the HIP
+    kernel (``hip.image_metrics``) and copy them to the host once per loader; 0 restores ``psnr`` / ``EvalTools`` on the host, one
+    copy per image (measured: DESIGN.md section 4, tools/eval_time.py)"""
+    import os
+    return os.environ.get("MNERF_DEVICE_METRICS", "1").lower() not in ("0", "off", "false", "no")
+
+
+class DeviceEval:
+    """Collects the [B,4] rows (PSNR dB, SSIM, MSE, kept pixels) of many batches on the device; ``finish()`` is the ONE copy to
+    the host.  Each batch has a key (its global index in the loader), so that the rows of several ranks can be merged in order."""
+
+    def __init__(self):
+        self.keys, self.rows = [], []
+
+    def add(self, key, pred, gt, invalid_mask=None):
+        """``pred`` [B,H*W,3], ``gt`` [B,3,H,W], ``invalid_mask`` [B,H,W] or None: as ``hip.image_metrics``.  Enqueues, no sync."""
+        from . import hip
+        self.rows.append(hip.image_metrics(pred, gt, invalid_mask))
+        self.keys.append(int(key))
+
+    def finish(self):
+        """-> (keys int64 [n, 2], rows float64 [n, 4]) numpy arrays, one row per IMAGE in the order added; an image's key is (its
+        batch's key, its index within the batch)"""
+        import torch
+        if not self.rows:
+            return np.zeros((0, 2), np.int64), np.zeros((0, 4), np.float64)
+        keys = np.asarray([(k, i) for k, r in zip(self.keys, self.rows) for i in range(r.shape[0])], np.int64)
+        rows = torch.cat(self.rows, 0).cpu().numpy()
+        self.keys, self.rows = [], []
+        return keys, rows
+
+
+def batch_owner(batch_index, world):
+    """sharded evaluation: batch ``bi`` of every loader belongs to rank ``bi % world``"""
+    return int(batch_index) % max(int(world), 1)
+
+
+def rank_batches(n_batches, rank, world):
+    """the global batch indices of ``rank``: rank, rank + world, ... below ``n_batches``"""
+    return list(range(int(rank), int(n_batches), max(int(world), 1)))
+
+
+def merge_rows(tagged):
+    """float64 [n, 2 + k] rows (global batch index, image within the batch, k values) gathered from all ranks in any order -> the
+    rows sorted by (batch, image): the order a single process evaluates them in.  The sort is stable and the keys are unique."""
+    tagged = np.asarray(tagged, np.float64)
+    if tagged.ndim != 2 or tagged.shape[1] < 2:
+        raise ValueError(f"merge_rows: expected [n, 2 + k] rows, got {tagged.shape}")
+    order = np.lexsort((tagged[:, 1], tagged[:, 0]))
+    return tagged[order]
+
+
+def gather_rows(tagged, device=None):
+    """Every rank's tagged rows (``merge_rows`` layout, float64 [n_r, 2 + k], n_r may be 0) in ONE ragged ``dist.gather_blocks``,
+    merged in order; without a process group: the rows themselves, in order.  Every rank receives the report."""
+    import torch
+    from . import dist as mdist
+    local = torch.from_numpy(np.ascontiguousarray(tagged, np.float64))
+    if mdist.group_active():
+        import torch.distributed as td
+        if td.get_backend() != "gloo" and device is not None:
+            local = local.to(device)
+        local = mdist.gather_blocks(local).cpu()
+    return merge_rows(local.numpy())
+
+
 # ----------------------------------------------------------------------------- LPIPS (VGG-16 variant of lpips v0.1)
 
 LPIPS_VGG_SLICES = ((0, 4), (4, 9), (9, 16), (16, 23), (23, 30))      # torchvision vgg16.features up to relu1_2 .. relu5_3

@@ -2,9 +2,18 @@
 """Inference entry point on the MI355X hot path (counterpart of the reference's test.py:10-33).
 
     python test.py --yaml=test --name=run --nerf.rand_rays_test=4096 --nerf.sample_intvs=64
+    python test.py --yaml=test --name=run --gpu_ids=0,1,2,3        # sharded: one process per listed GPU
 
 Options use the reference's ``--a.b.c=value`` grammar and YAML inheritance; the configured
-test sets are served by seeded synthetic scenes when no dataset is on disk."""
+test sets are served by seeded synthetic scenes when no dataset is on disk.
+
+PSNR and SSIM are computed on the device (csrc/metrics.hip; ``MNERF_DEVICE_METRICS=0``: on the host, as the reference does).
+
+Several GPUs: in a process without ``WORLD_SIZE``, ``--gpu_ids`` longer than one starts one fresh child process per listed GPU
+through train.py's launcher (the launching process never touches a GPU); under ``torchrun`` the ranks it is given are used as they
+are.  Batch ``bi`` of every test set is rendered and scored by rank ``bi % W``; rank 0 assembles the report of a one-process run and
+alone writes ``0results_<set>.txt``; every rank writes the images of its own share.  ``MNERF_FORCE_DEVICE=0
+MNERF_DIST_BACKEND=gloo`` runs all ranks on one GPU (dry runs, tests).  Video paths (``nerf.render_video``) are not sharded."""
 import os
 import sys
 
@@ -13,19 +22,43 @@ sys.path.insert(0, ROOT)
 
 
 def run(argv):
-    from matchnerf_amd import options
+    from matchnerf_amd import dist, options
     from matchnerf_amd.coach import Coach
 
-    opt = options.set(opt_cmd=options.parse_arguments(argv))
-    options.save_options_file(opt)
+    rank, world, device = 0, 1, None
+    if "WORLD_SIZE" in os.environ:
+        rank, world, device = dist.init_from_env()
+    opt = options.set(opt_cmd=options.parse_arguments(argv), make_output_dir=rank == 0, verbose=rank == 0)
+    if device is not None and not opt.cpu:
+        opt.device = str(device)  # the rank's device is init_from_env's (MNERF_FORCE_DEVICE)
+    if rank == 0:
+        options.save_options_file(opt)
+    dist.barrier()  # the output directory exists before any rank goes on
     coach = Coach(opt)
     coach.build_networks()
     coach.restore_checkpoint()
     coach.load_dataset(splits=["test"])
     if opt.nerf.render_video:
+        if world > 1:
+            raise SystemExit("test.py: nerf.render_video is not sharded; run it with one GPU")
         return coach.test_model_video()
-    return coach.test_model(save_images=bool(getattr(opt, "separate_save", False)))
+    report = coach.test_model(save_images=bool(getattr(opt, "separate_save", False)))
+    if world > 1:
+        import torch
+        dist.barrier(always=True)
+        torch.distributed.destroy_process_group()
+    return report
+
+
+def main(argv):
+    if "WORLD_SIZE" not in os.environ:
+        import train
+        gpu_ids = train.requested_gpu_ids(argv)
+        if len(gpu_ids) > 1:
+            return train.launch(argv, gpu_ids, script=os.path.abspath(__file__))
+    run(argv)
+    return 0
 
 
 if __name__ == "__main__":
-    run(sys.argv[1:])
+    sys.exit(main(sys.argv[1:]))

@@ -1,0 +1,264 @@
+"""Host side of the evaluation on the device, without a GPU: the two ABI-12 symbols in header, binding and library, the argument
+checks of the C entry point (they precede any launch), the batch -> rank rule and the merge of the ranks' rows - also over a gloo
+world of two with a rank that owns nothing -, Coach.test_model / validate_model sharded over two CPU ranks against the one-process
+report, and the launcher's child command for test.py."""
+import os
+import re
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from conftest import REPO
+from matchnerf_amd import hip, metrics, options
+
+
+def test_header_binding_and_library_agree_on_abi_12():
+    lib = hip.load()
+    header = open(os.path.join(REPO, "include", "mnerf.h")).read()
+    assert hip.MNERF_ABI_VERSION == 12 == lib.mnerf_abi_version()
+    assert int(re.search(r"#define MNERF_ABI_VERSION (\d+)", header).group(1)) == 12
+    declared = set(re.findall(r"\b(mnerf_[a-z_0-9]+)\s*\(", header))
+    for name in ("mnerf_image_metrics", "mnerf_image_metrics_workspace_bytes"):
+        assert name in declared and name in hip.EXPORTS and hasattr(lib, name), name
+    assert "metrics.hip" in __import__("matchnerf_amd.csrc.build", fromlist=["SOURCES"]).SOURCES
+
+
+def test_workspace_helper_and_argument_checks_need_no_gpu():
+    lib = hip.load()
+    size = lib.mnerf_image_metrics_workspace_bytes
+    assert size(1, 7, 7) > 0 and size(1, 7, 7) % 8 == 0
+    assert size(3, 7, 7) == 3 * size(1, 7, 7)                 # per image: nothing is shared between the images of a batch
+    assert size(1, 512, 640) >= size(1, 511, 640) >= size(1, 64, 80) >= size(1, 7, 7)
+    assert size(2, 512, 640) <= 1 << 20                       # a few slots per tile, not a copy of the frame
+    for bad in ((1, 6, 7), (1, 7, 6), (1, 0, 0), (1, -5, 40), (0, 64, 64), (-1, 64, 64)):
+        assert size(*bad) == -1, bad
+    fn = lib.mnerf_image_metrics  # every check precedes the launch: made-up, aligned, non-NULL pointers never reach a kernel
+    p = 1 << 20
+    assert fn(None, p, 300, None, 1, 10, 10, p, p, None) == hip.MNERF_E_NULL
+    assert fn(p, None, 300, None, 1, 10, 10, p, p, None) == hip.MNERF_E_NULL
+    assert fn(p, p, 300, None, 1, 10, 10, None, p, None) == hip.MNERF_E_NULL
+    assert fn(p, p, 300, None, 1, 10, 10, p, None, None) == hip.MNERF_E_NULL
+    assert fn(p, p, 270, None, 1, 9, 10, p, p, None) == hip.MNERF_E_RANGE      # H = 9 without a mask
+    assert fn(p, p, 270, None, 1, 10, 9, p, p, None) == hip.MNERF_E_RANGE
+    assert fn(p, p, 126, p, 1, 6, 7, p, p, None) == hip.MNERF_E_RANGE          # H = 6 with a mask
+    assert fn(p, p, 126, p, 1, 7, 6, p, p, None) == hip.MNERF_E_RANGE
+    assert fn(p, p, 300, None, 0, 10, 10, p, p, None) == hip.MNERF_E_RANGE     # no image
+    assert fn(p, p, 299, None, 2, 10, 10, p, p, None) == hip.MNERF_E_RANGE     # overlapping images of gt
+    assert fn(p, p, 300, None, 1, 10, 10, p + 4, p, None) == hip.MNERF_E_ALIGN
+    assert b"8-byte aligned" in lib.mnerf_last_error()
+    with pytest.raises(hip.MnerfError):  # the binding: no CPU fallback
+        hip.image_metrics(torch.rand(1, 100, 3), torch.rand(1, 3, 10, 10))
+
+
+def test_the_switch_reads_the_environment(monkeypatch):
+    monkeypatch.delenv("MNERF_DEVICE_METRICS", raising=False)
+    assert metrics.device_metrics_enabled()
+    for v, want in (("0", False), ("off", False), ("false", False), ("1", True), ("on", True)):
+        monkeypatch.setenv("MNERF_DEVICE_METRICS", v)
+        assert metrics.device_metrics_enabled() == want
+
+
+def test_batches_go_to_ranks_round_robin_and_rows_merge_in_order():
+    for n in (0, 1, 3, 8):
+        for world in (1, 2, 3, 8):
+            shares = [metrics.rank_batches(n, r, world) for r in range(world)]
+            assert sorted(b for s in shares for b in s) == list(range(n))
+            assert all(metrics.batch_owner(b, world) == r for r, s in enumerate(shares) for b in s)
+    assert metrics.rank_batches(3, 0, 2) == [0, 2] and metrics.rank_batches(3, 1, 2) == [1] and metrics.rank_batches(1, 1, 2) == []
+    # rank order (0: batches 0, 2; 1: batch 1 of two images) -> the one-process order
+    r0 = np.array([[0, 0, 30.0, 0.9], [2, 0, 32.0, 0.7]])
+    r1 = np.array([[1, 0, 31.0, 0.8], [1, 1, 31.5, np.nan]])
+    merged = metrics.merge_rows(np.concatenate([r0, r1]))
+    assert merged[:, :2].tolist() == [[0, 0], [1, 0], [1, 1], [2, 0]]
+    assert merged[:, 2].tolist() == [30.0, 31.0, 31.5, 32.0] and np.isnan(merged[2, 3])
+    assert metrics.merge_rows(np.zeros((0, 4))).shape == (0, 4)
+    with pytest.raises(ValueError):
+        metrics.merge_rows(np.zeros(4))
+    keys, rows = metrics.DeviceEval().finish()  # a rank that owned no batch
+    assert keys.shape == (0, 2) and rows.shape == (0, 4)
+
+
+# ------------------------------------------------------------------------------------------------ a stub model on CPU ranks
+
+
+class EvalLoader:
+    """a handed-in test / validation loader: a name and ``n`` one-image batches of 12 x 16 pixels, batch ``i`` from seed ``i``"""
+
+    def __init__(self, name, n):
+        self.name, self.n = name, n
+
+    def get_name(self):
+        return self.name
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        for i in range(self.n):
+            g = torch.Generator().manual_seed(1000 + i)
+            yield {"images": torch.rand(1, 4, 3, 12, 16, generator=g), "scene": [f"s{i}"]}
+
+
+class FrameModel(torch.nn.Module):
+    """'renders' the whole target frame: the first source view plus a little of the second"""
+
+    def __init__(self, opts=None):
+        super().__init__()
+        self.feat_enc, self.nerf_dec = torch.nn.Linear(1, 1), torch.nn.Linear(1, 1)
+
+    def forward(self, var, mode=None):
+        b, _, c, h, w = var.images.shape
+        var.rgb = (0.9 * var.images[:, -1] + 0.1 * var.images[:, 0]).reshape(b, c, h * w).permute(0, 2, 1)
+        return var
+
+
+def frame_coach(tmp, name, make_output_dir=True):
+    from matchnerf_amd import models
+    from matchnerf_amd.coach import Coach
+    models.models_dict["frames"] = FrameModel
+    os.chdir(tmp)
+    cmd = options.parse_arguments(["--yaml=train", f"--name={name}", "--cpu=true", "--tb=false", "--model=frames", f"--output_root={tmp}"])
+    opt = options.set(cmd, make_output_dir=make_output_dir, verbose=False)
+    c = Coach(opt)
+    c.build_networks()
+    c.test_loaders = [EvalLoader("alpha", 5), EvalLoader("dtu", 1)]  # shares 3 + 2, and 1 + 0: rank 1 owns nothing of the second
+    c.val_loader = EvalLoader("val", 3)
+    return c
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _eval_worker(rank, world, port, tmp, q):
+    try:
+        import datetime
+
+        import torch.distributed as td
+        os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        td.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+        # the ranks' rows in one ragged gather; rank 1 holds none
+        mine = np.array([[0, 0, 1.5, 0.5, np.nan], [2, 0, 2.5, 0.25, np.nan]]) if rank == 0 else np.zeros((0, 5))
+        got = metrics.gather_rows(mine)
+        ok = got.shape == (2, 5) and got[:, 0].tolist() == [0.0, 2.0]
+        mine = np.array([[b, 0, float(rank), 0.0] for b in metrics.rank_batches(3, rank, world)])
+        got = metrics.gather_rows(mine.reshape(-1, 4))
+        ok = ok and got[:, 0].tolist() == [0.0, 1.0, 2.0] and got[:, 2].tolist() == [0.0, 1.0, 0.0]
+        td.barrier()
+        c = frame_coach(tmp, "two", make_output_dir=rank == 0)
+        assert c.distributed and c.world == 2
+        c.it = 7
+        report = c.test_model(save_images=True)
+        val = c.validate_model()
+        td.barrier()
+        td.destroy_process_group()
+        q.put((rank, bool(ok), report, val))
+    except BaseException as e:  # noqa: BLE001
+        import traceback
+        q.put((rank, False, repr(e) + traceback.format_exc()[-2000:], None))
+
+
+def test_two_cpu_ranks_report_what_one_process_reports(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    one = frame_coach(str(tmp_path), "one")
+    one.it = 7
+    want = one.test_model(save_images=True)
+    want_val = one.validate_model()
+    assert list(want) == ["alpha", "dtu"] and list(want["alpha"]) == [f"alpha_{i:03d}_0" for i in range(5)]
+    assert all(np.isfinite(v) for v in want["alpha"].values())
+
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_eval_worker, args=(r, 2, port, str(tmp_path), q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res = sorted((q.get(timeout=180) for _ in procs), key=lambda r: r[0])
+    finally:
+        for p in procs:
+            p.join(timeout=30)
+            if p.is_alive():
+                p.kill()
+    for rank, ok, report, val in res:
+        assert ok is True, report
+        assert report == want and val == want_val, rank  # every rank holds the one-process report, bit for bit
+    for name in ("alpha", "dtu"):
+        a = open(tmp_path / "one" / "test" / f"0results_{name}.txt", "rb").read()
+        assert a == open(tmp_path / "two" / "test" / f"0results_{name}.txt", "rb").read()
+    assert sorted(os.listdir(tmp_path / "two" / "test")) == sorted(os.listdir(tmp_path / "one" / "test"))  # the images of both shares
+    assert sorted(os.listdir(tmp_path / "two" / "validation")) == ["s0_000_0_it7.jpg", "s1_001_0_it7.jpg", "s2_002_0_it7.jpg"]
+    rows = [l for l in open(tmp_path / "two" / "scalars.jsonl")]
+    assert len(rows) == 2 and rows == [l for l in open(tmp_path / "one" / "scalars.jsonl")]  # rank 0 alone logged
+
+
+class CountingDataset(torch.utils.data.Dataset):
+    def __init__(self, n):
+        self.n, self.read = n, []
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        self.read.append(i)
+        return {"index": torch.tensor(i)}
+
+
+def test_an_on_disk_loader_is_rebuilt_over_the_ranks_own_indices(tmp_path, monkeypatch):
+    """a sequential DataLoader: rank r reads the items of batches r, r + W, ... and no other (batch size 2, 7 items: 4 batches)"""
+    monkeypatch.chdir(tmp_path)
+    c = frame_coach(str(tmp_path), "loader")
+    seen = {}
+    for rank in range(2):
+        ds = CountingDataset(7)
+        loader = torch.utils.data.DataLoader(ds, batch_size=2, shuffle=False)
+        seen[rank] = [(bi, batch["index"].tolist()) for bi, batch in c._own_batches(loader, rank, 2)]
+        assert sorted(ds.read) == sorted(i for _, idx in seen[rank] for i in idx)
+    assert seen[0] == [(0, [0, 1]), (2, [4, 5])] and seen[1] == [(1, [2, 3]), (3, [6])]
+    ds = CountingDataset(3)
+    assert [bi for bi, _ in c._own_batches(torch.utils.data.DataLoader(ds, batch_size=2), 0, 1)] == [0, 1]
+    assert [bi for bi, _ in c._own_batches(EvalLoader("x", 5), 1, 2)] == [1, 3]  # any other loader: skipped by index
+
+
+# ------------------------------------------------------------------------------------------------ the launcher
+
+
+def test_the_launcher_starts_test_py_when_told_to(monkeypatch):
+    import sys
+
+    import train
+    argv = ["--yaml=test", "--gpu_ids=0,1"]
+    assert train.child_command(argv) == [sys.executable, os.path.join(REPO, "train.py")] + argv  # the default: as before
+    assert train.child_command(argv, script=os.path.join(REPO, "test.py")) == [sys.executable, os.path.join(REPO, "test.py")] + argv
+    started = []
+
+    class Done:
+        returncode = 0
+
+        def __init__(self, cmd, env=None):
+            started.append((cmd, env))
+
+        def poll(self):
+            return 0
+
+        def wait(self, timeout=None):
+            return 0
+
+    monkeypatch.setattr(train.subprocess, "Popen", Done)
+    assert train.launch(argv, [0, 1]) == 0
+    assert train.launch(argv, [3, 5], script=os.path.join(REPO, "test.py")) == 0
+    assert [c for c, _ in started] == [[sys.executable, os.path.join(REPO, "train.py")] + argv] * 2 + \
+        [[sys.executable, os.path.join(REPO, "test.py")] + argv] * 2
+    assert [(e["RANK"], e["LOCAL_RANK"], e["WORLD_SIZE"]) for _, e in started[2:]] == [("0", "3", "2"), ("1", "5", "2")]
+    import test as entry
+    calls = []
+    monkeypatch.setattr(train, "launch", lambda a, ids, script=None: calls.append((a, ids, script)) or 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    assert entry.main(argv) == 0 and calls == [(argv, [0, 1], os.path.join(REPO, "test.py"))]

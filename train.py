@@ -58,11 +58,16 @@ def free_port():
     return port
 
 
-def launch(argv, gpu_ids):
-    """One fresh child per GPU; -> 0 when all exit with 0.  When a child fails the others are ended (they would wait for it in
-    their next collective) and its status is returned."""
+def child_command(argv, script=None):
+    """what a rank is started with: this interpreter on ``script`` (default: this file) with the launcher's own arguments"""
+    return [sys.executable, os.path.abspath(script or __file__)] + list(argv)
+
+
+def launch(argv, gpu_ids, script=None):
+    """One fresh child per GPU, running ``script`` (default: this file; test.py passes itself); -> 0 when all exit with 0.  When a
+    child fails the others are ended (they would wait for it in their next collective) and its status is returned."""
     envs = child_environments(gpu_ids, os.environ, free_port())
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)] + list(argv), env=env) for env in envs]
+    procs = [subprocess.Popen(child_command(argv, script), env=env) for env in envs]
     status = 0
     try:
         while any(p.poll() is None for p in procs):
@@ -83,7 +88,7 @@ def launch(argv, gpu_ids):
                 p.kill()
                 p.wait()
     if status:
-        print(f"train.py: a rank failed (exit status {status}); ranks on GPUs {list(gpu_ids)}", file=sys.stderr)
+        print(f"{os.path.basename(script or __file__)}: a rank failed (exit status {status}); ranks on GPUs {list(gpu_ids)}", file=sys.stderr)
     return status if 0 < status < 256 else (1 if status else 0)
 
 
