@@ -42,6 +42,9 @@
  *       mnerf_grad_pack, mnerf_grad_unpack.
  *   v12 no layout change: evaluation on the device (matchnerf_amd/csrc/metrics.hip) - mnerf_image_metrics,
  *       mnerf_image_metrics_workspace_bytes.
+ *       Added under v12 without a layout change: LPIPS on the device (matchnerf_amd/csrc/lpips.hip) - the table mnerf_lpips_weights - struct
+ *       index 10 -, mnerf_lpips_wstream_floats, mnerf_lpips_workspace_bytes, mnerf_lpips_vgg, mnerf_maxpool2x2, mnerf_lpips_head_slots,
+ *       mnerf_lpips_head, mnerf_lpips_sum; mnerf_conv2d accepts c_out 256 / 512 (blocks of 128 output channels).
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -429,7 +432,10 @@ int mnerf_upsample_bilinear2x_backward(const float* dout, float* din, int64_t pl
 
 /* Convolutions of the GMFlow backbone / up-sampler (models/gmflow/backbone.py:6-122, superres.py:5-38) as implicit
  * GEMMs with fp32-grade split-fp16 products (matchnerf_amd/csrc/conv.hip).  Built: c_in a multiple of 32, c_out 64 /
- * 96 / 128, 1x1 and 3x3 filters with padding ksize/2, stride 1 / 2.
+ * 96 / 128, 1x1 and 3x3 filters with padding ksize/2, stride 1 / 2; and, for the VGG-16 of LPIPS (below), c_out 256 / 512 with
+ * NCHW input and output and no added tensor: the output channels are split into blocks of 128 along a grid dimension, and wstream
+ * is the concatenation of the blocks' streams, every block packed with the SAME ew (matchnerf_amd/gmflow.py: pack_conv_blocks).
+ * This is the entry point through which the wide convolution is tested alone.
  *   wstream     : A-operand fragments of 2^ew * W, K16-step s = (tap, 16 input channels), unit (s, 32-row block) =
  *                 [hi | lo] x 64 lanes x 8 fp16 (matchnerf_amd/gmflow.py: pack_conv); mnerf_conv_wstream_floats() words
  *   bias        : [c_out] or NULL;  leaky_slope: LeakyReLU slope applied to the result (1 = none)
@@ -665,6 +671,48 @@ int mnerf_grad_unpack(const mnerf_optim_row* rows, int32_t n_rows, int32_t n_blo
 int64_t mnerf_image_metrics_workspace_bytes(int32_t n_images, int32_t height, int32_t width);
 int mnerf_image_metrics(const float* pred, const float* gt, int64_t gt_image_stride, const uint8_t* invalid_mask,
                         int32_t n_images, int32_t height, int32_t width, void* workspace, double* out, void* stream);
+
+/* ABI v12 (added without a layout change) - LPIPS on the device: the VGG-16 variant of lpips v0.1 as matchnerf_amd/metrics.py
+ * (LPIPSVGG) restates it, replacing lpips.LPIPS(net='vgg') of misc/metrics.py:14-17,47-52 of the reference.  Same signature data as
+ * mnerf_image_metrics (pred [n, H*W, 3], gt [n, 3, H, W] with an image stride, invalid_mask [n, H, W] bytes or NULL).  With a mask the
+ * whole frame is used with the masked pixels set to 0 in both images (in [0, 1] space); without one the crop [H/10, H - H/10) x
+ * [W/10, W - W/10).  Then 2x - 1, (x - shift) / scale, the 13 convolutions 3x3 + bias + ReLU through mnerf_conv2d (three-product
+ * split-fp16, one power-of-two gain per operand tensor, fp32 accumulation; the first layer reads the 3 channels zero-padded to 32),
+ * four 2x2 max-pools and, after each of the five stages, the head: per pixel, unit(a) - unit(b) (channel norm + 1e-10), squared,
+ * weighted by the stage's non-negative head vector, spatial mean; the five means are added.  Norms, squares, sums and means are
+ * fp64.  The network is walked one pair (pred i, gt i) at a time with the pair's own absmax regions: out[i] depends neither on the
+ * other images nor on n_images, two runs are bit-identical (no floating-point atomics), and pred i == gt i gives exactly 0.
+ *   weights       the 13 layers in network order (relu1_1 .. relu5_3): wstream[l] = mnerf_lpips_wstream_floats(l) words, 16-byte
+ *                 aligned (gmflow.pack_conv_blocks; layer 0 from the weight zero-padded to 32 input channels), bias[l] [c_out],
+ *                 ew[l] the stream's exponent; head[s] [64 / 128 / 256 / 512 / 512] floats
+ *   workspace     16-byte aligned, mnerf_lpips_workspace_bytes(n, H, W, mask != NULL) bytes: two activation buffers shared by all
+ *                 pairs + n x (network input, 14 absmax regions, head slots):  bytes(n) = bytes(1) + (n - 1) x (bytes(2) - bytes(1))
+ *   out           [n] doubles, 8-byte aligned
+ * Every argument check precedes any launch (MNERF_E_NULL / _RANGE / _ALIGN).  Enqueue only.  The processed image must be at least
+ * 16 x 16 (four pools).  The one-gain-per-tensor split has been checked on random and layer-rescaled weights only; parity with the
+ * `lpips` package on its real weights is unpinned (tools/eval_time.py prints both paths' values for a user who has the files). */
+typedef struct mnerf_lpips_weights {
+  const float* wstream[13];
+  const float* bias[13];
+  const float* head[5];
+  int32_t ew[13];
+} mnerf_lpips_weights;
+/* host only; words of layer's weight stream (0 outside 0..12) */
+int64_t mnerf_lpips_wstream_floats(int32_t layer);
+/* host only; -1 for n_images < 1 or a processed image below 16 x 16 */
+int64_t mnerf_lpips_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t masked);
+int mnerf_lpips_vgg(const float* pred, const float* gt, int64_t gt_image_stride, const uint8_t* invalid_mask, int32_t n_images,
+                    int32_t height, int32_t width, const mnerf_lpips_weights* weights, void* workspace, double* out, void* stream);
+/* The building blocks, exported so that they can be tested alone (the wide convolution: mnerf_conv2d with c_out 256 / 512).
+ * mnerf_maxpool2x2: F.max_pool2d(x, 2, 2) of in [planes][h][w] -> out [planes][h/2][w/2] (floor: an odd last row / column is dropped).
+ * mnerf_lpips_head: one stage of one pair, feat_a / feat_b [channels][h][w] fp32 -> mnerf_lpips_head_slots(h, w) doubles, one per
+ * workgroup of 64 pixels, each already divided by h w; mnerf_lpips_sum: out[i] = the sum of image i's n_slots doubles at
+ * slots + i * image_stride, added in a fixed order by one workgroup. */
+int mnerf_maxpool2x2(const float* in, float* out, int64_t planes, int32_t h, int32_t w, void* stream);
+int64_t mnerf_lpips_head_slots(int32_t h, int32_t w);
+int mnerf_lpips_head(const float* feat_a, const float* feat_b, const float* head_w, int32_t channels, int32_t h, int32_t w,
+                     double* slots, void* stream);
+int mnerf_lpips_sum(const double* slots, int64_t image_stride, int32_t n_slots, int32_t n_images, double* out, void* stream);
 
 #ifdef __cplusplus
 }

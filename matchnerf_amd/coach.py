@@ -504,17 +504,19 @@ class Coach:
             if metrics.batch_owner(bi, world) == rank:
                 yield bi, batch
 
-    def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True):
+    def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True, device_lpips=None):
         """Render this rank's batches of ``loader`` in ``mode`` and score them -> rows float64 [n, 5] of ALL ranks' images in the
         order one process evaluates them: (batch index, image within the batch, PSNR, SSIM, LPIPS or NaN).
         On CUDA with ``metrics.device_metrics_enabled()`` PSNR / SSIM are rows of ``metrics.DeviceEval`` (csrc/metrics.hip) and reach
         the host in ONE copy after the last batch; a frame goes to the host only for ``on_frame(batch, bi, i, pred, gt)`` (images to
-        write) or an LPIPS callable.  Otherwise every frame is scored on the host (``metrics.psnr`` / ``EvalTools``).
+        write) or a host LPIPS callable ``lpips_fn``.  With ``device_lpips`` (a ``metrics.DeviceLPIPS``; CUDA path only) LPIPS is a
+        fifth column of the same rows (csrc/lpips.hip) and no frame leaves the device for it.  Otherwise every frame is scored on
+        the host (``metrics.psnr`` / ``EvalTools``).
         ``mask_of(gt_depth)`` -> the depth the invalid mask (depth == 0) comes from, or None for the 80 % centre crop.
         With a process group of more than one rank (``shard``), the ranks' rows travel in one ragged ``dist.gather_blocks``."""
         rank, world = self._eval_world() if shard else (0, 1)
         on_device = str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled()
-        dev = metrics.DeviceEval() if on_device else None
+        dev = metrics.DeviceEval(device_lpips) if on_device else None
         host_rows, lpips_of = [], {}
         for bi, batch in self._own_batches(loader, rank, world):
             if first_only and bi > 0:
@@ -544,10 +546,11 @@ class Coach:
                     on_frame(batch, bi, i, pred, gt)
         if dev is not None:
             keys, got = dev.finish()  # the one copy of this loader
-            rows = np.concatenate([keys.astype(np.float64), got[:, :2], np.full((len(keys), 1), np.nan)], 1)
+            last = got[:, 4:5] if dev.lpips is not None else np.full((len(keys), 1), np.nan)
+            rows = np.concatenate([keys.astype(np.float64), got[:, :2], last], 1)
         else:
             rows = np.asarray(host_rows, np.float64).reshape(-1, 5)
-        for j in range(len(rows)):
+        for j in range(len(rows) if lpips_of else 0):
             rows[j, 4] = lpips_of.get((int(rows[j, 0]), int(rows[j, 1])), np.nan)
         return metrics.gather_rows(rows, device=self.opts.device) if world > 1 else metrics.merge_rows(rows)
 
@@ -585,10 +588,21 @@ class Coach:
         With a process group of more than one rank every rank calls this and renders batch bi when bi % W is its rank; rank 0 alone
         writes the results files and prints, every rank returns the one-process report and writes the images of its own share."""
         self.model.eval()
-        try:
-            lpips_fn = metrics.load_lpips(device=self.opts.device)
-        except FileNotFoundError:
-            lpips_fn = None
+        lpips_fn, device_lpips = None, None
+        if str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled() and metrics.device_lpips_enabled():
+            try:  # LPIPS as a fifth column of the device rows (csrc/lpips.hip); the streams are packed once per coach
+                paths = (os.environ.get("MNERF_LPIPS_VGG16"), os.environ.get("MNERF_LPIPS_LIN"), os.environ.get("TORCH_HOME"))
+                if getattr(self, "_device_lpips", (None, None))[0] != paths:
+                    self._device_lpips = (paths, metrics.DeviceLPIPS(self.opts.device))
+                device_lpips = self._device_lpips[1]
+            except FileNotFoundError:
+                pass
+        else:
+            try:
+                lpips_fn = metrics.load_lpips(device=self.opts.device)
+            except FileNotFoundError:
+                pass
+        has_lpips = lpips_fn is not None or device_lpips is not None
         out_root = os.path.join(self.opts.output_path, "test")
         os.makedirs(out_root, exist_ok=True)
         report = {}
@@ -601,18 +615,19 @@ class Coach:
                 vis = np.concatenate([pred, gt], 1)
                 Image.fromarray((vis.clip(0, 1) * 255).astype("uint8")).save(os.path.join(out_root, f"{name}_{bi:03d}_{i}.png"))
 
-            rows = self._evaluate(loader, "test", lambda d: d, on_frame=save if save_images else None, lpips_fn=lpips_fn)
+            rows = self._evaluate(loader, "test", lambda d: d, on_frame=save if save_images else None, lpips_fn=lpips_fn,
+                                  device_lpips=device_lpips)
             self.model.nerf_setbg_opaque = False
             report[name] = {f"{name}_{int(r[0]):03d}_{int(r[1])}": float(r[2]) for r in rows}
             ssims = [float(r[3]) for r in rows]
-            lpipss = [float(r[4]) if lpips_fn else None for r in rows]
+            lpipss = [float(r[4]) if has_lpips else None for r in rows]
             vals = list(report[name].values())
             if self.rank == 0:
                 with open(os.path.join(out_root, f"0results_{name}.txt"), "w") as f:
                     for (k, v), sv, lv in zip(report[name].items(), ssims, lpipss):
                         f.write(f"{k}: PSNR {v:.4f} SSIM {sv:.4f}" + (f" LPIPS {lv:.4f}" if lv is not None else "") + "\n")
                     f.write(f"mean PSNR {np.mean(vals):.4f} SSIM {np.mean(ssims):.4f}" +
-                            (f" LPIPS {np.mean(lpipss):.4f}" if lpips_fn else "") + "\n")
+                            (f" LPIPS {np.mean(lpipss):.4f}" if has_lpips else "") + "\n")
             self.say(f"[coach] {name}: mean PSNR {np.mean(vals):.2f} over {len(vals)} images")
         return report
 

@@ -34,6 +34,7 @@ extern "C" int64_t mnerf_struct_size(int32_t which) {
     case 7: return (int64_t)sizeof(mnerf_encoder_layer_train);
     case 8: return (int64_t)sizeof(mnerf_optim_row);
     case 9: return (int64_t)sizeof(mnerf_optim_group);
+    case 10: return (int64_t)sizeof(mnerf_lpips_weights);
     default: return -1;
   }
 }

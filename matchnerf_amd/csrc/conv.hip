@@ -20,6 +20,8 @@
 // Weights: packed by the host as A-operand fragments (matchnerf_amd/gmflow.py, pack_conv), streamed in segments of
 // whole K16-step pairs (<= 36 KiB) through a 2 x 36 KiB LDS double buffer by LDS-DMA, one barrier per segment, two
 // workgroups of four waves per CU.
+// The VGG-16 of LPIPS (lpips.hip) runs its 3x3 convolutions here as well: 256 / 512 output channels as blocks of 128 along grid.y,
+// each block with its own weight stream, bias offset and output channel offset; for the widths above the block index is 0.
 #include "split_f16.hpp"
 
 #define CONV_NW 4
@@ -56,6 +58,10 @@ struct ConvParams {
   float leaky;                // LeakyReLU slope applied to the result (1 = none)
   int out_layout;             // MNERF_CONV_OUT_*: NCHW, channel-last tokens, pair-major channel-last
   const float* add_cl;        // [h_out * w_out][c_out] added to a channel-last result (position tile), or NULL
+  // wide outputs (c_out 256 / 512, NCHW only): blockIdx.y owns the 32 NMB output channels from 32 NMB blockIdx.y on, its weights are
+  // the blockIdx.y-th stream of wblock_floats words; c_total = channels of the stored output (32 NMB and one block otherwise)
+  int c_total;
+  long long wblock_floats;
 };
 
 // NMB: 32-row blocks of output channels; TPW: 32-pixel tiles per wave (2, or 1 when that is what it takes to give
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
   const int pieces = seg_units * 2;  // 1 KiB each
 
   auto stage = [&](int seg) {
-    const float* src = P.wstream + (size_t)seg * (size_t)seg_units * 512 + lane * 4;
+    const float* src = P.wstream + (size_t)blockIdx.y * (size_t)P.wblock_floats + (size_t)seg * (size_t)seg_units * 512 + lane * 4;
     const unsigned dst = buf0 + (unsigned)(seg & 1) * CONV_BUF_BYTES;
     glds_segment(src, dst, pieces, wave, CONV_NW);
   };
@@ -93,7 +99,7 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
     oy[t] = rem / P.w_out;
     ox[t] = rem - oy[t] * P.w_out;
     ibase[t] = (long long)img * P.si + (long long)(8 * hl) * P.sc;
-    obase[t] = (long long)img * (32 * NMB) * hw_out + rem;
+    obase[t] = ((long long)img * P.c_total + (long long)blockIdx.y * (32 * NMB)) * hw_out + rem;
   }
   const int pad = P.ksize >> 1;
   const int h_eff = P.h_in << P.up, w_eff = P.w_in << P.up;
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(CONV_NW * 64, 2) void conv_kernel(ConvParams P) {
   // ---- epilogue: scale back, bias, LeakyReLU, largest magnitude, NCHW store (32 consecutive pixels per register)
   const float cm = pow2i(-(P.ew + eg));
   float* bias_lds = conv_smem;  // the weight buffers are free now
-  for (int i = tid; i < 32 * NMB; i += CONV_NW * 64) bias_lds[i] = P.bias ? P.bias[i] : 0.0f;
+  for (int i = tid; i < 32 * NMB; i += CONV_NW * 64) bias_lds[i] = P.bias ? P.bias[blockIdx.y * (32 * NMB) + i] : 0.0f;
   __syncthreads();
   float omax = 0.0f;
 #pragma unroll
@@ -338,9 +344,9 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
                             int32_t w_in, void* stream) {
   const char* who = "mnerf_conv2d";
   MNERF_REQUIRE(cv, MNERF_E_NULL, "%s: cv is NULL", who);
-  MNERF_REQUIRE(cv->c_in >= 32 && cv->c_in % 32 == 0 && (cv->c_out == 64 || cv->c_out == 96 || cv->c_out == 128) &&
+  MNERF_REQUIRE(cv->c_in >= 32 && cv->c_in % 32 == 0 && (cv->c_out == 64 || cv->c_out == 96 || cv->c_out == 128 || cv->c_out == 256 || cv->c_out == 512) &&
                     (cv->ksize == 1 || cv->ksize == 3) && (cv->stride == 1 || cv->stride == 2),
-                MNERF_E_UNSUPPORTED, "%s: c_in=%d c_out=%d ksize=%d stride=%d (built: c_in %% 32 == 0, c_out 64/96/128, 1x1 / 3x3, stride 1 / 2)",
+                MNERF_E_UNSUPPORTED, "%s: c_in=%d c_out=%d ksize=%d stride=%d (built: c_in %% 32 == 0, c_out 64/96/128/256/512, 1x1 / 3x3, stride 1 / 2)",
                 who, cv->c_in, cv->c_out, cv->ksize, cv->stride);
   MNERF_REQUIRE(n_img >= 0 && h_in >= 1 && w_in >= 1, MNERF_E_RANGE, "%s: n_img=%d h_in=%d w_in=%d", who, n_img, h_in, w_in);
   MNERF_REQUIRE(cv->leaky_slope >= 0.0f, MNERF_E_RANGE, "%s: leaky_slope=%g", who, (double)cv->leaky_slope);
@@ -383,7 +389,13 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
                   (long long)n_img * p.si * 4);
   }
   p.ew = cv->ew;
-  const int nmb = cv->c_out / 32, n_steps = cv->ksize * cv->ksize * (cv->c_in / 16);
+  // c_out 256 / 512: blocks of 128 output channels along grid.y, each with its own weight stream (gmflow.pack_conv_blocks)
+  const int n_blk = cv->c_out > 128 ? cv->c_out / 128 : 1;
+  const int nmb = cv->c_out / n_blk / 32, n_steps = cv->ksize * cv->ksize * (cv->c_in / 16);
+  p.c_total = cv->c_out;
+  p.wblock_floats = mnerf_conv_wstream_floats(cv->c_in, 32 * nmb, cv->ksize);
+  MNERF_REQUIRE(n_blk == 1 || (out_layout == MNERF_CONV_OUT_NCHW && !in_channels_last && !add_bilinear2x && !add_channel_last), MNERF_E_UNSUPPORTED,
+                "%s: c_out=%d is built for NCHW in and out without an added tensor", who, cv->c_out);
   p.seg_steps = conv_seg_steps(n_steps, nmb);
   p.n_seg = n_steps / p.seg_steps;
   p.leaky = cv->leaky_slope;
@@ -401,7 +413,7 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
   // two pixel tiles per wave share every weight fragment read; one tile per wave when that grid would leave CUs idle
   const int tpw = (n_pix + 255) / 256 >= 256 ? 2 : 1;
   const long long per_wg = 32 * tpw * CONV_NW;
-  const dim3 grid((unsigned)((n_pix + per_wg - 1) / per_wg));
+  const dim3 grid((unsigned)((n_pix + per_wg - 1) / per_wg), (unsigned)n_blk);
   const size_t lds = 2 * CONV_BUF_BYTES;
   hipStream_t st = (hipStream_t)stream;
   const bool cl = in_channels_last != 0;

@@ -101,6 +101,28 @@ def pack_conv(weight):
     return halfs.reshape(-1).view(np.float32).copy(), int(ew)
 
 
+def pack_conv_blocks(weight, block=128):
+    """Conv2d weight [c_out, c_in, k, k] of ANY width -> (wstream, ew) for ``mnerf_conv2d`` with c_out above 128 (csrc/conv.hip: the
+    output channels run in blocks of ``block`` along a grid dimension): the ``pack_conv`` stream of every block of ``block`` rows,
+    one after the other, all with ONE exponent ew (the kernel scales the result back by one power of two per layer).  c_in is
+    zero-padded to a multiple of 32 (the first layer of LPIPS's VGG-16: 3 -> 32).  c_out <= ``block``: exactly ``pack_conv``."""
+    import numpy as np
+    from . import cond_nerf as CN
+    w = (weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)).astype(np.float32)
+    c_out, c_in, kh, kw = w.shape
+    pad = -c_in % 32
+    if pad:
+        w = np.concatenate([w, np.zeros((c_out, pad, kh, kw), np.float32)], 1)
+        c_in += pad
+    assert kh == kw and c_out % 32 == 0 and (c_out <= block or c_out % block == 0), w.shape
+    mat = np.ascontiguousarray(w.transpose(0, 2, 3, 1).reshape(c_out, kh * kw * c_in))
+    ew = CN.f16_weight_exponent(mat)
+    cols = np.arange(mat.shape[1]).reshape(-1, 2, 8)
+    rows = min(block, c_out)
+    parts = [CN._fragments_h(mat[r:r + rows], cols, rows // 32, ew).reshape(-1) for r in range(0, c_out, rows)]
+    return np.concatenate(parts).view(np.float32).copy(), int(ew)
+
+
 def pack_conv_stem(weight):
     """The stem's weight [64, 3, 7, 7] -> (wstream, ew) for ``mnerf_conv_stem``: matrix [64, 3 tap + c], 147 columns
     padded with zeros to ten K16-steps."""

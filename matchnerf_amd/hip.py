@@ -34,7 +34,9 @@ EXPORTS = ("mnerf_abi_version", "mnerf_last_error", "mnerf_struct_size", "mnerf_
            "mnerf_window_attention_presplit_stats", "mnerf_window_attention_backward_stats", "mnerf_encoder_block_save", "mnerf_encoder_layer_backward_saved",
            "mnerf_optim_row_blocks", "mnerf_grad_sumsq", "mnerf_adamw_step", "mnerf_l2_loss",
            "mnerf_grad_bucket_floats", "mnerf_grad_pack", "mnerf_grad_unpack",
-           "mnerf_image_metrics_workspace_bytes", "mnerf_image_metrics")
+           "mnerf_image_metrics_workspace_bytes", "mnerf_image_metrics",
+           "mnerf_lpips_wstream_floats", "mnerf_lpips_workspace_bytes", "mnerf_lpips_vgg", "mnerf_maxpool2x2", "mnerf_lpips_head_slots",
+           "mnerf_lpips_head", "mnerf_lpips_sum")
 
 
 class MnerfError(RuntimeError):
@@ -107,6 +109,15 @@ class ConvLayer(C.Structure):
     _fields_ = [("wstream", C.c_void_p), ("wstream_floats", C.c_int64), ("bias", C.c_void_p), ("c_in", C.c_int32),
                 ("c_out", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("ew", C.c_int32),
                 ("leaky_slope", C.c_float)]
+
+
+LPIPS_LAYERS, LPIPS_STAGES = 13, 5
+
+
+class LpipsWeightTable(C.Structure):
+    """struct mnerf_lpips_weights: the by-pointer table of mnerf_lpips_vgg"""
+    _fields_ = [("wstream", C.c_void_p * LPIPS_LAYERS), ("bias", C.c_void_p * LPIPS_LAYERS), ("head", C.c_void_p * LPIPS_STAGES),
+                ("ew", C.c_int32 * LPIPS_LAYERS)]
 
 
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8  # MNERF_OPTIM_CHUNK, MNERF_OPTIM_MAX_GROUPS
@@ -267,6 +278,20 @@ def load():
     lib.mnerf_image_metrics_workspace_bytes.argtypes = [i32, i32, i32]
     lib.mnerf_image_metrics.restype = C.c_int
     lib.mnerf_image_metrics.argtypes = [fp, fp, i64, vp, i32, i32, i32, vp, vp, vp]
+    lib.mnerf_lpips_wstream_floats.restype = i64
+    lib.mnerf_lpips_wstream_floats.argtypes = [i32]
+    lib.mnerf_lpips_workspace_bytes.restype = i64
+    lib.mnerf_lpips_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.mnerf_lpips_vgg.restype = C.c_int
+    lib.mnerf_lpips_vgg.argtypes = [fp, fp, i64, vp, i32, i32, i32, C.POINTER(LpipsWeightTable), vp, vp, vp]
+    lib.mnerf_maxpool2x2.restype = C.c_int
+    lib.mnerf_maxpool2x2.argtypes = [fp, fp, i64, i32, i32, vp]
+    lib.mnerf_lpips_head_slots.restype = i64
+    lib.mnerf_lpips_head_slots.argtypes = [i32, i32]
+    lib.mnerf_lpips_head.restype = C.c_int
+    lib.mnerf_lpips_head.argtypes = [fp, fp, fp, i32, i32, i32, vp, vp]
+    lib.mnerf_lpips_sum.restype = C.c_int
+    lib.mnerf_lpips_sum.argtypes = [vp, i64, i32, i32, vp, vp]
     ver = lib.mnerf_abi_version()
     if ver != MNERF_ABI_VERSION:
         raise MnerfError(f"libmnerf_hip.so ABI {ver} != binding ABI {MNERF_ABI_VERSION}")
@@ -1320,6 +1345,138 @@ def image_metrics(pred, gt, invalid_mask=None, stream=None):
         check(lib.mnerf_image_metrics(_ptr(pred), _ptr(gt), int(gt_stride), _ptr(invalid_mask), b, h, w, _ptr(workspace), _ptr(out), st),
               "mnerf_image_metrics")
         if stream is not None:  # the caching allocator must not hand the buffers on before this stream is through with them
+            workspace.record_stream(stream)
+            out.record_stream(stream)
+    return out
+
+
+# ----------------------------------------------------------------------- LPIPS on the device (csrc/lpips.hip)
+
+
+def maxpool2x2(x, stream=None):
+    """``F.max_pool2d(x, 2, 2)`` of a contiguous float32 CUDA tensor [..., H, W] -> [..., H // 2, W // 2] (mnerf_maxpool2x2)."""
+    import torch
+    lib = load()
+    if not torch.is_tensor(x) or x.dim() < 2:
+        raise MnerfError("maxpool2x2: expected a tensor [..., H, W]")
+    _f32c(x, "x")
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    planes = x.numel() // (h * w)
+    out = torch.empty(tuple(x.shape[:-2]) + (h // 2, w // 2), dtype=torch.float32, device=x.device)
+    with _on(x.device, stream) as st:
+        check(lib.mnerf_maxpool2x2(_ptr(x), _ptr(out), planes, h, w, st), "mnerf_maxpool2x2")
+    return out
+
+
+def lpips_head(feat_a, feat_b, head_w, stream=None):
+    """One stage of the LPIPS distance of one pair: feat_a, feat_b [C, H, W] float32 CUDA, head_w [C] -> float64 CUDA tensor [1]:
+    mean over pixels of sum_c head_w[c] (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, all in fp64 (mnerf_lpips_head + mnerf_lpips_sum)."""
+    import torch
+    lib = load()
+    for name, t in (("feat_a", feat_a), ("feat_b", feat_b), ("head_w", head_w)):
+        _f32c(t, name)
+    if feat_a.dim() != 3 or feat_a.shape != feat_b.shape or head_w.numel() != feat_a.shape[0]:
+        raise MnerfError(f"lpips_head: feat_a {tuple(feat_a.shape)}, feat_b {tuple(feat_b.shape)}, head_w {tuple(head_w.shape)}")
+    c, h, w = (int(v) for v in feat_a.shape)
+    n_slots = int(lib.mnerf_lpips_head_slots(h, w))
+    with _on(feat_a.device, stream) as st:
+        slots = torch.empty(n_slots, dtype=torch.float64, device=feat_a.device)
+        out = torch.empty(1, dtype=torch.float64, device=feat_a.device)
+        check(lib.mnerf_lpips_head(_ptr(feat_a), _ptr(feat_b), _ptr(head_w), c, h, w, _ptr(slots), st), "mnerf_lpips_head")
+        check(lib.mnerf_lpips_sum(_ptr(slots), n_slots, n_slots, 1, _ptr(out), st), "mnerf_lpips_sum")
+        if stream is not None:
+            slots.record_stream(stream)
+            out.record_stream(stream)
+    return out
+
+
+class LpipsWeights:
+    """The device-resident weights of ``lpips_vgg``: 13 x (wstream, bias, ew) in network order and the 5 head vectors, with the
+    by-pointer table ``mnerf_lpips_vgg`` takes.  ``layers``: 13 (wstream float32 numpy / tensor from gmflow.pack_conv_blocks, bias
+    [c_out], ew); ``heads``: 5 vectors.  (metrics.DeviceLPIPS builds one from the two weight files.)"""
+
+    def __init__(self, layers, heads, device):
+        import torch
+        lib = load()
+        if len(layers) != LPIPS_LAYERS or len(heads) != LPIPS_STAGES:
+            raise MnerfError(f"LpipsWeights: {len(layers)} layers and {len(heads)} heads, expected {LPIPS_LAYERS} and {LPIPS_STAGES}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise MnerfError(f"LpipsWeights: the HIP kernels need a CUDA device, got {self.device} (there is no CPU fallback)")
+        if self.device.index is None:  # "cuda": the current device, by its index (tensors report theirs)
+            self.device = _current_device()
+        to_dev = lambda a: torch.as_tensor(np.asarray(a, np.float32) if not torch.is_tensor(a) else a.detach().float()).contiguous().to(self.device)
+        self.table = LpipsWeightTable()
+        self.tensors = []
+        for l, (ws, bias, ew) in enumerate(layers):
+            ws, bias = to_dev(ws).reshape(-1), to_dev(bias).reshape(-1)
+            if ws.numel() != lib.mnerf_lpips_wstream_floats(l):
+                raise MnerfError(f"LpipsWeights: layer {l} has a stream of {ws.numel()} words, expected {lib.mnerf_lpips_wstream_floats(l)}")
+            self.tensors += [ws, bias]
+            self.table.wstream[l], self.table.bias[l], self.table.ew[l] = ws.data_ptr(), bias.data_ptr(), int(ew)
+        for l, hw in enumerate(heads):
+            hw = to_dev(hw).reshape(-1)
+            self.tensors.append(hw)
+            self.table.head[l] = hw.data_ptr()
+
+
+def lpips_workspace_bytes(n_images, height, width, masked):
+    """bytes of the workspace of ``lpips_vgg`` (mnerf_lpips_workspace_bytes; -1: no image, or a processed image below 16 x 16)"""
+    return int(load().mnerf_lpips_workspace_bytes(int(n_images), int(height), int(width), int(bool(masked))))
+
+
+def lpips_vgg(pred, gt, invalid_mask, weights, workspace=None, stream=None):
+    """LPIPS (VGG-16 variant, ``metrics.LPIPSVGG``) of a batch of frames on the device (mnerf_lpips_vgg): ``pred`` [B, H*W, 3], ``gt``
+    [B, 3, H, W], ``invalid_mask`` [B, H, W] bool / uint8 or None - exactly the arguments of ``image_metrics`` -, ``weights`` an
+    ``LpipsWeights``.  With a mask the masked pixels are zeroed in both images, without one the 80 % centre crop is scored.
+    -> float64 CUDA tensor [B].  ``workspace``: a uint8 CUDA tensor of at least ``lpips_workspace_bytes`` bytes to reuse, or None.
+    Everything is checked here, before any launch; CPU tensors raise (there is no CPU fallback)."""
+    import torch
+    lib = load()
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise MnerfError(f"lpips_vgg: {name} must be a CUDA tensor, got {getattr(t, 'device', type(t))} (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise MnerfError(f"lpips_vgg: {name} must be float32, got {t.dtype}")
+    if not isinstance(weights, LpipsWeights) or weights.device != pred.device:
+        raise MnerfError(f"lpips_vgg: weights must be an LpipsWeights on {pred.device}")
+    if gt.dim() != 4 or gt.shape[1] != 3:
+        raise MnerfError(f"lpips_vgg: gt must be [B, 3, H, W], got {tuple(gt.shape)}")
+    b, _, h, w = gt.shape
+    if tuple(pred.shape) != (b, h * w, 3) or pred.device != gt.device:
+        raise MnerfError(f"lpips_vgg: pred {tuple(pred.shape)} on {pred.device} does not match gt {tuple(gt.shape)} on {gt.device}: "
+                         f"expected [{b}, {h * w}, 3]")
+    if not pred.is_contiguous():
+        raise MnerfError("lpips_vgg: pred must be contiguous")
+    if b < 1 or b > 65535:
+        raise MnerfError(f"lpips_vgg: {b} images, the kernel takes 1..65535")
+    if gt.stride()[1:] != (h * w, w, 1):
+        raise MnerfError(f"lpips_vgg: every image of gt must be contiguous, got strides {gt.stride()}")
+    gt_stride = gt.stride(0) if b > 1 else 3 * h * w
+    if gt_stride < 3 * h * w:
+        raise MnerfError(f"lpips_vgg: gt's images overlap (batch stride {gt_stride})")
+    if invalid_mask is not None:
+        if not torch.is_tensor(invalid_mask) or invalid_mask.device != pred.device or invalid_mask.dtype not in (torch.bool, torch.uint8):
+            raise MnerfError("lpips_vgg: invalid_mask must be a bool or uint8 tensor on pred's device")
+        if tuple(invalid_mask.shape) != (b, h, w):
+            raise MnerfError(f"lpips_vgg: invalid_mask {tuple(invalid_mask.shape)}, expected [{b}, {h}, {w}]")
+        invalid_mask = invalid_mask.contiguous()
+        if invalid_mask.dtype == torch.bool:
+            invalid_mask = invalid_mask.view(torch.uint8)
+    n_bytes = lib.mnerf_lpips_workspace_bytes(b, h, w, int(invalid_mask is not None))
+    if n_bytes <= 0:
+        raise MnerfError(f"lpips_vgg: {h} x {w} images: the processed image (the whole frame with a mask, the 80 % centre crop without) "
+                         "must be at least 16 x 16")
+    if workspace is not None and (not torch.is_tensor(workspace) or workspace.device != pred.device or workspace.dtype != torch.uint8
+                                  or not workspace.is_contiguous() or workspace.numel() < n_bytes):
+        raise MnerfError(f"lpips_vgg: workspace must be a contiguous uint8 tensor of at least {n_bytes} bytes on {pred.device}")
+    with _on(pred.device, stream) as st:
+        if workspace is None:
+            workspace = torch.empty(n_bytes, dtype=torch.uint8, device=pred.device)
+        out = torch.empty(b, dtype=torch.float64, device=pred.device)
+        check(lib.mnerf_lpips_vgg(_ptr(pred), _ptr(gt), int(gt_stride), _ptr(invalid_mask), b, h, w, C.byref(weights.table),
+                                  _ptr(workspace), _ptr(out), st), "mnerf_lpips_vgg")
+        if stream is not None:
             workspace.record_stream(stream)
             out.record_stream(stream)
     return out

@@ -8,6 +8,12 @@ files it downloads (torchvision's ImageNet VGG-16 and the learned linear heads, 
 `LPIPSVGG` below restates the published network (Zhang et al. 2018, lpips v0.1 'vgg' variant) and loads those two files from
 where the user put them (`load_lpips`); PARITY UNPINNED — without the weights there is no number to compare, the tests check the
 structure against an independent functional evaluation with the files' key names and shapes.  `EvalTools` takes any callable.
+LPIPS on the device: `DeviceLPIPS` runs the same network through the HIP kernels (csrc/lpips.hip, `hip.lpips_vgg`: split-fp16
+convolutions with one power-of-two gain per tensor, fp64 heads) and `DeviceEval` carries its number as a fifth column, so that
+`Coach.test_model` keeps every frame on the device (`MNERF_DEVICE_LPIPS`, default 1).  It is checked against `LPIPSVGG` in float64
+on seeded random and layer-rescaled weights only (tests/test_lpips_gpu.py); the real weights have a wider per-channel range, and
+parity with the `lpips` package stays unpinned for both paths - tools/eval_time.py prints the device and the host value of the same
+frame side by side for a user who has the two files.
 PARITY (rest): PSNR is checked against the reference's formula; the SSIM restatement against a direct per-window evaluation of the
 published definition and against hand-derived closed-form vectors (tests/golden/ssim_hand_derived.json, generator
 tools/gen_ssim_golden.py; tests/test_datasets.py) — not against scikit-image itself, which this image does not have."""
@@ -109,25 +115,42 @@ def device_metrics_enabled():
     return os.environ.get("MNERF_DEVICE_METRICS", "1").lower() not in ("0", "off", "false", "no")
 
 
+def device_lpips_enabled():
+    """``MNERF_DEVICE_LPIPS`` (default 1, the spellings of ``MNERF_DEVICE_METRICS``): where ``Coach.test_model`` scores on the device
+    and the two LPIPS weight files are on disk, LPIPS comes from ``DeviceLPIPS`` (csrc/lpips.hip) as a fifth column of
+    ``DeviceEval``; 0 restores ``load_lpips`` behind ``EvalTools``: one host round trip per frame and library convolutions"""
+    import os
+    return os.environ.get("MNERF_DEVICE_LPIPS", "1").lower() not in ("0", "off", "false", "no")
+
+
 class DeviceEval:
     """Collects the [B,4] rows (PSNR dB, SSIM, MSE, kept pixels) of many batches on the device; ``finish()`` is the ONE copy to
-    the host.  Each batch has a key (its global index in the loader), so that the rows of several ranks can be merged in order."""
+    the host.  Each batch has a key (its global index in the loader), so that the rows of several ranks can be merged in order.
+    With a ``DeviceLPIPS`` every row gains a fifth column, the frame's LPIPS; without one the rows are exactly [B,4]."""
 
-    def __init__(self):
-        self.keys, self.rows = [], []
+    def __init__(self, lpips=None):
+        self.keys, self.rows, self.lpips = [], [], lpips
+
+    @property
+    def width(self):
+        return 4 if self.lpips is None else 5
 
     def add(self, key, pred, gt, invalid_mask=None):
         """``pred`` [B,H*W,3], ``gt`` [B,3,H,W], ``invalid_mask`` [B,H,W] or None: as ``hip.image_metrics``.  Enqueues, no sync."""
+        import torch
         from . import hip
-        self.rows.append(hip.image_metrics(pred, gt, invalid_mask))
+        row = hip.image_metrics(pred, gt, invalid_mask)
+        if self.lpips is not None:
+            row = torch.cat([row, self.lpips(pred, gt, invalid_mask)[:, None]], 1)
+        self.rows.append(row)
         self.keys.append(int(key))
 
     def finish(self):
-        """-> (keys int64 [n, 2], rows float64 [n, 4]) numpy arrays, one row per IMAGE in the order added; an image's key is (its
-        batch's key, its index within the batch)"""
+        """-> (keys int64 [n, 2], rows float64 [n, 4 or 5]) numpy arrays, one row per IMAGE in the order added; an image's key is
+        (its batch's key, its index within the batch)"""
         import torch
         if not self.rows:
-            return np.zeros((0, 2), np.int64), np.zeros((0, 4), np.float64)
+            return np.zeros((0, 2), np.int64), np.zeros((0, self.width), np.float64)
         keys = np.asarray([(k, i) for k, r in zip(self.keys, self.rows) for i in range(r.shape[0])], np.int64)
         rows = torch.cat(self.rows, 0).cpu().numpy()
         self.keys, self.rows = [], []
@@ -221,10 +244,10 @@ def _lpips_module():
     return LPIPSVGG
 
 
-def load_lpips(vgg16_path=None, lin_path=None, device="cpu"):
-    """-> callable `lpips_fn(pred, gt) -> float` on [H,W,3] float arrays in [0,1] (what `EvalTools(lpips_fn=...)` takes), built
-    from the two files the `lpips` package would have downloaded: torchvision's `vgg16-397923af.pth` (or any state dict with
-    `features.*` keys) and lpips v0.1's `vgg.pth`.  Paths default to $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN and torch hub's cache."""
+def lpips_state_dict(vgg16_path=None, lin_path=None):
+    """The state dict of ``LPIPSVGG`` from the two files the `lpips` package would have downloaded: torchvision's
+    `vgg16-397923af.pth` (or any state dict with `features.*` keys) and lpips v0.1's `vgg.pth`.  Paths default to
+    $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN and torch hub's cache; a missing file raises FileNotFoundError."""
     import os
     import torch
     hub = os.path.join(os.path.expanduser(os.environ.get("TORCH_HOME", "~/.cache/torch")), "hub", "checkpoints")
@@ -234,10 +257,17 @@ def load_lpips(vgg16_path=None, lin_path=None, device="cpu"):
         if not os.path.isfile(path):
             raise FileNotFoundError(f"LPIPS: {what} not found at {path}; there is no network here — copy the file and point "
                                     "MNERF_LPIPS_VGG16 / MNERF_LPIPS_LIN at it (the reference downloads both through the lpips package)")
-    net = _lpips_module()()
     sd = {k: v for k, v in torch.load(vgg16_path, map_location="cpu", weights_only=True).items() if k.startswith("features.")}
     sd.update(torch.load(lin_path, map_location="cpu", weights_only=True))
-    net.load_state_dict(sd, strict=True)
+    return sd
+
+
+def load_lpips(vgg16_path=None, lin_path=None, device="cpu"):
+    """-> callable `lpips_fn(pred, gt) -> float` on [H,W,3] float arrays in [0,1] (what `EvalTools(lpips_fn=...)` takes), built
+    from the two files of ``lpips_state_dict``."""
+    import torch
+    net = _lpips_module()()
+    net.load_state_dict(lpips_state_dict(vgg16_path, lin_path), strict=True)
     net = net.to(device).eval()
 
     @torch.no_grad()
@@ -246,3 +276,47 @@ def load_lpips(vgg16_path=None, lin_path=None, device="cpu"):
         return float(net(to_t(pred), to_t(gt)).item())
 
     return lpips_fn
+
+
+def pack_lpips(state_dict):
+    """``LPIPSVGG`` state dict -> (13 x (wstream, bias, ew) in network order, 5 head vectors) as numpy arrays for
+    ``hip.LpipsWeights``: every convolution as the split-fp16 fragment streams of its blocks of 128 output channels
+    (gmflow.pack_conv_blocks; the first layer's 3 input channels zero-padded to 32)."""
+    from .gmflow import pack_conv_blocks
+    get = lambda k: np.asarray(state_dict[k].detach().cpu().numpy() if hasattr(state_dict[k], "detach") else state_dict[k], np.float32)
+    layers = []
+    for i in sorted(LPIPS_VGG_CONVS):
+        ws, ew = pack_conv_blocks(get(f"features.{i}.weight"))
+        layers.append((ws, get(f"features.{i}.bias"), ew))
+    heads = [get(f"lin{l}.model.1.weight").reshape(-1) for l in range(len(LPIPS_CHANNELS))]
+    return layers, heads
+
+
+def lpips_stage_sizes(h, w):
+    """the five feature-map sizes of a [h, w] network input: four 2x2 pools with floor sizes, as F.max_pool2d"""
+    return [(h >> l, w >> l) for l in range(len(LPIPS_CHANNELS))]
+
+
+class DeviceLPIPS:
+    """LPIPS on the device: the two weight files (``lpips_state_dict``: the path rules and the FileNotFoundError of ``load_lpips``)
+    packed ONCE on the host into the 13 weight streams, and one workspace per (batch, frame size, masked) kept across calls.
+    ``__call__(pred, gt, invalid_mask)`` takes the arguments of ``hip.image_metrics`` and returns a float64 CUDA tensor [B]; it
+    enqueues and does not synchronise.  ``state_dict``: use these weights instead of the files."""
+
+    def __init__(self, device, vgg16_path=None, lin_path=None, state_dict=None):
+        from . import hip
+        sd = state_dict if state_dict is not None else lpips_state_dict(vgg16_path, lin_path)
+        self.weights = hip.LpipsWeights(*pack_lpips(sd), device=device)
+        self.workspaces = {}
+
+    def __call__(self, pred, gt, invalid_mask=None):
+        import torch
+        from . import hip
+        b, _, h, w = gt.shape
+        key = (int(b), int(h), int(w), invalid_mask is not None)
+        if key not in self.workspaces:
+            n_bytes = hip.lpips_workspace_bytes(*key)
+            if n_bytes <= 0:
+                raise hip.MnerfError(f"DeviceLPIPS: {h} x {w} frames are too small: the processed image must be at least 16 x 16")
+            self.workspaces[key] = torch.empty(n_bytes, dtype=torch.uint8, device=self.weights.device)
+        return hip.lpips_vgg(pred, gt, invalid_mask, self.weights, workspace=self.workspaces[key])

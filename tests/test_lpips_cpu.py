@@ -1,0 +1,177 @@
+"""Host side of LPIPS on the device, without a GPU: the names added under ABI 12 in header, binding and library, the workspace
+helper and the argument checks of mnerf_lpips_vgg (they precede any launch), the block-wise weight stream of a 512-channel layer
+against the numpy fragment emulation, the floor rule of the stage sizes, the MNERF_DEVICE_LPIPS switch and DeviceEval without
+LPIPS."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import REPO
+from matchnerf_amd import gmflow, hip, metrics
+
+NEW = ("mnerf_lpips_wstream_floats", "mnerf_lpips_workspace_bytes", "mnerf_lpips_vgg", "mnerf_maxpool2x2", "mnerf_lpips_head_slots",
+       "mnerf_lpips_head", "mnerf_lpips_sum")
+
+
+def test_header_binding_and_library_agree_on_the_new_names_under_abi_12():
+    lib = hip.load()
+    header = open(os.path.join(REPO, "include", "mnerf.h")).read()
+    assert hip.MNERF_ABI_VERSION == 12 == lib.mnerf_abi_version()
+    assert int(re.search(r"#define MNERF_ABI_VERSION (\d+)", header).group(1)) == 12
+    declared = set(re.findall(r"\b(mnerf_[a-z_0-9]+)\s*\(", header))
+    for name in NEW:
+        assert name in declared and name in hip.EXPORTS and hasattr(lib, name), name
+    assert "lpips.hip" in __import__("matchnerf_amd.csrc.build", fromlist=["SOURCES"]).SOURCES
+    assert lib.mnerf_struct_size(10) == ctypes.sizeof(hip.LpipsWeightTable) == (13 + 13 + 5) * 8 + 13 * 4 + 4
+    shapes = [metrics.LPIPS_VGG_CONVS[i] for i in sorted(metrics.LPIPS_VGG_CONVS)]
+    for l, (ci, co) in enumerate(shapes):  # the first layer reads 32 stored channels
+        assert lib.mnerf_lpips_wstream_floats(l) == lib.mnerf_conv_wstream_floats(max(ci, 32), co, 3) == 9 * (max(ci, 32) // 16) * (co // 32) * 512
+    assert lib.mnerf_lpips_wstream_floats(13) == 0 == lib.mnerf_lpips_wstream_floats(-1)
+
+
+def test_workspace_helper():
+    size = hip.load().mnerf_lpips_workspace_bytes
+    assert size(1, 64, 80, 0) > 0 and size(1, 64, 80, 0) % 16 == 0
+    assert size(1, 512, 640, 1) > size(1, 512, 640, 0) > size(1, 64, 80, 1) > size(1, 64, 80, 0) > size(1, 20, 20, 0)
+    # the rule (include/mnerf.h): two activation buffers shared by all pairs + a fixed amount per image
+    for args in ((64, 80, 0), (37, 50, 1), (512, 640, 0)):
+        per_image = size(2, *args) - size(1, *args)
+        assert 0 < per_image < size(1, *args)
+        assert size(3, *args) == size(1, *args) + 2 * per_image and size(7, *args) == size(1, *args) + 6 * per_image
+    # the processed image must be 16 x 16: without a mask the crop of 19 rows keeps 17, of 18 keeps 16, of 17 keeps 15
+    assert size(1, 19, 40, 0) > 0 and size(1, 18, 40, 0) > 0 and size(1, 40, 18, 0) > 0
+    assert size(1, 17, 40, 0) == -1 and size(1, 40, 17, 0) == -1
+    assert size(1, 16, 40, 1) > 0 and size(1, 15, 40, 1) == -1 and size(1, 40, 15, 1) == -1
+    for bad in ((0, 64, 64, 0), (-1, 64, 64, 1), (1, 0, 0, 0), (1, -5, 40, 1)):
+        assert size(*bad) == -1, bad
+    assert hip.lpips_workspace_bytes(2, 64, 80, True) == size(2, 64, 80, 1)
+
+
+def test_argument_checks_precede_any_launch():
+    """made-up, aligned, non-NULL pointers never reach a kernel"""
+    lib = hip.load()
+    fn = lib.mnerf_lpips_vgg
+    p = 1 << 20
+    tab = hip.LpipsWeightTable()
+    for l in range(13):
+        tab.wstream[l], tab.bias[l], tab.ew[l] = p, p, 0
+    for l in range(5):
+        tab.head[l] = p
+    t = ctypes.byref(tab)
+    n20 = 3 * 20 * 20
+    assert fn(None, p, n20, None, 1, 20, 20, t, p, p, None) == hip.MNERF_E_NULL
+    assert fn(p, None, n20, None, 1, 20, 20, t, p, p, None) == hip.MNERF_E_NULL
+    assert fn(p, p, n20, None, 1, 20, 20, None, p, p, None) == hip.MNERF_E_NULL
+    assert fn(p, p, n20, None, 1, 20, 20, t, None, p, None) == hip.MNERF_E_NULL
+    assert fn(p, p, n20, None, 1, 20, 20, t, p, None, None) == hip.MNERF_E_NULL
+    tab.bias[7] = None
+    assert fn(p, p, n20, None, 1, 20, 20, t, p, p, None) == hip.MNERF_E_NULL
+    assert b"layer 7" in lib.mnerf_last_error()
+    tab.bias[7] = p
+    tab.head[4] = None
+    assert fn(p, p, n20, None, 1, 20, 20, t, p, p, None) == hip.MNERF_E_NULL
+    tab.head[4] = p
+    assert fn(p, p, n20, None, 0, 20, 20, t, p, p, None) == hip.MNERF_E_RANGE            # no image
+    assert fn(p, p, 3 * 17 * 40, None, 1, 17, 40, t, p, p, None) == hip.MNERF_E_RANGE    # the crop keeps 15 rows
+    assert fn(p, p, 3 * 15 * 40, p, 1, 15, 40, t, p, p, None) == hip.MNERF_E_RANGE       # 15 rows with a mask
+    assert fn(p, p, n20 - 1, None, 2, 20, 20, t, p, p, None) == hip.MNERF_E_RANGE        # overlapping images of gt
+    assert fn(p, p, n20, None, 1, 20, 20, t, p + 8, p, None) == hip.MNERF_E_ALIGN
+    assert fn(p, p, n20, None, 1, 20, 20, t, p, p + 4, None) == hip.MNERF_E_ALIGN
+    tab.wstream[3] = p + 4
+    assert fn(p, p, n20, None, 1, 20, 20, t, p, p, None) == hip.MNERF_E_ALIGN
+    assert lib.mnerf_lpips_head(None, p, p, 64, 5, 7, p, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_lpips_head(p, p, p, 0, 5, 7, p, None) == hip.MNERF_E_RANGE
+    assert lib.mnerf_lpips_head(p, p, p, 64, 5, 7, p + 4, None) == hip.MNERF_E_ALIGN
+    assert lib.mnerf_lpips_sum(None, 3, 3, 1, p, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_lpips_sum(p, 2, 3, 1, p, None) == hip.MNERF_E_RANGE
+    assert lib.mnerf_maxpool2x2(None, p, 4, 8, 8, None) == hip.MNERF_E_NULL
+    assert lib.mnerf_maxpool2x2(p, p, -1, 8, 8, None) == hip.MNERF_E_RANGE
+    assert lib.mnerf_lpips_head_slots(5, 7) == 1 and lib.mnerf_lpips_head_slots(9, 12) == 2 and lib.mnerf_lpips_head_slots(0, 7) == -1
+    with pytest.raises(hip.MnerfError):  # the binding: no CPU fallback
+        hip.lpips_vgg(torch.rand(1, 400, 3), torch.rand(1, 3, 20, 20), None, None)
+    with pytest.raises(hip.MnerfError):
+        hip.maxpool2x2(torch.rand(2, 8, 8))
+    with pytest.raises(hip.MnerfError):
+        hip.LpipsWeights([], [], "cpu")
+
+
+def _unpack_block(ws, rows, k_total, ew):
+    """numpy emulation of the fragment addressing (tests/test_conv.py): hi + lo of one block's stream -> [rows, k_total]"""
+    halfs = ws.view(np.float16).reshape(k_total // 16, rows // 32, 2, 64, 8).astype(np.float64)
+    lane = np.arange(64)
+    mat = np.zeros((rows, k_total))
+    for s in range(k_total // 16):
+        for m in range(rows // 32):
+            v = (halfs[s, m, 0] + halfs[s, m, 1]) * 2.0 ** -ew   # [64, 8]
+            for j in range(8):
+                mat[32 * m + (lane & 31), 16 * s + 8 * (lane >> 5) + j] = v[:, j]
+    return mat
+
+
+def test_a_512_channel_weight_packs_block_wise():
+    rng = np.random.default_rng(512)
+    w = (rng.standard_normal((512, 512, 3, 3)) * np.sqrt(2.0 / (512 * 9))).astype(np.float32)
+    ws, ew = gmflow.pack_conv_blocks(w)
+    lib = hip.load()
+    assert ws.size == lib.mnerf_lpips_wstream_floats(12) == 4 * lib.mnerf_conv_wstream_floats(512, 128, 3)
+    want = w.transpose(0, 2, 3, 1).reshape(512, -1).astype(np.float64)
+    per = ws.size // 4
+    for b in range(4):
+        mat = _unpack_block(ws[b * per:(b + 1) * per], 128, 9 * 512, ew)
+        blk = want[128 * b:128 * (b + 1)]
+        # hi carries 11 bits and lo the next 11: |hi + lo - w| <= 2^-22 |w|, or half an fp16 subnormal step where lo underflows;
+        # both are below 2^-21 of the tensor's largest weight, the scale the one exponent ew is chosen for
+        assert np.abs(mat - blk).max() <= 2.0 ** -21 * np.abs(w).max(), b
+    # up to 128 output channels the stream is pack_conv's; 3 input channels are zero-padded to 32
+    w64 = (rng.standard_normal((64, 64, 3, 3)) * 0.1).astype(np.float32)
+    a, b = gmflow.pack_conv_blocks(w64), gmflow.pack_conv(w64)
+    assert a[1] == b[1] and (a[0].view(np.uint32) == b[0].view(np.uint32)).all()
+    w3 = (rng.standard_normal((64, 3, 3, 3)) * 0.3).astype(np.float32)
+    ws3, ew3 = gmflow.pack_conv_blocks(w3)
+    assert ws3.size == lib.mnerf_lpips_wstream_floats(0)
+    mat3 = _unpack_block(ws3, 64, 9 * 32, ew3).reshape(64, 9, 32)
+    assert (mat3[:, :, 3:] == 0).all()
+    assert np.abs(mat3[:, :, :3] - w3.transpose(0, 2, 3, 1).reshape(64, 9, 3)).max() <= 2.0 ** -21 * np.abs(w3).max()
+
+
+def test_stage_sizes_follow_the_floor_rule():
+    assert metrics.lpips_stage_sizes(32, 42) == [(32, 42), (16, 21), (8, 10), (4, 5), (2, 2)]
+    for h, w in ((32, 42), (37, 50), (52, 64), (16, 16), (410, 512)):
+        x, got = torch.zeros(1, 1, h, w), []
+        for _ in range(5):
+            got.append(tuple(x.shape[2:]))
+            if min(x.shape[2:]) >= 2:
+                x = F.max_pool2d(x, 2, 2)
+        assert metrics.lpips_stage_sizes(h, w) == got
+
+
+def test_the_switch_reads_the_environment(monkeypatch):
+    monkeypatch.delenv("MNERF_DEVICE_LPIPS", raising=False)
+    assert metrics.device_lpips_enabled()
+    for v, want in (("0", False), ("off", False), ("false", False), ("no", False), ("1", True), ("on", True)):
+        monkeypatch.setenv("MNERF_DEVICE_LPIPS", v)
+        assert metrics.device_lpips_enabled() == want
+
+
+def test_device_eval_without_lpips_is_unchanged_and_the_files_are_found_by_one_rule(tmp_path, monkeypatch):
+    keys, rows = metrics.DeviceEval().finish()
+    assert keys.shape == (0, 2) and rows.shape == (0, 4)
+    assert metrics.DeviceEval().lpips is None and metrics.DeviceEval().width == 4 and metrics.DeviceEval(lpips=object()).width == 5
+    monkeypatch.setenv("MNERF_LPIPS_VGG16", str(tmp_path / "no_vgg.pth"))
+    monkeypatch.setenv("MNERF_LPIPS_LIN", str(tmp_path / "no_lin.pth"))
+    with pytest.raises(FileNotFoundError, match="torchvision VGG-16 weights"):
+        metrics.load_lpips()
+    with pytest.raises(FileNotFoundError, match="torchvision VGG-16 weights"):
+        metrics.DeviceLPIPS("cuda")  # the files are looked for before anything touches a device
+    # packing: 13 layers in network order, 5 heads
+    net = metrics._lpips_module()()
+    layers, heads = metrics.pack_lpips(net.state_dict())
+    assert len(layers) == 13 and [len(h) for h in heads] == list(metrics.LPIPS_CHANNELS)
+    lib = hip.load()
+    assert [l[0].size for l in layers] == [lib.mnerf_lpips_wstream_floats(i) for i in range(13)]
+    assert [l[1].size for l in layers] == [metrics.LPIPS_VGG_CONVS[i][1] for i in sorted(metrics.LPIPS_VGG_CONVS)]
