@@ -45,6 +45,9 @@
  *       Added under v12 without a layout change: LPIPS on the device (matchnerf_amd/csrc/lpips.hip) - the table mnerf_lpips_weights - struct
  *       index 10 -, mnerf_lpips_wstream_floats, mnerf_lpips_workspace_bytes, mnerf_lpips_vgg, mnerf_maxpool2x2, mnerf_lpips_head_slots,
  *       mnerf_lpips_head, mnerf_lpips_sum; mnerf_conv2d accepts c_out 256 / 512 (blocks of 128 output channels).
+ *       Added under v12 WITH a layout change of mnerf_rays (tgt_height / tgt_width appended before the pad: the offsets of the older
+ *       fields are unchanged, sizeof grows by 8) and one export, mnerf_box_downsample.  The version number stays 12; a binding built
+ *       against the older layout is caught by mnerf_struct_size(1), which every binding is expected to compare before its first call.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -86,11 +89,11 @@ typedef struct mnerf_view {
 typedef struct mnerf_rays {
   int32_t n_rays;         /* rays in this chunk                                               */
   int32_t n_samples;      /* S = opt.nerf.sample_intvs                                        */
-  int32_t ray_begin;      /* first pixel index (row-major y*W+x) when ray_idx == NULL          */
+  int32_t ray_begin;      /* first pixel index (row-major y*tgt_width+x) when ray_idx == NULL  */
   int32_t legacy_coord;   /* opt.nerf.legacy_coord: integer pixel centres, i/(S-1) depths      */
   int32_t depth_inverse;  /* opt.nerf.depth.param == "inverse"                                 */
-  int32_t height, width;  /* image size of the views                                          */
-  const int32_t* ray_idx; /* device, [n_rays] pixel indices (train / test-optim), or NULL      */
+  int32_t height, width;  /* image size of the SOURCE views (scene->images, the normalisation of projected coordinates) */
+  const int32_t* ray_idx; /* device, [n_rays] pixel indices of the target grid (train / test-optim), or NULL */
   const float* strat_u;   /* device, [n_rays, S] U[0,1) offsets (stratified train), or NULL    */
   float kinv[9];          /* inverse target intrinsics, fp32 (camera.py:221-222)              */
   float c2w[12];          /* target camera->world 3x4 (legacy: fp64 inverse cast to fp32,      */
@@ -105,6 +108,14 @@ typedef struct mnerf_rays {
    * (staged form) where mnerf_render_takes_pose_table() returns 1; MNERF_E_UNSUPPORTED everywhere else. */
   const float* pose_table;
   int32_t rays_per_pose;
+  /* TARGET GRID: the pixel grid the rays are cast through, which need not be the source views' (a fly-through at another
+   * resolution, a preview, a crop, a supersampled frame: kinv belongs to this grid).  Pixel indices - ray_begin, ray_idx, the
+   * frames of a pose table (rays_per_pose = tgt_height * tgt_width is the caller's business) - decode with tgt_width; height /
+   * width above keep describing the source images.  0, 0 = the views' size.  Both zero or both >= 1 (MNERF_E_RANGE otherwise);
+   * with ray_idx == NULL and no pose table, ray_begin >= 0 and ray_begin + n_rays <= tgt_height * tgt_width.  Every entry point
+   * works on a copy with the zeros replaced.  Forward entry points only: mnerf_cost_volume_backward answers
+   * MNERF_E_UNSUPPORTED to a target grid that differs from the views' size. */
+  int32_t tgt_height, tgt_width;
   int32_t pad_;
 } mnerf_rays;
 #define MNERF_POSE_FLOATS 24
@@ -261,6 +272,13 @@ int mnerf_render_chunk(const mnerf_scene* scene, const mnerf_decoder* dec, const
 int mnerf_render_chunk_fused(const mnerf_scene* scene, const mnerf_decoder* dec, const mnerf_rays* rays,
                              float* rgb, float* depth, float* opacity, void* stream);
 
+/* Box filter of a supersampled frame: src [k*h, k*w, channels] fp32 row-major (what a render chunk sequence leaves for one frame:
+ * channels = 3 for rgb, 1 for depth / opacity) -> dst [h, w, channels].  Each output value is the sum of its k x k block taken in
+ * row-major order with sequential fp32 additions, multiplied by fp32(1 / (k*k)): a fixed order, so that a float32 restatement on
+ * the host gives the same bits.  1 <= k <= 8, channels in {1, 3}, h, w >= 0 (MNERF_E_RANGE otherwise).  Enqueue-only, one thread
+ * per output value.  Replaces nothing in the reference, which renders at the views' size only. */
+int mnerf_box_downsample(const float* src, int32_t h, int32_t w, int32_t channels, int32_t k, float* dst, void* stream);
+
 /* Backward kernels of the ray chunk (training through the HIP path; reference: autograd through the eager chain,
  * coach.py:215-243).
  * K5 backward — given d(rgb [R,3], depth [R] or NULL, opacity [R] or NULL) and the forward's per-sample inputs,
@@ -272,7 +290,8 @@ int mnerf_composite_backward(int32_t n_rays, int32_t n_samples, const float* rgb
 /* K1+K2 backward — g_cond [n_rays*S, cond_stride] (gradient of mnerf_cost_volume's rows; only the cosine
  * entries are read) is scattered into the feature-map gradients g_feat0 / g_feat1 (layouts of scene->feat[0] /
  * feat[1]; ACCUMULATED with atomic adds: the caller zero-fills them; g_feat1 may be NULL when n_scales == 1).
- * The forward interpolation is recomputed from `scene` and `rays` (query_cond_info, matchnerf.py:209-293). */
+ * The forward interpolation is recomputed from `scene` and `rays` (query_cond_info, matchnerf.py:209-293).  Training renders at
+ * the views' size: a rays->tgt_height / tgt_width that differs from it is MNERF_E_UNSUPPORTED. */
 int mnerf_cost_volume_backward(const mnerf_scene* scene, const mnerf_rays* rays, int32_t cond_stride,
                                const float* g_cond, float* g_feat0, float* g_feat1, void* stream);
 

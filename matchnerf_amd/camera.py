@@ -32,3 +32,33 @@ def target_ray_consts(extr34, intr33, legacy=True):
 def pair_list(n_views):
     """Ordered view pairs (a<b) (gmflow.py:49, matchnerf.py:194)."""
     return [(a, b) for a in range(n_views - 1) for b in range(a + 1, n_views)]
+
+
+def resize_intrinsics(K, src_hw, tgt_hw, legacy=True):
+    """Intrinsics of the same field of view on another pixel grid: ``K`` [..., 3, 3] (numpy or torch) of a ``src_hw`` = (H, W)
+    frame -> those of a ``tgt_hw`` = (h', w') frame, with sx = w'/W, sy = h'/H:
+
+    non-legacy (pixel centres at +0.5, the frame spans [0, W]):      diag(sx, sy, 1) @ K
+    legacy (integer pixel centres, the frame spans [-0.5, W - 0.5]):  [[sx, 0, 0.5 sx - 0.5], [0, sy, 0.5 sy - 0.5], [0, 0, 1]] @ K
+
+    The product is written out row by row (the matrix has two entries per row), in K's own dtype: a host copy and a device copy of
+    K give the same bits.  The identity size returns ``K`` itself."""
+    (src_h, src_w), (tgt_h, tgt_w) = (int(v) for v in src_hw), (int(v) for v in tgt_hw)
+    if min(src_h, src_w, tgt_h, tgt_w) < 1:
+        raise ValueError(f"resize_intrinsics: frame sizes {src_hw} -> {tgt_hw}")
+    if (src_h, src_w) == (tgt_h, tgt_w):
+        return K
+    sx, sy = tgt_w / src_w, tgt_h / src_h
+    ox, oy = (0.5 * sx - 0.5, 0.5 * sy - 0.5) if legacy else (0.0, 0.0)
+    if torch.is_tensor(K):
+        out = K.clone()
+    else:
+        K = np.asarray(K)
+        out = K.copy()
+        sx, sy, ox, oy = (K.dtype.type(v) for v in (sx, sy, ox, oy))
+    out[..., 0, :] = K[..., 0, :] * sx
+    out[..., 1, :] = K[..., 1, :] * sy
+    if legacy:
+        out[..., 0, :] += K[..., 2, :] * ox
+        out[..., 1, :] += K[..., 2, :] * oy
+    return out

@@ -523,8 +523,13 @@ class Coach:
                 break
             var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
             gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
-            var = self.model(var, mode=mode)
             b, _, _, h, w = var.images.shape
+            # scored against a ground truth of the batch's size: the option nerf.render_hw (videos) is not read here, and a batch
+            # that names another grid cannot be scored
+            if tuple(int(v) for v in var.get("tgt_hw", (h, w))) != (h, w):
+                raise ValueError(f"evaluation: batch.tgt_hw={tuple(var.tgt_hw)} differs from the ground truth's size {(h, w)}")
+            var.tgt_hw = (h, w)
+            var = self.model(var, mode=mode)
             depth = mask_of(gt_depth)
             frames = None
             if dev is None or on_frame is not None or lpips_fn is not None:
@@ -637,7 +642,8 @@ class Coach:
         interpolate, llff: spiral; white background for blender), written under <output_path>/test_videos/<set>/ as the reference
         names them: `<scene>_view<tgt>_src<ids>.gif` at 12 fps when nerf.save_gif, `..._f<i>.jpg` frames when nerf.save_frames, and
         the strip of source views `<name>.jpg` (PIL instead of imageio; the reference's .mp4 needs scikit-video / ffmpeg, neither in
-        this image, and is skipped).  Returns {set: frames [F,H,W,3] uint8 of its FIRST batch element}."""
+        this image, and is skipped).  Frames have the rendered size: the views', or nerf.render_hw (optionally
+        supersampled: nerf.render_ssaa).  Returns {set: frames [F,h,w,3] uint8 of its FIRST batch element}."""
         from PIL import Image
         self.model.eval()
         out_root = os.path.join(self.opts.output_path, "test_videos")
@@ -669,9 +675,10 @@ class Coach:
                     warnings.warn("test_model_video: vis_depth (depth maps next to the frames, coach.py:497-505) and the .mp4 "
                                   "container (skvideo, coach.py:511-525) are not written: frames / GIF / source strip only")
                     self._warned_vis_depth = True
+                b = var.images.shape[0]
+                h, w = self.model.target_grid(var, "test", self.model.extract_poses(var)[0], var.images.shape[-2:])[1]  # nerf.render_hw
                 var = self.model(var, mode="test", render_video=True, render_path_mode=mode)
-                b, _, _, h, w = var.images.shape
-                # forward returns the reference's frame-major layout [n_frames * B, HW, 3]
+                # forward returns the reference's frame-major layout [n_frames * B, h*w, 3] at the rendered size
                 frames = (var.rgb.reshape(n_frames, b, h, w, 3).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
                 for bi in range(b):
                     clip = frames[:, bi]

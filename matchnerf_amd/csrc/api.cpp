@@ -39,6 +39,21 @@ extern "C" int64_t mnerf_struct_size(int32_t which) {
   }
 }
 
+int mnerf_rays_canonical(const mnerf_rays* rays, mnerf_rays* out, const char* who) {
+  MNERF_REQUIRE(rays, MNERF_E_NULL, "%s: rays is NULL", who);
+  *out = *rays;
+  MNERF_REQUIRE(rays->tgt_height >= 0 && rays->tgt_width >= 0 && (rays->tgt_height == 0) == (rays->tgt_width == 0), MNERF_E_RANGE,
+                "%s: target grid %dx%d (both 0 = the views' size, or both >= 1)", who, rays->tgt_height, rays->tgt_width);
+  if (rays->tgt_height == 0) out->tgt_height = rays->height, out->tgt_width = rays->width;
+  MNERF_REQUIRE(out->tgt_height >= 1 && out->tgt_width >= 1, MNERF_E_RANGE, "%s: target grid %dx%d", who, out->tgt_height,
+                out->tgt_width);
+  if (!rays->ray_idx && !rays->pose_table && rays->n_rays > 0)
+    MNERF_REQUIRE(rays->ray_begin >= 0 && (long long)rays->ray_begin + rays->n_rays <= (long long)out->tgt_height * out->tgt_width,
+                  MNERF_E_RANGE, "%s: pixels [%d, %d + %d) outside the %dx%d target grid", who, rays->ray_begin, rays->ray_begin,
+                  rays->n_rays, out->tgt_height, out->tgt_width);
+  return MNERF_OK;
+}
+
 // ---- debug / tuning knobs: the environment is read ONCE, when the library is loaded (a static initialiser), into a
 // table that launches only read (mnerf_debug_set_knob below is the one writer, for tests).  Nothing in a launch path calls getenv or keeps mutable state; the only
 // per-process bookkeeping left is "has this kernel's LDS attribute been set on this device" (mnerf_once_per_device).

@@ -371,10 +371,17 @@ __global__ __launch_bounds__(256, CVB_WALK_WAVES) void cost_volume_backward_walk
   }
 }
 
-extern "C" int mnerf_cost_volume_backward(const mnerf_scene* scene, const mnerf_rays* rays, int32_t cond_stride,
+extern "C" int mnerf_cost_volume_backward(const mnerf_scene* scene, const mnerf_rays* rays_in, int32_t cond_stride,
                                           const float* g_cond, float* g_feat0, float* g_feat1, void* stream) {
-  int rc = mnerf_scene_check(scene, rays, "mnerf_cost_volume_backward");
+  mnerf_rays canon;
+  int rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_cost_volume_backward");
   if (rc) return rc;
+  const mnerf_rays* rays = &canon;
+  rc = mnerf_scene_check(scene, rays, "mnerf_cost_volume_backward");
+  if (rc) return rc;
+  MNERF_REQUIRE(rays->tgt_height == rays->height && rays->tgt_width == rays->width, MNERF_E_UNSUPPORTED,
+                "mnerf_cost_volume_backward: target grid %dx%d differs from the views' %dx%d (training renders at the views' size)",
+                rays->tgt_height, rays->tgt_width, rays->height, rays->width);
   MNERF_REQUIRE(g_cond && g_feat0 && (scene->n_scales < 2 || g_feat1), MNERF_E_NULL,
                 "mnerf_cost_volume_backward: NULL buffer");
   MNERF_REQUIRE(!rays->pose_table, MNERF_E_UNSUPPORTED, "mnerf_cost_volume_backward: pose tables are inference-only");

@@ -50,6 +50,9 @@ struct mnerf_tuning {
 mnerf_tuning mnerf_tune();  // a snapshot (api.cpp: copied under the table lock)
 // true exactly once per (mask, current HIP device): guards hipFuncSetAttribute, which is per device
 bool mnerf_once_per_device(std::atomic<unsigned long long>& mask);
+// *out = *rays with the target grid made explicit (tgt_height / tgt_width = height / width where the caller left them 0) after
+// the range checks of include/mnerf.h "TARGET GRID"; the kernels read tgt_* unconditionally (api.cpp)
+int mnerf_rays_canonical(const mnerf_rays* rays, mnerf_rays* out, const char* who);
 // argument checks of the scene / rays structs (cost_volume.hip)
 int mnerf_scene_check(const mnerf_scene* sc, const mnerf_rays* rays, const char* who);
 // fused ray-chunk form (decoder_fused.hip), used by mnerf_render_chunk (render_chunk.hip)
@@ -107,8 +110,8 @@ __device__ __forceinline__ void rays_for_pose(mnerf_rays& Rt, const mnerf_rays& 
 
 __device__ __forceinline__ RayGeom make_ray(const mnerf_rays& R, int ray_local) {
   int pix = R.ray_idx ? R.ray_idx[ray_local] : (R.ray_begin + ray_local);
-  int py = pix / R.width;
-  int px = pix - py * R.width;
+  int py = pix / R.tgt_width;  // the target grid (a canonical copy: never 0), not the source views' R.width
+  int px = pix - py * R.tgt_width;
   float off = R.legacy_coord ? 0.0f : 0.5f;
   float x = (float)px + off, y = (float)py + off;
   // cam = [x y 1] @ Kinv^T   (img2cam, camera.py:221-222)

@@ -102,3 +102,39 @@ extern "C" int mnerf_composite(int32_t n_rays, int32_t n_samples, const float* r
                      rgb, depth, opacity, prob);
   return mnerf_check_launch("mnerf_composite");
 }
+
+// Box filter of a supersampled frame (include/mnerf.h): dst [h, w, C] <- src [k h, k w, C], one thread per output value.  The k x k
+// block is summed in row-major order with sequential additions and scaled by fp32(1 / k^2) - additions only, so there is nothing
+// for the compiler to contract, and a float32 restatement on the host reproduces the bits.  Consecutive threads take consecutive
+// output values: a wave reads k runs of 64 k (channels interleaved) floats per block row.  Bandwidth-bound: the frame is read once.
+__global__ __launch_bounds__(256) void box_downsample_kernel(const float* __restrict__ src, int h, int w, int C, int k,
+                                                             float inv_area, float* __restrict__ dst) {
+  const long long total = (long long)h * w * C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int row_vals = w * C;
+  const int y = (int)(i / row_vals), xc = (int)(i - (long long)y * row_vals);
+  const int x = xc / C, c = xc - x * C;
+  const long long src_row = (long long)k * row_vals;  // floats per source row
+  const float* p = src + (long long)y * k * src_row + (long long)x * k * C + c;
+  float acc = p[0];
+  for (int dy = 0; dy < k; ++dy)
+    for (int dx = (dy == 0 ? 1 : 0); dx < k; ++dx) acc = acc + p[dy * src_row + dx * C];
+  dst[i] = acc * inv_area;
+}
+
+extern "C" int mnerf_box_downsample(const float* src, int32_t h, int32_t w, int32_t channels, int32_t k, float* dst,
+                                    void* stream) {
+  MNERF_REQUIRE(h >= 0 && w >= 0, MNERF_E_RANGE, "mnerf_box_downsample: frame %dx%d", h, w);
+  MNERF_REQUIRE(k >= 1 && k <= 8, MNERF_E_RANGE, "mnerf_box_downsample: k=%d outside [1,8]", k);
+  MNERF_REQUIRE(channels == 1 || channels == 3, MNERF_E_RANGE, "mnerf_box_downsample: channels=%d not in {1,3}", channels);
+  const long long total = (long long)h * w * channels;
+  MNERF_REQUIRE(total * k * k < (1ll << 31) * 256, MNERF_E_RANGE, "mnerf_box_downsample: frame %dx%dx%d x %d^2 too large", h, w,
+                channels, k);
+  if (total == 0) return MNERF_OK;  // empty frame: nothing to read or write
+  MNERF_REQUIRE(src && dst, MNERF_E_NULL, "mnerf_box_downsample: NULL buffer");
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(box_downsample_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, h, w, channels, k,
+                     1.0f / (float)(k * k), dst);
+  return mnerf_check_launch("mnerf_box_downsample");
+}

@@ -522,9 +522,13 @@ bool mnerf_cost_volume_takes_pose_table(const mnerf_scene* scene) {
   return variant == 3 && !uvpair;
 }
 
-extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* rays,
+extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* rays_in,
                                  int32_t cond_stride, float* cond, void* stream) {
-  int rc = mnerf_scene_check(scene, rays, "mnerf_cost_volume");
+  mnerf_rays canon;
+  int rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_cost_volume");
+  if (rc) return rc;
+  const mnerf_rays* rays = &canon;
+  rc = mnerf_scene_check(scene, rays, "mnerf_cost_volume");
   if (rc) return rc;
   MNERF_REQUIRE(cond, MNERF_E_NULL, "mnerf_cost_volume: cond is NULL");
   int sumG = scene->n_group[0] + (scene->n_scales > 1 ? scene->n_group[1] : 0);

@@ -516,7 +516,8 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: the depth index and
   const int n = lane & 31, half = lane >> 5;                                                      //  what derives from it stay scalar)
   const int S = R.n_samples, V = sc.n_views, NS = sc.n_scales;
-  const int W = R.width, H = R.height;
+  const int W = R.tgt_width, H = R.tgt_height;  // the TARGET grid: what tiles and pixel indices decode with
+  const int Ws = R.width, Hs = R.height;        // the SOURCE views: coordinate normalisation, taps and stride of sc.images
   const int items = V * NS;
   const CvmLayout L = cvm_layout(sc);
   const float* gain = reinterpret_cast<const float*>(opnd);
@@ -546,7 +547,7 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
   const int ray_geo = pix - R.ray_begin;                                           // make_ray: pixel = ray_begin + ray
   const int ray = max(0, min(ray_geo, R.n_rays - 1));                              // rows / stratified offsets: a ray of the launch
   const bool row_wr = grid.stage_rows || (px < W && py < H && ray_geo >= 0 && ray_geo < R.n_rays);  // direct rows: live rays only
-  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
+  const float wm1 = (float)(Ws - 1), hm1 = (float)(Hs - 1);
   const int G0 = sc.n_group[0], G1 = NS > 1 ? sc.n_group[1] : 0;
   const int sumG = G0 + G1;
   const int n_pairs = V * (V - 1) / 2;
@@ -573,8 +574,8 @@ __global__ __launch_bounds__(64 * CVM_WG_WAVES, CVM_WAVES_PER_SIMD) void cost_vo
       project(sc.views[v], wx, wy, wz, wm1, hm1, u, w_, z);
       uv[v * 32 + n] = make_float2(u, w_);
       if (row_wr && first_block) {  // (a later pair block only needs the projections)
-        const Bilin b = bilin_setup(u, w_, H, W);
-        const float4* img = reinterpret_cast<const float4*>(sc.images) + (size_t)v * H * W;
+        const Bilin b = bilin_setup(u, w_, Hs, Ws);
+        const float4* img = reinterpret_cast<const float4*>(sc.images) + (size_t)v * Hs * Ws;
         const float4 t00 = img[b.o00], t01 = img[b.o01], t10 = img[b.o10], t11 = img[b.o11];
         const float gx = u * 2.0f - 1.0f, gy = w_ * 2.0f - 1.0f;
         const float m = (gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f) ? 1.0f : 0.0f;
@@ -812,7 +813,7 @@ bool mnerf_cost_volume_mm_applies(const mnerf_scene* scene, const mnerf_rays* ra
 
 int mnerf_cost_volume_mm_launch(const mnerf_scene* scene, const mnerf_rays* rays, int cond_stride, float* cond, void* stream) {
   MNERF_REQUIRE(mnerf_aligned16(scene->feat_op), MNERF_E_ALIGN, "mnerf_cost_volume: feat_op not 16B aligned");
-  const int W = rays->width;
+  const int W = rays->tgt_width;  // (a canonical copy: mnerf_cost_volume) tiles cover the target grid
   const int row_first = rays->ray_begin / W, row_last = (rays->ray_begin + rays->n_rays - 1) / W;
   CvmGrid g;
   g.tile_y0 = row_first / 4;

@@ -1318,10 +1318,13 @@ bool mnerf_decoder_takes_pose_table(const mnerf_decoder* dec, int n_samples) {
 }
 
 extern "C" int mnerf_decoder_chunk(const mnerf_decoder* dec, const mnerf_view* view0,
-                                   const mnerf_rays* rays, const float* cond, float* rgb,
+                                   const mnerf_rays* rays_in, const float* cond, float* rgb,
                                    float* depth, float* opacity, float* dbg_rgb_s,
                                    float* dbg_sigma, void* stream) {
-  MNERF_REQUIRE(dec && view0 && rays, MNERF_E_NULL, "mnerf_decoder_chunk: NULL argument struct");
+  MNERF_REQUIRE(dec && view0 && rays_in, MNERF_E_NULL, "mnerf_decoder_chunk: NULL argument struct");
+  mnerf_rays canon;
+  if (const int rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_decoder_chunk")) return rc;
+  const mnerf_rays* rays = &canon;
   MNERF_REQUIRE(rgb && depth && opacity && cond, MNERF_E_NULL, "mnerf_decoder_chunk: NULL buffer");
   MNERF_REQUIRE(rays->legacy_coord == 0 || rays->n_samples >= 2, MNERF_E_RANGE,
                 "mnerf_decoder_chunk: legacy depth sampling needs S >= 2");
@@ -1339,7 +1342,7 @@ extern "C" int mnerf_decoder_samples(const mnerf_decoder* dec, int32_t n_rays, i
   mnerf_rays rays = {};
   rays.n_rays = n_rays;
   rays.n_samples = n_samples;
-  rays.height = rays.width = 2;
+  rays.height = rays.width = rays.tgt_height = rays.tgt_width = 2;
   rays.legacy_coord = legacy_coord ? 1 : 0;  // here it only selects the positional-encoding frequency factor (1 | pi)
   const mnerf_view none = {};
   MNERF_REQUIRE(cond, MNERF_E_NULL, "mnerf_decoder_samples: cond is NULL");

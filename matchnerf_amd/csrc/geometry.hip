@@ -11,7 +11,7 @@ __global__ __launch_bounds__(256) void ray_samples_kernel(mnerf_rays R, mnerf_vi
                                                           float* __restrict__ ndc,
                                                           float* __restrict__ depth) {
   const long long total = (long long)R.n_rays * R.n_samples;
-  const float wm1 = (float)(R.width - 1), hm1 = (float)(R.height - 1);
+  const float wm1 = (float)(R.width - 1), hm1 = (float)(R.height - 1);  // the SOURCE view's size
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int ray = (int)(i / R.n_samples);
@@ -36,9 +36,11 @@ __global__ __launch_bounds__(256) void ray_samples_kernel(mnerf_rays R, mnerf_vi
   }
 }
 
-extern "C" int mnerf_ray_samples(const mnerf_rays* rays, const mnerf_view* view, float* pts,
+extern "C" int mnerf_ray_samples(const mnerf_rays* rays_in, const mnerf_view* view, float* pts,
                                  float* ndc, float* depth, void* stream) {
-  MNERF_REQUIRE(rays, MNERF_E_NULL, "mnerf_ray_samples: rays is NULL");
+  mnerf_rays canon;
+  if (const int rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_ray_samples")) return rc;
+  const mnerf_rays* rays = &canon;
   MNERF_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 1, MNERF_E_RANGE,
                 "mnerf_ray_samples: n_rays=%d S=%d", rays->n_rays, rays->n_samples);
   MNERF_REQUIRE(!ndc || view, MNERF_E_NULL, "mnerf_ray_samples: view required for ndc output");

@@ -43,10 +43,14 @@ extern "C" int32_t mnerf_render_takes_pose_table(const mnerf_scene* scene, const
 }
 
 extern "C" int mnerf_render_chunk_fused(const mnerf_scene* scene, const mnerf_decoder* dec,
-                                        const mnerf_rays* rays, float* rgb, float* depth,
+                                        const mnerf_rays* rays_in, float* rgb, float* depth,
                                         float* opacity, void* stream) {
-  int rc = check_render_args(scene, dec, rays);
+  int rc = check_render_args(scene, dec, rays_in);
   if (rc) return rc;
+  mnerf_rays canon;
+  rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_render_chunk_fused");
+  if (rc) return rc;
+  const mnerf_rays* rays = &canon;
   MNERF_REQUIRE(rgb && depth && opacity, MNERF_E_NULL, "mnerf_render_chunk_fused: NULL output buffer");
   MNERF_REQUIRE(mnerf_fused_render_applies(scene, dec, rays), MNERF_E_UNSUPPORTED,
                 "mnerf_render_chunk_fused: the one-launch form needs the split-fp16 stream, S <= 128, <= 32 conditioning "
@@ -57,10 +61,14 @@ extern "C" int mnerf_render_chunk_fused(const mnerf_scene* scene, const mnerf_de
 }
 
 extern "C" int mnerf_render_chunk(const mnerf_scene* scene, const mnerf_decoder* dec,
-                                  const mnerf_rays* rays, void* workspace, float* rgb,
+                                  const mnerf_rays* rays_in, void* workspace, float* rgb,
                                   float* depth, float* opacity, void* stream) {
-  int rc = check_render_args(scene, dec, rays);
+  int rc = check_render_args(scene, dec, rays_in);
   if (rc) return rc;
+  mnerf_rays canon;  // (the two launches below canonicalise again: idempotent)
+  rc = mnerf_rays_canonical(rays_in, &canon, "mnerf_render_chunk");
+  if (rc) return rc;
+  const mnerf_rays* rays = &canon;
   MNERF_REQUIRE(rgb && depth && opacity, MNERF_E_NULL, "mnerf_render_chunk: NULL output buffer");
   if (mnerf_tune().render_fused && mnerf_fused_render_applies(scene, dec, rays))
     return mnerf_render_chunk_fused(scene, dec, rays, rgb, depth, opacity, stream);

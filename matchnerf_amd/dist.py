@@ -147,7 +147,7 @@ def _source_features(model, ref_images, encoder):
 def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
     """BASELINE config[3], row-tile form: every rank renders its contiguous band of rows of the target view through the HIP
     path, and ONE all_gather returns the [rays_local, 5] tiles (rgb, depth, opacity) to all ranks.  -> edict(rgb [B,HW,3],
-    depth [B,HW,1], opacity [B,HW,1]), identical on every rank and bit-identical to the unsharded ``model.render`` from the
+    depth [B,HW,1], opacity [B,HW,1]) of the target grid (``model.target_grid``: the views' size unless the batch or the options name another), identical on every rank and bit-identical to the unsharded ``model.render`` from the
     same feature maps (rays are independent; tests/test_dist_gpu.py).  ``encoder``: "recompute" - every rank encodes the
     (replicated) source views itself; "shared" - the ranks split the encoder (``encode_shared``, inference only)."""
     from .edict import EasyDict as edict
@@ -158,10 +158,11 @@ def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)
     tgt_pose, ref_poses = model.extract_poses(batch)
-    b, _, _, h, w = ref_images.shape
+    b = ref_images.shape[0]
+    tgt_pose, (h, w), ssaa = model.target_grid(batch, mode, tgt_pose, ref_images.shape[-2:])  # rows of the TARGET grid are split
     first, n = shard_rows(h, w, rank, world)
     out = model.render(model.opts, tgt_pose, ray_range=(first, n), mode=mode, ref_poses=ref_poses, ref_images=ref_images,
-                       ref_feats_list=feats)
+                       ref_feats_list=feats, tgt_hw=(h, w), ssaa=ssaa)
     tile = torch.cat([out.rgb, out.depth, out.opacity], -1).permute(1, 0, 2).reshape(n, b * 5)   # rows = rays
     full = gather_tiles(tile, [shard_rows(h, w, r, world)[1] for r in range(world)])
     full = full.reshape(h * w, b, 5).permute(1, 0, 2)
@@ -170,7 +171,8 @@ def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
 
 def render_views_sharded(model, batch, poses, mode="test", encoder="shared"):
     """BASELINE config[3] as the reference runs it: ONE source set (``batch``'s source views and cameras) and a list of target
-    ``poses`` (dicts of extrinsics / intrinsics / near_fars, e.g. a ``model.get_video_rendering_path`` result).  The poses are
+    ``poses`` (dicts of extrinsics / intrinsics / near_fars, e.g. a ``model.get_video_rendering_path`` result; their intrinsics are
+    the batch's target camera's, which ``model.target_grid`` moves to ``nerf.render_hw`` where that option applies).  The poses are
     split contiguously over the ranks (``shard_range``), each rank renders its own full frames with ``model.render``, and one
     ragged all_gather of [n_local_poses * B * HW, 5] returns them.  -> the reference's frame-major edict(rgb [F*B, HW, 3],
     depth [F*B, HW, 1], opacity [F*B, HW, 1]) (matchnerf.py:62-70), identical on every rank.  ``encoder``: as in
@@ -183,12 +185,15 @@ def render_views_sharded(model, batch, poses, mode="test", encoder="shared"):
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)
     _, ref_poses = model.extract_poses(batch)
-    b, _, _, h, w = ref_images.shape
+    b = ref_images.shape[0]
+    h, w = model.target_grid(batch, mode, None, ref_images.shape[-2:])[1]  # frames of the TARGET grid are gathered
     spans = [shard_range(len(poses), r, world) for r in range(world)]
     first, n = spans[rank]
     frames = []
     for pose in poses[first:first + n]:
-        out = model.render(model.opts, pose, mode=mode, ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=feats)
+        pose, tgt_hw, ssaa = model.target_grid(batch, mode, pose, ref_images.shape[-2:])
+        out = model.render(model.opts, pose, mode=mode, ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=feats,
+                           tgt_hw=tgt_hw, ssaa=ssaa)
         frames.append(torch.cat([out.rgb, out.depth, out.opacity], -1))   # [B, HW, 5]
     local = torch.stack(frames, 0).reshape(n * b * h * w, 5) if frames else ref_images.new_zeros((0, 5))
     full = gather_tiles(local, [c * b * h * w for _, c in spans]).reshape(len(poses) * b, h * w, 5)

@@ -38,7 +38,8 @@ class Rays(C.Structure):
                 ("legacy_coord", C.c_int32), ("depth_inverse", C.c_int32), ("height", C.c_int32),
                 ("width", C.c_int32), ("ray_idx", C.c_void_p), ("strat_u", C.c_void_p),
                 ("kinv", C.c_float * 9), ("c2w", C.c_float * 12), ("near_", C.c_float), ("far_", C.c_float),
-                ("pose_table", C.c_void_p), ("rays_per_pose", C.c_int32), ("pad_", C.c_int32)]
+                ("pose_table", C.c_void_p), ("rays_per_pose", C.c_int32), ("tgt_height", C.c_int32),
+                ("tgt_width", C.c_int32), ("pad_", C.c_int32)]
 
 
 class Scene(C.Structure):
@@ -152,6 +153,7 @@ SIGNATURES = {
     "mnerf_render_takes_pose_table": (_i32, [_P(Scene), _P(Decoder), _i32, _i32]),
     "mnerf_render_chunk": (_int, [_P(Scene), _P(Decoder), _P(Rays)] + [_vp] * 5),
     "mnerf_render_chunk_fused": (_int, [_P(Scene), _P(Decoder), _P(Rays)] + [_vp] * 4),
+    "mnerf_box_downsample": (_int, [_vp] + [_i32] * 4 + [_vp] * 2),
     "mnerf_composite_backward": (_int, [_i32] * 2 + [_vp] * 4 + [_i32] * 2 + [_vp] * 6),
     "mnerf_cost_volume_backward": (_int, [_P(Scene), _P(Rays), _i32] + [_vp] * 4),
     "mnerf_debug_set_knob": (_int, [C.c_char_p, _int, _P(_int)]),
@@ -284,10 +286,15 @@ def make_view(extr34, intr33, near, far):
 
 
 def make_rays(n_rays, n_samples, height, width, kinv, c2w, near, far, ray_begin=0, legacy=True,
-              depth_inverse=False, ray_idx_ptr=None, strat_u_ptr=None, pose_table_ptr=None, rays_per_pose=0):
-    """``pose_table_ptr`` / ``rays_per_pose``: several target poses in one launch (include/mnerf.h: POSE TABLE; rows from
+              depth_inverse=False, ray_idx_ptr=None, strat_u_ptr=None, pose_table_ptr=None, rays_per_pose=0, tgt_hw=None):
+    """``height`` / ``width``: the SOURCE views' size.  ``tgt_hw`` = (h, w): the pixel grid of the target the rays are cast through
+    (``kinv``, ``ray_begin`` and a ``ray_idx`` list belong to it); None leaves the fields 0 = the views' size (include/mnerf.h:
+    TARGET GRID).
+    ``pose_table_ptr`` / ``rays_per_pose``: several target poses in one launch (include/mnerf.h: POSE TABLE; rows from
     ``pose_table_rows``); kinv / c2w / near / far are then ignored (pass those of any pose)."""
     r = Rays()
+    if tgt_hw is not None:
+        r.tgt_height, r.tgt_width = int(tgt_hw[0]), int(tgt_hw[1])
     r.pose_table = pose_table_ptr
     r.rays_per_pose = int(rays_per_pose) if pose_table_ptr else 0
     r.n_rays, r.n_samples, r.ray_begin = int(n_rays), int(n_samples), int(ray_begin)
@@ -381,6 +388,22 @@ def composite(rgb_s, sigma, depth_s, ray_len=None, wo_render_interval=True, setb
     if want_prob:
         return rgb, depth, opacity, prob
     return rgb, depth, opacity
+
+
+def box_downsample(src, h, w, k, stream=None):
+    """Box filter of a supersampled frame on the device (mnerf_box_downsample): src [k*h, k*w, C] or [k*h*k*w, C] fp32, C in
+    {1, 3} (what ``render`` returns per batch element) -> [h, w, C].  Block sums in row-major order, times fp32(1 / k^2)."""
+    import torch
+    lib = load()
+    _f32c(src, "src")
+    h, w, k = int(h), int(w), int(k)
+    c = int(src.shape[-1])
+    if src.numel() != k * h * k * w * c:
+        raise MnerfError(f"box_downsample: src {tuple(src.shape)} is not a [{k}*{h}, {k}*{w}, {c}] frame")
+    dst = torch.empty(h, w, c, device=src.device)
+    with _on(src.device, stream) as st:
+        check(lib.mnerf_box_downsample(_ptr(src), h, w, c, k, _ptr(dst), st), "mnerf_box_downsample")
+    return dst
 
 
 def composite_backward(rgb_s, sigma, depth_s, g_rgb, g_depth=None, g_opacity=None, ray_len=None,

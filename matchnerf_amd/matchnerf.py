@@ -78,10 +78,14 @@ class MatchNeRF(torch.nn.Module):
         self._frame = None  # the launch context below never outlives one forward (see _frame_ctx)
         self._cv_ops = None
         ref_images = batch.images[:, :self.n_src_views]
-        ref_feats_list = self.get_img_feat(ref_images, attn_splits_list=self.opts.encoder.attn_splits_list,
-                                           cur_n_src_views=self.n_src_views)
         tgt_pose, ref_poses = self.extract_poses(batch)
         batch_size, _, _, img_h, img_w = ref_images.shape
+        tgt_pose, tgt_hw, ssaa = self.target_grid(batch, mode, tgt_pose, (img_h, img_w))  # the outputs are [B, h*w, C] of this grid
+        if mode == "train" and (tgt_hw != (img_h, img_w) or ssaa != 1):  # (before the first launch)
+            raise NotImplementedError(f"mode='train' renders at the views' size {(img_h, img_w)}, not at {tgt_hw} x ssaa {ssaa}: "
+                                      "the ground truth has the batch's size")
+        ref_feats_list = self.get_img_feat(ref_images, attn_splits_list=self.opts.encoder.attn_splits_list,
+                                           cur_n_src_views=self.n_src_views)
 
         if render_video:
             assert mode in ["test", "val"], f"Do NOT render video in mode {mode}, change to either 'test' or 'val'."
@@ -95,8 +99,8 @@ class MatchNeRF(torch.nn.Module):
         if render_video and self.pose_batching:
             # small frames: as many poses per launch as fill one (mnerf_rays.pose_table); None where the kernels or the
             # frame size do not take a table -> the pose loop below
-            frames = self.render_poses(self.opts, poses_paths, ref_poses=ref_poses, ref_images=ref_images,
-                                       ref_feats_list=ref_feats_list)
+            frames = None if ssaa > 1 else self.render_poses(self.opts, poses_paths, ref_poses=ref_poses, ref_images=ref_images,
+                                                             ref_feats_list=ref_feats_list, tgt_hw=tgt_hw)
             if frames is not None:
                 for k, v in frames.items():  # [n_poses, B, N, C] -> the reference's frame-major [n_poses * B, N, C]
                     host = torch.empty((v.shape[0] * v.shape[1],) + tuple(v.shape[2:]), dtype=v.dtype, pin_memory=True)
@@ -108,13 +112,13 @@ class MatchNeRF(torch.nn.Module):
             if mode_rand_rays and mode in ["train", "test-optim"]:
                 batch.ray_idx = torch.randperm(img_h * img_w, device=ref_images.device)[:mode_rand_rays // batch_size]
                 ret = self.render(self.opts, cur_tgt_pose, ray_idx=batch.ray_idx, mode=mode, ref_poses=ref_poses,
-                                  ref_images=ref_images, ref_feats_list=ref_feats_list)
+                                  ref_images=ref_images, ref_feats_list=ref_feats_list, tgt_hw=tgt_hw, ssaa=ssaa)
             elif mode_rand_rays:
                 ret = self.render_by_slices(self.opts, cur_tgt_pose, mode=mode, ref_poses=ref_poses,
-                                            ref_images=ref_images, ref_feats_list=ref_feats_list)
+                                            ref_images=ref_images, ref_feats_list=ref_feats_list, tgt_hw=tgt_hw, ssaa=ssaa)
             else:
                 ret = self.render(self.opts, cur_tgt_pose, mode=mode, ref_poses=ref_poses, ref_images=ref_images,
-                                  ref_feats_list=ref_feats_list)
+                                  ref_feats_list=ref_feats_list, tgt_hw=tgt_hw, ssaa=ssaa)
             if render_video:
                 # Frames go to the host as the reference's do (matchnerf.py:62-70, per-frame .cpu()), but without a
                 # host sync per frame: one pinned buffer per output holds all frames, each frame is an async copy
@@ -146,6 +150,52 @@ class MatchNeRF(torch.nn.Module):
         ref_poses = dict(extrinsics=batch.extrinsics[:, :-1, :3, :], intrinsics=batch.intrinsics[:, :-1],
                          near_fars=batch.near_fars[:, :-1])
         return tgt_pose, ref_poses
+
+    # ------------------------------------------------------------------ target grid
+    @staticmethod
+    def resize_pose(pose, src_hw, tgt_hw, legacy):
+        """``pose`` (dict of extrinsics / intrinsics / near_fars [+ "_host"]) with its intrinsics moved from a ``src_hw`` frame to
+        a ``tgt_hw`` frame of the same field of view (``camera.resize_intrinsics``)."""
+        if tuple(src_hw) == tuple(tgt_hw):
+            return pose
+        out = dict(pose)
+        out["intrinsics"] = camera.resize_intrinsics(pose["intrinsics"], src_hw, tgt_hw, legacy)
+        if "_host" in pose:
+            ex, it, nf = pose["_host"]
+            out["_host"] = (ex, camera.resize_intrinsics(it, src_hw, tgt_hw, legacy), nf)
+        return out
+
+    def target_grid(self, batch, mode, tgt_pose, src_hw):
+        """The pixel grid the target view is rendered on -> (tgt_pose, (h, w), ssaa).  The source views do not tie it down: the
+        radiance field is continuous and the source maps do not depend on the target's grid (mnerf_rays.tgt_height / tgt_width).
+          ``batch.tgt_hw`` = (h, w)   the caller's grid; ``batch.intrinsics[:, -1]`` already belongs to it;
+          ``nerf.render_hw`` = [h, w] (option, modes 'test' / 'val', when the batch names no grid): the batch's target camera at
+                                      another resolution - the intrinsics are ``camera.resize_intrinsics`` of the batch's;
+          neither                     the views' size.
+        ``ssaa`` (``batch.ssaa``, else the option ``nerf.render_ssaa`` in modes 'test' / 'val'; default 1): ``render`` casts k x k
+        rays per pixel and box-filters them on the device."""
+        src_hw = (int(src_hw[0]), int(src_hw[1]))
+        evaluating = mode in ("test", "val")
+        tgt_hw = batch.get("tgt_hw") if hasattr(batch, "get") else None
+        if tgt_hw is not None:
+            tgt_hw = (int(tgt_hw[0]), int(tgt_hw[1]))
+        else:
+            opt_hw = getattr(self.opts.nerf, "render_hw", None) if evaluating else None
+            if opt_hw:
+                if len(opt_hw) != 2:
+                    raise ValueError(f"nerf.render_hw={opt_hw!r}: expected height,width")
+                tgt_hw = (int(opt_hw[0]), int(opt_hw[1]))
+                if tgt_pose is not None:  # (None: the caller only wants the size)
+                    tgt_pose = self.resize_pose(tgt_pose, src_hw, tgt_hw, bool(self.opts.nerf.legacy_coord))
+            else:
+                tgt_hw = src_hw
+        ssaa = batch.get("ssaa") if hasattr(batch, "get") else None
+        if ssaa is None:
+            ssaa = (getattr(self.opts.nerf, "render_ssaa", None) if evaluating else None) or 1
+        ssaa = int(ssaa)
+        if min(tgt_hw) < 1 or not 1 <= ssaa <= 8:
+            raise ValueError(f"target grid {tgt_hw}, ssaa={ssaa}: sizes >= 1 and 1 <= ssaa <= 8")
+        return tgt_pose, tgt_hw, ssaa
 
     # ------------------------------------------------------------------ encoder (matchnerf.py:183-207)
     def get_img_feat(self, imgs, attn_splits_list=None, cur_n_src_views=3):
@@ -283,20 +333,27 @@ class MatchNeRF(torch.nn.Module):
 
     # ------------------------------------------------------------------ render (matchnerf.py:88-143)
     def render(self, opt, tgt_pose=None, ray_idx=None, mode=None, ref_poses=None, ref_images=None,
-               ref_feats_list=None, ray_range=None):
+               ref_feats_list=None, ray_range=None, tgt_hw=None, ssaa=1):
         """Rays of one target pose -> edict(rgb [B,N,3], depth [B,N,1], opacity [B,N,1]).
         ``ray_idx`` (LongTensor [N], shared by the batch) selects pixels; ``ray_range`` = (first pixel, count) a contiguous run of
-        pixels (a band of rows: dist.render_frame_sharded) that keeps the kernels of the full-frame path; neither = full image."""
+        pixels (a band of rows: dist.render_frame_sharded) that keeps the kernels of the full-frame path; neither = full image.
+        ``tgt_hw`` = (h, w): the pixel grid of the target (default: the source views'); ``tgt_pose``'s intrinsics, ``ray_idx`` and
+        ``ray_range`` belong to it.  ``ssaa`` = k > 1: k x k rays per pixel (the frame at (k h, k w), intrinsics resized once more),
+        box-filtered on the device (``hip.box_downsample``) - full frames and runs of whole rows."""
         if tgt_pose is None:
             raise Exception("Must provide tgt_pose.")
         if not ref_images.is_cuda:
             raise RuntimeError("MatchNeRF.render: the HIP render path needs CUDA tensors (no CPU fallback)")
         batch_size, _, _, img_h, img_w = ref_images.shape
+        tgt_h, tgt_w = (img_h, img_w) if tgt_hw is None else (int(tgt_hw[0]), int(tgt_hw[1]))
         device = ref_images.device
         n_samples = int(opt.nerf.sample_intvs)
         legacy = bool(opt.nerf.legacy_coord)
         assert ray_idx is None or ray_range is None
-        pix0, n_rays = (0, img_h * img_w) if ray_range is None else (int(ray_range[0]), int(ray_range[1]))
+        if int(ssaa) > 1:
+            return self._render_ssaa(opt, tgt_pose, int(ssaa), (tgt_h, tgt_w), ray_idx, ray_range, mode, ref_poses, ref_images,
+                                     ref_feats_list)
+        pix0, n_rays = (0, tgt_h * tgt_w) if ray_range is None else (int(ray_range[0]), int(ray_range[1]))
         if ray_idx is not None:
             n_rays = int(ray_idx.numel())
         idx32 = None if ray_idx is None else ray_idx.to(device=device, dtype=torch.int32).contiguous()
@@ -307,6 +364,9 @@ class MatchNeRF(torch.nn.Module):
                                                   any(p.requires_grad for p in dec_mod.parameters()))
         ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
         tgt_ex, tgt_in, tgt_nf = self._tgt_host(tgt_pose)
+        if (needs_grad or mode == "train") and (tgt_h, tgt_w) != (img_h, img_w):
+            raise NotImplementedError(f"a target grid {(tgt_h, tgt_w)} other than the views' {(img_h, img_w)} is inference only "
+                                      "(the backward kernels answer MNERF_E_UNSUPPORTED)")
         if needs_grad:
             if ray_range is not None:
                 ray_idx = torch.arange(pix0, pix0 + n_rays, device=device)
@@ -329,7 +389,7 @@ class MatchNeRF(torch.nn.Module):
                     m, n_samples, img_h, img_w, kinv, c2w, tgt_nf[b, 0], tgt_nf[b, 1], ray_begin=pix0 + c, legacy=legacy,
                     depth_inverse=(opt.nerf.depth.param == "inverse"),
                     ray_idx_ptr=None if idx32 is None else idx32[c:].data_ptr(),
-                    strat_u_ptr=None if strat is None else strat[c:].data_ptr())
+                    strat_u_ptr=None if strat is None else strat[c:].data_ptr(), tgt_hw=(tgt_h, tgt_w))
                 fused = self.fused_render and hip.render_is_fused(sc, dec, rays)
                 if ws is None and not fused:
                     ws = self._workspace(hip.render_workspace_bytes(chunk, n_samples, dec.cond_stride) // 4, device)
@@ -337,7 +397,24 @@ class MatchNeRF(torch.nn.Module):
                                  timer=self.kernel_timer, fused=fused)
         return edict(rgb=rgb, depth=depth, opacity=opacity)
 
-    def render_poses(self, opt, poses, ref_poses=None, ref_images=None, ref_feats_list=None):
+    def _render_ssaa(self, opt, tgt_pose, k, tgt_hw, ray_idx, ray_range, mode, ref_poses, ref_images, ref_feats_list):
+        """``render`` with k x k rays per pixel: rows [r0, r1) of the (h, w) frame are rows [k r0, k r1) of the (k h, k w) frame of the
+        same camera, rendered as one run of pixels and reduced per output by the box filter on the device, before anything is
+        copied or gathered."""
+        h, w = tgt_hw
+        if ray_idx is not None:
+            raise ValueError("render: ssaa > 1 renders full frames or runs of whole rows (ray_range), not a ray_idx list")
+        pix0, n = (0, h * w) if ray_range is None else (int(ray_range[0]), int(ray_range[1]))
+        if pix0 % w or n % w:
+            raise ValueError(f"render: ssaa > 1 needs a ray_range of whole rows, got ({pix0}, {n}) at width {w}")
+        rows = n // w
+        hi = self.render(opt, self.resize_pose(tgt_pose, (h, w), (k * h, k * w), bool(opt.nerf.legacy_coord)), mode=mode,
+                         ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=ref_feats_list,
+                         ray_range=(k * k * pix0, k * k * n), tgt_hw=(k * h, k * w))
+        return edict({key: torch.stack([hip.box_downsample(v[b], rows, w, k).reshape(n, -1) for b in range(v.shape[0])], 0)
+                      for key, v in hi.items()})
+
+    def render_poses(self, opt, poses, ref_poses=None, ref_images=None, ref_feats_list=None, tgt_hw=None):
         """Full frames of SEVERAL target poses of one source set (the video loop of matchnerf.py:42-71) with as many poses per
         launch as fit MAX_RAYS_PER_POSE_LAUNCH rays: the poses' camera constants travel as a table in HBM (mnerf_rays.pose_table,
         include/mnerf.h) instead of by value in the kernel arguments.  A 128 x 160 frame is 20 480 rays = 80 decoder tiles, a
@@ -348,7 +425,8 @@ class MatchNeRF(torch.nn.Module):
         128, a non-default decoder form: ``hip.render_takes_pose_table``)."""
         batch_size, _, _, img_h, img_w = ref_images.shape
         device = ref_images.device
-        n_pix = img_h * img_w
+        tgt_hw = (img_h, img_w) if tgt_hw is None else (int(tgt_hw[0]), int(tgt_hw[1]))
+        n_pix = tgt_hw[0] * tgt_hw[1]  # a pose's frame on the TARGET grid
         per_launch = MAX_RAYS_PER_POSE_LAUNCH // n_pix
         if per_launch < 2 or len(poses) < 2 or not ref_images.is_cuda or self.fused_render:
             return None
@@ -389,7 +467,7 @@ class MatchNeRF(torch.nn.Module):
                 g = min(per_launch, n_poses - p0)
                 rays = hip.make_rays(g * n_pix, n_samples, img_h, img_w, kinv, c2w, rows[b, 0, 21], rows[b, 0, 22],
                                      ray_begin=p0 * n_pix, legacy=legacy, depth_inverse=(opt.nerf.depth.param == "inverse"),
-                                     pose_table_ptr=table[b].data_ptr(), rays_per_pose=n_pix)
+                                     pose_table_ptr=table[b].data_ptr(), rays_per_pose=n_pix, tgt_hw=tgt_hw)
                 if contiguous_out:
                     outs = (rgb[p0:p0 + g, 0].reshape(-1, 3), depth[p0:p0 + g, 0].reshape(-1, 1),
                             opacity[p0:p0 + g, 0].reshape(-1, 1))
@@ -441,13 +519,14 @@ class MatchNeRF(torch.nn.Module):
         return edict(rgb=torch.stack([o[0] for o in outs], 0), depth=torch.stack([o[1] for o in outs], 0),
                      opacity=torch.stack([o[2] for o in outs], 0))
 
-    def render_by_slices(self, opt, tgt_pose, mode=None, ref_poses=None, ref_images=None, ref_feats_list=None):
+    def render_by_slices(self, opt, tgt_pose, mode=None, ref_poses=None, ref_images=None, ref_feats_list=None, tgt_hw=None,
+                         ssaa=1):
         """matchnerf.py:145-161.  The reference loops over ``rand_rays_<mode>``-sized slices to
         bound memory; the fused kernels have no such temporaries, so the full image is rendered
         in launches of up to MAX_RAYS_PER_LAUNCH rays (identical results, see module docstring)."""
         assert ref_images is not None, "Must provide the reference images for MatchNeRF."
         return self.render(opt, tgt_pose, ray_idx=None, mode=mode, ref_poses=ref_poses, ref_images=ref_images,
-                           ref_feats_list=ref_feats_list)
+                           ref_feats_list=ref_feats_list, tgt_hw=tgt_hw, ssaa=ssaa)
 
     # ------------------------------------------------------------------ API-compat helpers
     def sample_depth(self, opt, batch_size, num_rays, near_far, legacy=False, mode="train"):
