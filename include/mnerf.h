@@ -48,6 +48,8 @@
  *       Added under v12 WITH a layout change of mnerf_rays (tgt_height / tgt_width appended before the pad: the offsets of the older
  *       fields are unchanged, sizeof grows by 8) and one export, mnerf_box_downsample.  The version number stays 12; a binding built
  *       against the older layout is caught by mnerf_struct_size(1), which every binding is expected to compare before its first call.
+ *       Added under v12 without a layout change: mnerf_debug_launch_plan (which kernel instance a problem size selects, host only);
+ *       mnerf_debug_set_knob knows "wa_min4".
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -303,6 +305,26 @@ int mnerf_cost_volume_backward(const mnerf_scene* scene, const mnerf_rays* rays,
  * on a copy of the table, so a launch on another thread sees the value from before or after the call, never a torn table;
  * kernels already enqueued are not affected. */
 int mnerf_debug_set_knob(const char* name, int value, int* old_value);
+
+/* Test / diagnosis hook: the kernel instance that a launch of the given problem would select, from the very function the launch
+ * calls.  Host only: no device is touched and nothing is launched, so it answers on a machine without a GPU.  `what` names the
+ * dispatcher, `args` its n_args problem sizes, `plan` receives the selection (n_plan >= the number of values listed):
+ *   "conv2d"            c_in, c_out, ksize, stride, n_img, h_in, w_in, in_channels_last, upsample2x
+ *                       -> NMB, TPW, CL of conv_kernel<NMB, TPW, CL>, and the number of 128-channel blocks (grid.y)
+ *   "conv_gemm"         fwd (1: mnerf_conv2d_forward_f32, 0: mnerf_conv2d_backward_data), n_img, c_in, c_out, h_in, w_in, ksize, stride
+ *                       -> CIB, NB, TAIL, FWD of conv_gemm_kernel (TAIL: a source channel count that is no multiple of 8)
+ *   "conv_wgrad"        n_img, c_in, c_out, h_in, w_in, ksize, stride
+ *                       -> chunks, rows of dY per chunk (mnerf_conv2d_backward_weight and ..._f16x3 alike)
+ *   "instance_norm", "instance_norm_backward"   plane_size, aligned (1: all buffers 16-byte aligned)
+ *                       -> THREADS, VPT of the register-cached instance, or 0, 0 for the streaming kernel
+ *   "window_attention"  batch, h, w, num_splits
+ *                       -> 4 or 2: query waves per workgroup (every arithmetic of mnerf_window_attention and the pre-split /
+ *                          images forms take the same rule; it reads the knob "wa_min4")
+ * Returns MNERF_OK, MNERF_E_RANGE for an unknown name, a wrong count or a size out of range, MNERF_E_UNSUPPORTED for channel
+ * counts, filters or strides that the convolution entry points do not build.  The query answers the selection only: it does not
+ * repeat every argument check of the launch (buffers, alignment, workspace, layouts), so MNERF_OK is no promise that a launch of
+ * that problem is accepted. */
+int mnerf_debug_launch_plan(const char* what, const int64_t* args, int32_t n_args, int32_t* plan, int32_t n_plan);
 
 /* K3+K4 backward — gradients of the conditional MLP + ray transformer (CondNeRF.forward, cond_nerf.py:52-100;
  * MultiHeadAttention.forward, ray_transformer.py:29-79; what `loss.backward()` does to them in coach.py:215-243).

@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "launch_plan.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -100,7 +101,7 @@ extern "C" int mnerf_debug_set_knob(const char* name, int value, int* old_value)
   const Knob knobs[] = {{"decoder_pp", &g_tuning.decoder_pp}, {"decoder_pp_grid", &g_tuning.decoder_pp_grid},
                         {"decoder_pp_max_s", &g_tuning.decoder_pp_max_s}, {"decoder_grid", &g_tuning.decoder_grid},
                         {"cv_variant", &g_tuning.cv_variant}, {"cv_mm", &g_tuning.cv_mm}, {"cv_mm_spw", &g_tuning.cv_mm_spw}, {"cv_uvpair", &g_tuning.cv_uvpair}, {"cv_pair_block", &g_tuning.cv_pair_block}, {"cv_grid", &g_tuning.cv_grid},
-                        {"render_fused", &g_tuning.render_fused}};
+                        {"render_fused", &g_tuning.render_fused}, {"wa_min4", &g_tuning.wa_min4}};
   for (const Knob& k : knobs)
     if (name && strcmp(name, k.name) == 0) {
       if (old_value) *old_value = *k.slot;
@@ -108,6 +109,20 @@ extern "C" int mnerf_debug_set_knob(const char* name, int value, int* old_value)
       return MNERF_OK;
     }
   mnerf_set_error("mnerf_debug_set_knob: unknown knob '%s'", name ? name : "(null)");
+  return MNERF_E_RANGE;
+}
+
+// Test / diagnosis hook: which kernel instance a launch of the given problem would take.  The rules live next to their launches
+// (launch_plan.hpp lists them) and the launches call the same functions; nothing here touches the device.
+extern "C" int mnerf_debug_launch_plan(const char* what, const int64_t* args, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  MNERF_REQUIRE(what && args && plan, MNERF_E_NULL, "mnerf_debug_launch_plan: NULL argument");
+  struct Planner { const char* name; int (*fn)(const int64_t*, int32_t, int32_t*, int32_t); };
+  const Planner planners[] = {{"conv2d", mnerf_plan_conv2d}, {"conv_gemm", mnerf_plan_conv_gemm}, {"conv_wgrad", mnerf_plan_conv_wgrad},
+                              {"instance_norm", mnerf_plan_instance_norm}, {"instance_norm_backward", mnerf_plan_instance_norm},
+                              {"window_attention", mnerf_plan_window_attention}};
+  for (const Planner& p : planners)
+    if (strcmp(what, p.name) == 0) return p.fn(args, n_args, plan, n_plan);
+  mnerf_set_error("mnerf_debug_launch_plan: unknown dispatcher '%s'", what);
   return MNERF_E_RANGE;
 }
 

@@ -23,6 +23,7 @@
 // The VGG-16 of LPIPS (lpips.hip) runs its 3x3 convolutions here as well: 256 / 512 output channels as blocks of 128 along grid.y,
 // each block with its own weight stream, bias offset and output channel offset; for the widths above the block index is 0.
 #include "split_f16.hpp"
+#include "launch_plan.hpp"
 
 #define CONV_NW 4
 #define CONV_BUF_BYTES 36864u  // one LDS weight buffer (36 KiB: six K16-steps x three 32-row blocks)
@@ -338,15 +339,49 @@ extern "C" int64_t mnerf_conv_wstream_floats(int32_t c_in, int32_t c_out, int32_
   return (int64_t)ksize * ksize * (c_in / 16) * (c_out / 32) * (H16_UNIT_BYTES / 4);
 }
 
+// which conv_kernel<NMB, TPW, CL> a problem launches, and over how many 128-channel blocks (grid.y): the launch below and
+// mnerf_debug_launch_plan("conv2d") both read it from here
+struct ConvPlan { int nmb, tpw, cl, n_blk; };
+static ConvPlan conv_plan(int c_out, long long n_pix, bool channels_last) {
+  ConvPlan pl;
+  // c_out 256 / 512: blocks of 128 output channels along grid.y, each with its own weight stream (gmflow.pack_conv_blocks)
+  pl.n_blk = c_out > 128 ? c_out / 128 : 1;
+  pl.nmb = c_out / pl.n_blk / 32;
+  // two pixel tiles per wave share every weight fragment read; one tile per wave when that grid would leave CUs idle
+  pl.tpw = (n_pix + 255) / 256 >= 256 ? 2 : 1;
+  pl.cl = channels_last ? 1 : 0;
+  return pl;
+}
+static bool conv_built(int c_in, int c_out, int ksize, int stride) {
+  return c_in >= 32 && c_in % 32 == 0 && (c_out == 64 || c_out == 96 || c_out == 128 || c_out == 256 || c_out == 512) &&
+         (ksize == 1 || ksize == 3) && (stride == 1 || stride == 2);
+}
+static int conv_out_size(int in, int up, int ksize, int stride) { return ((in << up) + 2 * (ksize / 2) - ksize) / stride + 1; }
+
+// args: c_in, c_out, ksize, stride, n_img, h_in, w_in, in_channels_last, upsample2x -> plan: nmb, tpw, cl, n_blk
+int mnerf_plan_conv2d(const int64_t* a, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  const char* who = "mnerf_debug_launch_plan(conv2d)";
+  MNERF_REQUIRE(n_args == 9 && n_plan >= 4, MNERF_E_RANGE, "%s: takes 9 arguments and fills 4 values, got %d and %d", who, n_args, n_plan);
+  for (int i = 0; i < 9; ++i) MNERF_REQUIRE(a[i] >= 0 && a[i] <= 0x3fffffff, MNERF_E_RANGE, "%s: argument %d = %lld", who, i, (long long)a[i]);
+  MNERF_REQUIRE(conv_built((int)a[0], (int)a[1], (int)a[2], (int)a[3]), MNERF_E_UNSUPPORTED, "%s: c_in=%lld c_out=%lld ksize=%lld stride=%lld",
+                who, (long long)a[0], (long long)a[1], (long long)a[2], (long long)a[3]);
+  MNERF_REQUIRE(a[4] >= 1 && a[5] >= 1 && a[6] >= 1, MNERF_E_RANGE,
+                "%s: n_img=%lld h_in=%lld w_in=%lld", who, (long long)a[4], (long long)a[5], (long long)a[6]);
+  const int up = a[8] ? 1 : 0;
+  const long long n_pix = a[4] * conv_out_size((int)a[5], up, (int)a[2], (int)a[3]) * conv_out_size((int)a[6], up, (int)a[2], (int)a[3]);
+  const ConvPlan pl = conv_plan((int)a[1], n_pix, a[7] != 0);
+  MNERF_REQUIRE(!pl.cl || pl.nmb == 4, MNERF_E_UNSUPPORTED, "%s: channel-last input is built for c_out = 128 only", who);
+  plan[0] = pl.nmb, plan[1] = pl.tpw, plan[2] = pl.cl, plan[3] = pl.n_blk;
+  return MNERF_OK;
+}
+
 extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_channels_last, int32_t upsample2x,
                             const float* in_absmax, const float* add_bilinear2x, const float* add_channel_last,
                             float* out, int32_t out_layout, float* out_absmax, int32_t n_img, int32_t h_in,
                             int32_t w_in, void* stream) {
   const char* who = "mnerf_conv2d";
   MNERF_REQUIRE(cv, MNERF_E_NULL, "%s: cv is NULL", who);
-  MNERF_REQUIRE(cv->c_in >= 32 && cv->c_in % 32 == 0 && (cv->c_out == 64 || cv->c_out == 96 || cv->c_out == 128 || cv->c_out == 256 || cv->c_out == 512) &&
-                    (cv->ksize == 1 || cv->ksize == 3) && (cv->stride == 1 || cv->stride == 2),
-                MNERF_E_UNSUPPORTED, "%s: c_in=%d c_out=%d ksize=%d stride=%d (built: c_in %% 32 == 0, c_out 64/96/128/256/512, 1x1 / 3x3, stride 1 / 2)",
+  MNERF_REQUIRE(conv_built(cv->c_in, cv->c_out, cv->ksize, cv->stride), MNERF_E_UNSUPPORTED, "%s: c_in=%d c_out=%d ksize=%d stride=%d (built: c_in %% 32 == 0, c_out 64/96/128/256/512, 1x1 / 3x3, stride 1 / 2)",
                 who, cv->c_in, cv->c_out, cv->ksize, cv->stride);
   MNERF_REQUIRE(n_img >= 0 && h_in >= 1 && w_in >= 1, MNERF_E_RANGE, "%s: n_img=%d h_in=%d w_in=%d", who, n_img, h_in, w_in);
   MNERF_REQUIRE(cv->leaky_slope >= 0.0f, MNERF_E_RANGE, "%s: leaky_slope=%g", who, (double)cv->leaky_slope);
@@ -356,7 +391,7 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
   MNERF_REQUIRE(cv->wstream_floats == mnerf_conv_wstream_floats(cv->c_in, cv->c_out, cv->ksize), MNERF_E_RANGE,
                 "%s: wstream has %lld floats, expected %lld", who, (long long)cv->wstream_floats,
                 (long long)mnerf_conv_wstream_floats(cv->c_in, cv->c_out, cv->ksize));
-  const int up = upsample2x ? 1 : 0, pad = cv->ksize / 2;
+  const int up = upsample2x ? 1 : 0;
   ConvParams p;
   p.in = in;
   p.wstream = cv->wstream;
@@ -373,8 +408,8 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
   p.c_in = cv->c_in;
   p.h_in = h_in;
   p.w_in = w_in;
-  p.h_out = ((h_in << up) + 2 * pad - cv->ksize) / cv->stride + 1;
-  p.w_out = ((w_in << up) + 2 * pad - cv->ksize) / cv->stride + 1;
+  p.h_out = conv_out_size(h_in, up, cv->ksize, cv->stride);
+  p.w_out = conv_out_size(w_in, up, cv->ksize, cv->stride);
   MNERF_REQUIRE(!add_bilinear2x || (p.h_out % 2 == 0 && p.w_out % 2 == 0), MNERF_E_RANGE,
                 "%s: add_bilinear2x needs an even output size, got %dx%d", who, p.h_out, p.w_out);
   p.ksize = cv->ksize;
@@ -389,9 +424,9 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
                   (long long)n_img * p.si * 4);
   }
   p.ew = cv->ew;
-  // c_out 256 / 512: blocks of 128 output channels along grid.y, each with its own weight stream (gmflow.pack_conv_blocks)
-  const int n_blk = cv->c_out > 128 ? cv->c_out / 128 : 1;
-  const int nmb = cv->c_out / n_blk / 32, n_steps = cv->ksize * cv->ksize * (cv->c_in / 16);
+  const long long n_pix = (long long)n_img * p.h_out * p.w_out;
+  const ConvPlan pl = conv_plan(cv->c_out, n_pix, in_channels_last != 0);
+  const int n_blk = pl.n_blk, nmb = pl.nmb, tpw = pl.tpw, n_steps = cv->ksize * cv->ksize * (cv->c_in / 16);
   p.c_total = cv->c_out;
   p.wblock_floats = mnerf_conv_wstream_floats(cv->c_in, 32 * nmb, cv->ksize);
   MNERF_REQUIRE(n_blk == 1 || (out_layout == MNERF_CONV_OUT_NCHW && !in_channels_last && !add_bilinear2x && !add_channel_last), MNERF_E_UNSUPPORTED,
@@ -409,14 +444,11 @@ extern "C" int mnerf_conv2d(const mnerf_conv* cv, const float* in, int32_t in_ch
                 "%s: pair-major output needs an even number of images, got %d", who, n_img);
   MNERF_REQUIRE(!add_channel_last || (out_layout != MNERF_CONV_OUT_NCHW && mnerf_aligned16(add_channel_last)), MNERF_E_RANGE,
                 "%s: add_channel_last needs a channel-last output layout and a 16-byte aligned tile", who);
-  const long long n_pix = (long long)n_img * p.h_out * p.w_out;
-  // two pixel tiles per wave share every weight fragment read; one tile per wave when that grid would leave CUs idle
-  const int tpw = (n_pix + 255) / 256 >= 256 ? 2 : 1;
   const long long per_wg = 32 * tpw * CONV_NW;
   const dim3 grid((unsigned)((n_pix + per_wg - 1) / per_wg), (unsigned)n_blk);
   const size_t lds = 2 * CONV_BUF_BYTES;
   hipStream_t st = (hipStream_t)stream;
-  const bool cl = in_channels_last != 0;
+  const bool cl = pl.cl != 0;
   MNERF_REQUIRE(!cl || nmb == 4, MNERF_E_UNSUPPORTED, "%s: channel-last input is built for c_out = 128 only", who);
 #define CONV_CASE(NMB, TPW, CLV)                                                                                      \
   if (nmb == NMB && tpw == TPW && cl == CLV) {                                                                        \

@@ -26,6 +26,7 @@
 //     consume them.  Partial sums per chunk go to a workspace, a second kernel adds the chunks in a fixed order
 //     (bit-reproducible) and writes torch's [co][ci][ky][kx].
 #include "common.hpp"
+#include "launch_plan.hpp"
 #include "split_f16.hpp"
 
 typedef float cb_f16 __attribute__((ext_vector_type(16)));
@@ -489,24 +490,39 @@ static int cb_geom(const char* who, ConvBwdGeom& G, int32_t n, int32_t c_in, int
   return MNERF_OK;
 }
 
-// launch of conv_gemm_kernel: channel blocks per wave - all of them (the source loads are shared) unless that leaves the chip short of
-// waves (the 64 x 80 maps of the last stage: 576 waves with four blocks each); two position blocks per wave where they fit
-template <bool FWD>
-static void cb_gemm_launch(const float* src, const float* wt, const float* bias, float* dst, const ConvGemm& G, hipStream_t st) {
-  const int classes = FWD ? 1 : G.s;
-  const int per_class = FWD ? G.wd : (G.wd + G.s - 1) / G.s;
+// which conv_gemm_kernel<CIB, NB, FWD, TAIL> a problem launches: channel blocks per wave - all of them (the source loads are shared)
+// unless that leaves the chip short of waves (the 64 x 80 maps of the last stage: 576 waves with four blocks each); two position
+// blocks per wave where they fit.  The launch below and mnerf_debug_launch_plan("conv_gemm") both read it from here.
+struct CbGemmPlan {
+  int cib, nb, tail, nseg;
+  long long waves;
+};
+static CbGemmPlan cb_gemm_plan(bool fwd, const ConvGemm& G) {
+  const int classes = fwd ? 1 : G.s;
+  const int per_class = fwd ? G.wd : (G.wd + G.s - 1) / G.s;
   const int segs = (per_class + 31) / 32;
   const long long rows = (long long)G.n * G.hd * classes;
+  CbGemmPlan pl;
   int cib = G.cm / 32;
   while (cib > 1 && cib % 2 == 0 && rows * segs * (G.cm / 32 / cib) < 2048) cib /= 2;
   if (cib == 3 && rows * segs < 2048) cib = 1;
-  const int nb = cib <= 2 && rows * ((segs + 1) / 2) * (G.cm / 32 / cib) >= 2048 ? 2 : 1;
-  const int nseg = (segs + nb - 1) / nb;
-  const long long waves = rows * nseg * (G.cm / 32 / cib);
+  pl.cib = cib;
+  pl.nb = cib <= 2 && rows * ((segs + 1) / 2) * (G.cm / 32 / cib) >= 2048 ? 2 : 1;
+  pl.tail = G.ck % 8 == 0 ? 0 : 1;
+  pl.nseg = (segs + pl.nb - 1) / pl.nb;
+  pl.waves = rows * pl.nseg * (G.cm / 32 / cib);
+  return pl;
+}
+
+template <bool FWD>
+static void cb_gemm_launch(const float* src, const float* wt, const float* bias, float* dst, const ConvGemm& G, hipStream_t st) {
+  const CbGemmPlan pl = cb_gemm_plan(FWD, G);
+  const int cib = pl.cib, nb = pl.nb, nseg = pl.nseg;
+  const long long waves = pl.waves;
   const dim3 grid((unsigned)((waves + 3) / 4));
 #define CB_DG(C_, N_)                                                                                                           \
   do {                                                                                                                          \
-    if (G.ck % 8 == 0)                                                                                                          \
+    if (!pl.tail)                                                                                                               \
       hipLaunchKernelGGL((conv_gemm_kernel<C_, N_, FWD, false>), grid, dim3(256), 0, st, src, wt, bias, dst, G, nseg, waves);   \
     else                                                                                                                        \
       hipLaunchKernelGGL((conv_gemm_kernel<C_, N_, FWD, true>), grid, dim3(256), 0, st, src, wt, bias, dst, G, nseg, waves);    \
@@ -520,6 +536,23 @@ static void cb_gemm_launch(const float* src, const float* wt, const float* bias,
 #undef CB_DG
 }
 
+// the GEMM views of the two entry points: backward-data reads dY (c_out channels) and writes dX, the fp32 forward reads x
+static void cb_gemm_geom_bwd(ConvGemm& G, const ConvBwdGeom& B) {
+  G.n = B.n, G.cm = B.c_in, G.ck = B.c_out, G.hs = B.ho, G.ws = B.wo, G.hd = B.h, G.wd = B.w, G.k = B.k, G.s = B.s, G.pad = B.pad;
+}
+static int cb_gemm_geom_fwd(const char* who, ConvGemm& G, int32_t n_img, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                            int32_t ksize, int32_t stride) {
+  MNERF_REQUIRE(n_img >= 0 && h_in >= 1 && w_in >= 1, MNERF_E_RANGE, "%s: n=%d h=%d w=%d", who, n_img, h_in, w_in);
+  MNERF_REQUIRE(c_in >= 1 && c_in <= 128 && c_out >= 32 && c_out <= 128 && c_out % 32 == 0, MNERF_E_UNSUPPORTED,
+                "%s: channels %d -> %d (any input count up to 128, output multiples of 32 up to 128 are built)", who, c_in, c_out);
+  MNERF_REQUIRE((ksize == 1 || ksize == 3 || ksize == 7) && (stride == 1 || stride == 2), MNERF_E_UNSUPPORTED, "%s: ksize=%d stride=%d", who,
+                ksize, stride);
+  G.n = n_img, G.cm = c_out, G.ck = c_in, G.hs = h_in, G.ws = w_in, G.k = ksize, G.s = stride, G.pad = ksize / 2;
+  G.hd = (h_in + 2 * G.pad - ksize) / stride + 1;
+  G.wd = (w_in + 2 * G.pad - ksize) / stride + 1;
+  return MNERF_OK;
+}
+
 extern "C" int mnerf_conv2d_backward_data(const float* dy, const float* w_tap_major, float* dx, int32_t n_img, int32_t c_in, int32_t c_out,
                                           int32_t h_in, int32_t w_in, int32_t ksize, int32_t stride, void* stream) {
   const char* who = "mnerf_conv2d_backward_data";
@@ -528,7 +561,7 @@ extern "C" int mnerf_conv2d_backward_data(const float* dy, const float* w_tap_ma
   if (n_img == 0) return MNERF_OK;
   MNERF_REQUIRE(dy && w_tap_major && dx, MNERF_E_NULL, "%s: NULL buffer", who);
   ConvGemm G;
-  G.n = n_img, G.cm = c_in, G.ck = c_out, G.hs = B.ho, G.ws = B.wo, G.hd = h_in, G.wd = w_in, G.k = ksize, G.s = stride, G.pad = B.pad;
+  cb_gemm_geom_bwd(G, B);
   cb_gemm_launch<false>(dy, w_tap_major, nullptr, dx, G, (hipStream_t)stream);
   return mnerf_check_launch(who);
 }
@@ -536,19 +569,32 @@ extern "C" int mnerf_conv2d_backward_data(const float* dy, const float* w_tap_ma
 extern "C" int mnerf_conv2d_forward_f32(const float* x, const float* w_tap_major, const float* bias, float* y, int32_t n_img, int32_t c_in,
                                         int32_t c_out, int32_t h_in, int32_t w_in, int32_t ksize, int32_t stride, void* stream) {
   const char* who = "mnerf_conv2d_forward_f32";
-  MNERF_REQUIRE(n_img >= 0 && h_in >= 1 && w_in >= 1, MNERF_E_RANGE, "%s: n=%d h=%d w=%d", who, n_img, h_in, w_in);
-  MNERF_REQUIRE(c_in >= 1 && c_in <= 128 && c_out >= 32 && c_out <= 128 && c_out % 32 == 0, MNERF_E_UNSUPPORTED,
-                "%s: channels %d -> %d (any input count up to 128, output multiples of 32 up to 128 are built)", who, c_in, c_out);
-  MNERF_REQUIRE((ksize == 1 || ksize == 3 || ksize == 7) && (stride == 1 || stride == 2), MNERF_E_UNSUPPORTED, "%s: ksize=%d stride=%d", who,
-                ksize, stride);
+  ConvGemm G;
+  if (const int rc = cb_gemm_geom_fwd(who, G, n_img, c_in, c_out, h_in, w_in, ksize, stride)) return rc;
   if (n_img == 0) return MNERF_OK;
   MNERF_REQUIRE(x && w_tap_major && y, MNERF_E_NULL, "%s: NULL buffer", who);
-  ConvGemm G;
-  G.n = n_img, G.cm = c_out, G.ck = c_in, G.hs = h_in, G.ws = w_in, G.k = ksize, G.s = stride, G.pad = ksize / 2;
-  G.hd = (h_in + 2 * G.pad - ksize) / stride + 1;
-  G.wd = (w_in + 2 * G.pad - ksize) / stride + 1;
   cb_gemm_launch<true>(x, w_tap_major, bias, y, G, (hipStream_t)stream);
   return mnerf_check_launch(who);
+}
+
+// args: fwd (1: mnerf_conv2d_forward_f32, 0: mnerf_conv2d_backward_data), n_img, c_in, c_out, h_in, w_in, ksize, stride
+// -> plan: cib, nb, tail, fwd
+int mnerf_plan_conv_gemm(const int64_t* a, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  const char* who = "mnerf_debug_launch_plan(conv_gemm)";
+  MNERF_REQUIRE(n_args == 8 && n_plan >= 4, MNERF_E_RANGE, "%s: takes 8 arguments and fills 4 values, got %d and %d", who, n_args, n_plan);
+  for (int i = 1; i < 8; ++i) MNERF_REQUIRE(a[i] >= 0 && a[i] <= 0x3fffffff, MNERF_E_RANGE, "%s: argument %d = %lld", who, i, (long long)a[i]);
+  MNERF_REQUIRE(a[1] >= 1, MNERF_E_RANGE, "%s: n_img=%lld", who, (long long)a[1]);
+  ConvGemm G;
+  if (a[0]) {
+    if (const int rc = cb_gemm_geom_fwd(who, G, (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5], (int)a[6], (int)a[7])) return rc;
+  } else {
+    ConvBwdGeom B;
+    if (const int rc = cb_geom(who, B, (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5], (int)a[6], (int)a[7])) return rc;
+    cb_gemm_geom_bwd(G, B);
+  }
+  const CbGemmPlan pl = cb_gemm_plan(a[0] != 0, G);
+  plan[0] = pl.cib, plan[1] = pl.nb, plan[2] = pl.tail, plan[3] = a[0] ? 1 : 0;
+  return MNERF_OK;
 }
 
 // chunks of dY rows: enough waves for the chip, partial sums of at most ~32 MiB
@@ -562,6 +608,18 @@ static void cb_chunks(const ConvBwdGeom& G, int& chunks, int& rpc) {
   if (want > rows) want = rows;
   rpc = (int)((rows + want - 1) / want);
   chunks = (int)((rows + rpc - 1) / rpc);
+}
+
+// args: n_img, c_in, c_out, h_in, w_in, ksize, stride -> plan: chunks, rows per chunk (both weight-gradient forms)
+int mnerf_plan_conv_wgrad(const int64_t* a, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  const char* who = "mnerf_debug_launch_plan(conv_wgrad)";
+  MNERF_REQUIRE(n_args == 7 && n_plan >= 2, MNERF_E_RANGE, "%s: takes 7 arguments and fills 2 values, got %d and %d", who, n_args, n_plan);
+  for (int i = 0; i < 7; ++i) MNERF_REQUIRE(a[i] >= 0 && a[i] <= 0x3fffffff, MNERF_E_RANGE, "%s: argument %d = %lld", who, i, (long long)a[i]);
+  MNERF_REQUIRE(a[0] >= 1, MNERF_E_RANGE, "%s: n_img=%lld", who, (long long)a[0]);
+  ConvBwdGeom G;
+  if (const int rc = cb_geom(who, G, (int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5], (int)a[6])) return rc;
+  cb_chunks(G, plan[0], plan[1]);
+  return MNERF_OK;
 }
 
 extern "C" size_t mnerf_conv2d_backward_weight_workspace_bytes(int32_t n_img, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,

@@ -12,6 +12,7 @@
 // reductions) and writes the finished value once: one read, one write - the kernel is HBM/L2-bound by construction.
 // Planes that do not fit (or whose size is not a multiple of four) take a three-pass streaming kernel.
 #include "common.hpp"
+#include "launch_plan.hpp"
 
 template <int THREADS>
 __device__ __forceinline__ float in_block_sum(float v, float* red) {
@@ -137,6 +138,25 @@ __global__ __launch_bounds__(256) void instance_norm_stream_kernel(const float* 
   in_merge_absmax<256>(omax, red, out_absmax);
 }
 
+// which register-cached instance <THREADS, VPT> holds a plane of n floats (16-byte pieces: n a multiple of 4, aligned buffers); T = 0:
+// the streaming kernel.  The forward, the backward and mnerf_debug_launch_plan("instance_norm" / "instance_norm_backward") read it here.
+static void in_plan(int n, bool vec, int& T, int& V) {
+  if (vec && n <= 256 * 8 * 4) T = 256, V = 8;
+  else if (vec && n <= 256 * 20 * 4) T = 256, V = 20;
+  else if (vec && n <= 512 * 40 * 4) T = 512, V = 40;  // two workgroups per CU: one plane loads while another stores
+  else T = 0, V = 0;
+}
+
+// args: plane_size, aligned (1: every buffer is 16-byte aligned) -> plan: T, V (0, 0: the streaming kernel); one table for both directions
+int mnerf_plan_instance_norm(const int64_t* a, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  const char* who = "mnerf_debug_launch_plan(instance_norm)";
+  MNERF_REQUIRE(n_args == 2 && n_plan >= 2, MNERF_E_RANGE, "%s: takes 2 arguments and fills 2 values, got %d and %d", who, n_args, n_plan);
+  MNERF_REQUIRE(a[0] >= 1 && a[0] <= 0x7fffffffLL, MNERF_E_RANGE, "%s: plane_size=%lld", who, (long long)a[0]);
+  const int n = (int)a[0];
+  in_plan(n, (n & 3) == 0 && a[1] != 0, plan[0], plan[1]);
+  return MNERF_OK;
+}
+
 extern "C" int mnerf_instance_norm(const float* x, const float* residual, float* out, int64_t planes,
                                    int64_t plane_size, float eps, int32_t relu_inner, int32_t relu_outer,
                                    float* out_absmax, void* stream) {
@@ -152,9 +172,11 @@ extern "C" int mnerf_instance_norm(const float* x, const float* residual, float*
 #define IN_LAUNCH(T, V)                                                                                              \
   hipLaunchKernelGGL((instance_norm_cached_kernel<T, V>), grid, dim3(T), 0, st, x, residual, out, n, eps, relu_inner, \
                      relu_outer, out_absmax)
-  if (vec && n <= 256 * 8 * 4) IN_LAUNCH(256, 8);
-  else if (vec && n <= 256 * 20 * 4) IN_LAUNCH(256, 20);
-  else if (vec && n <= 512 * 40 * 4) IN_LAUNCH(512, 40);  // two workgroups per CU: one plane loads while another stores
+  int T, V;
+  in_plan(n, vec, T, V);
+  if (T == 256 && V == 8) IN_LAUNCH(256, 8);
+  else if (T == 256 && V == 20) IN_LAUNCH(256, 20);
+  else if (T == 512 && V == 40) IN_LAUNCH(512, 40);
   else
     hipLaunchKernelGGL(instance_norm_stream_kernel, grid, dim3(256), 0, st, x, residual, out, n, eps, relu_inner, relu_outer,
                        out_absmax);
@@ -279,9 +301,11 @@ extern "C" int mnerf_instance_norm_backward(const float* x, const float* dy, flo
   const dim3 grid((unsigned)planes);
   const bool vec = (n & 3) == 0 && mnerf_aligned16(x) && mnerf_aligned16(dy) && mnerf_aligned16(dx);
 #define INB_LAUNCH(T, V) hipLaunchKernelGGL((instance_norm_backward_cached_kernel<T, V>), grid, dim3(T), 0, st, x, dy, dx, n, eps, relu)
-  if (vec && n <= 256 * 8 * 4) INB_LAUNCH(256, 8);
-  else if (vec && n <= 256 * 20 * 4) INB_LAUNCH(256, 20);
-  else if (vec && n <= 512 * 40 * 4) INB_LAUNCH(512, 40);
+  int T, V;
+  in_plan(n, vec, T, V);
+  if (T == 256 && V == 8) INB_LAUNCH(256, 8);
+  else if (T == 256 && V == 20) INB_LAUNCH(256, 20);
+  else if (T == 512 && V == 40) INB_LAUNCH(512, 40);
   else hipLaunchKernelGGL(instance_norm_backward_kernel, grid, dim3(512), 0, st, x, dy, dx, n, eps, relu);
 #undef INB_LAUNCH
   return mnerf_check_launch("mnerf_instance_norm_backward");

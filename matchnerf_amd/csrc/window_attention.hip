@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "wa_common.hpp"
+#include "launch_plan.hpp"
 
 // ---- LDS-DMA helpers (see decoder_common.hpp: an asm global_load_lds is invisible to hipcc's
 // wait-count bookkeeping, so the prefetch of tile t+1 is not drained in front of tile t's reads)
@@ -988,6 +989,25 @@ extern "C" size_t mnerf_window_attention_workspace_bytes(int32_t batch, int32_t 
   return wa_workspace_bytes(batch, h, w, num_splits);
 }
 
+// 128-query workgroups (the <4> instances, four waves) once there are wa_min4 of them, 64-query ones (<2>) below that: both launch
+// sites and mnerf_debug_launch_plan("window_attention") read it here
+static bool wa_take_four(int Lw, int n_win, int batch) {
+  const long long wgs4 = (long long)((Lw + 127) / 128) * n_win * batch;
+  return wgs4 >= mnerf_tune().wa_min4;
+}
+
+// args: batch, h, w, num_splits -> plan: 4 or 2 (query waves per workgroup; the same for every arithmetic and for the images form)
+int mnerf_plan_window_attention(const int64_t* a, int32_t n_args, int32_t* plan, int32_t n_plan) {
+  const char* who = "mnerf_debug_launch_plan(window_attention)";
+  MNERF_REQUIRE(n_args == 4 && n_plan >= 1, MNERF_E_RANGE, "%s: takes 4 arguments and fills 1 value, got %d and %d", who, n_args, n_plan);
+  MNERF_REQUIRE(a[0] >= 1 && a[0] <= 65535 && a[1] >= 1 && a[2] >= 1 && a[1] <= 0x7fff && a[2] <= 0x7fff && a[3] >= 1 && a[3] <= 255,
+                MNERF_E_RANGE, "%s: batch=%lld h=%lld w=%lld splits=%lld", who, (long long)a[0], (long long)a[1], (long long)a[2], (long long)a[3]);
+  MNERF_REQUIRE(a[1] % a[3] == 0 && a[2] % a[3] == 0, MNERF_E_RANGE, "%s: %lldx%lld not divisible into %lld splits", who, (long long)a[1],
+                (long long)a[2], (long long)a[3]);
+  plan[0] = wa_take_four((int)((a[1] / a[3]) * (a[2] / a[3])), (int)(a[3] * a[3]), (int)a[0]) ? 4 : 2;
+  return MNERF_OK;
+}
+
 // the attention kernel over prepared images (filled by wa_presplit_kernel or by the q|k|v kernel, qkv.hip)
 static int wa_launch_main(const char* who, const float* q, float* out, const WinGeom& G, int do_shift, int32_t batch,
                           int32_t num_splits, void* workspace, hipStream_t st, float* row_stats = nullptr) {
@@ -1008,10 +1028,9 @@ static int wa_launch_main(const char* who, const float* q, float* out, const Win
 #ifdef MNERF_TIMELINE
   if (const char* e = getenv("MNERF_WA_TIMELINE_PTR")) tl = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-  const long long wgs4 = (long long)((G.Lw + 127) / 128) * n_win * batch;
   const long long win_groups = ((long long)n_win * batch + 7) / 8;  // windows per XCD
   const int xcd = mnerf_tune().wa_xcd;
-  const bool four = wgs4 >= mnerf_tune().wa_min4;
+  const bool four = wa_take_four(G.Lw, n_win, batch);
   const int n_qb = four ? (G.Lw + 127) / 128 : (G.Lw + 63) / 64;
   const dim3 grid((unsigned)(8 * win_groups * n_qb));
 #ifndef MNERF_TIMELINE
@@ -1118,7 +1137,6 @@ extern "C" int mnerf_window_attention(const float* q, const float* k, const floa
   G.Lw = G.wh * G.ww;
   const float scale = 1.0f / sqrtf((float)WA_C);
   hipStream_t st = (hipStream_t)stream;
-  const long long wgs4 = (long long)((G.Lw + 127) / 128) * num_splits * num_splits * batch;
   const size_t lds = 4 * WA_KT * WA_C * sizeof(float);  // 64 KiB: K and V tiles, double buffered
   const bool split = math == MNERF_WA_SPLIT_BF16;  // split-bf16 products (the host's default), split-fp16 products or the exact-f32 MFMA
   const bool split_h = math == MNERF_WA_SPLIT_F16;
@@ -1135,8 +1153,7 @@ extern "C" int mnerf_window_attention(const float* q, const float* k, const floa
     (void)hipFuncSetAttribute((const void*)window_attention_bf16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void*)window_attention_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  const int min4 = mnerf_tune().wa_min4;
-  if (wgs4 >= min4) {
+  if (wa_take_four(G.Lw, num_splits * num_splits, batch)) {
     dim3 grid((G.Lw + 127) / 128, num_splits * num_splits, batch);
     if (split_h)
       hipLaunchKernelGGL(window_attention_f16_kernel<4>, grid, dim3(256), lds, st, q, k, v, out, G, do_shift, scale);

@@ -157,6 +157,7 @@ SIGNATURES = {
     "mnerf_composite_backward": (_int, [_i32] * 2 + [_vp] * 4 + [_i32] * 2 + [_vp] * 6),
     "mnerf_cost_volume_backward": (_int, [_P(Scene), _P(Rays), _i32] + [_vp] * 4),
     "mnerf_debug_set_knob": (_int, [C.c_char_p, _int, _P(_int)]),
+    "mnerf_debug_launch_plan": (_int, [C.c_char_p, _vp, _i32, _P(_i32), _i32]),
     "mnerf_decoder_backward_workspace_bytes": (_i64, [_i32] * 2),
     "mnerf_decoder_backward": (_int, [_P(DecoderTrain)] + [_i32] * 2 + [_vp] * 3 + [_i32] + [_vp] * 5),
     "mnerf_window_attention": (_int, [_vp] * 4 + [_i32] * 6 + [_vp]),
@@ -259,6 +260,16 @@ def knob(name, value):
         yield
     finally:
         lib.mnerf_debug_set_knob(name.encode(), old.value, None)
+
+
+def launch_plan(what, *args, n_plan=4):
+    """Tests / diagnosis: the kernel instance the library would launch for a problem (mnerf_debug_launch_plan; include/mnerf.h lists
+    the arguments and the values per dispatcher).  Needs no GPU.  -> tuple of ``n_plan`` ints."""
+    lib = load()
+    a = (C.c_int64 * len(args))(*[int(v) for v in args])
+    plan = (C.c_int32 * n_plan)()
+    check(lib.mnerf_debug_launch_plan(what.encode(), a, len(args), plan, n_plan), "mnerf_debug_launch_plan")
+    return tuple(plan)
 
 
 def check(rc, what):

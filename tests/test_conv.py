@@ -4,6 +4,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from launch_plan_tables import CONV_CASES as CASES, CONV_TPW2_CASES, CONV_WIDE_CASES
 from matchnerf_amd import gmflow as G
 
 
@@ -46,29 +47,20 @@ def hip():
     return H
 
 
-CASES = [  # n, c_in, c_out, k, stride, h, w, channels_last, upsample2x, leaky, bias
-    (3, 64, 64, 3, 1, 64, 80, False, False, 1.0, False),
-    (2, 64, 96, 3, 2, 64, 80, False, False, 1.0, False),
-    (2, 64, 96, 1, 2, 64, 80, False, False, 1.0, True),
-    (2, 96, 96, 3, 1, 32, 40, False, False, 1.0, False),
-    (2, 96, 128, 3, 2, 33, 41, False, False, 1.0, False),   # odd sizes: ragged last tile, odd stride-2 geometry
-    (1, 128, 128, 1, 1, 8, 10, False, False, 1.0, True),
-    (2, 128, 128, 3, 1, 16, 20, True, False, 1.0, True),     # channel-last tokens in
-    (2, 128, 128, 3, 1, 16, 20, True, True, 0.2, True),      # ... through a nearest 2x up-sampling, LeakyReLU epilogue
-    (1, 128, 128, 3, 1, 9, 7, False, True, 0.2, True),
-]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES)
 def test_conv2d_matches_float64(hip, case):
+    _conv2d_against_float64(hip, case)
+
+
+def _conv2d_against_float64(hip, case):
     n, ci, co, k, s, h, w, cl, up, leaky, use_bias = case
     gen = torch.Generator().manual_seed(ci * 7 + co + k + h)
     x = torch.randn(n, ci, h, w, generator=gen) * (0.5 + 4 * torch.rand(1, ci, 1, 1, generator=gen))
     x[0, 0, 0, 0] = 37.0                                            # one spike: sets the tensor's operand scale
     wt = torch.randn(co, ci, k, k, generator=gen) * (1.0 / np.sqrt(ci * k * k))
     bias = torch.randn(co, generator=gen) if use_bias else None
-    ws, ew = G.pack_conv(wt)
+    ws, ew = G.pack_conv(wt) if co <= 128 else G.pack_conv_blocks(wt)
     xin = x.permute(0, 2, 3, 1).contiguous() if cl else x
     scal = hip.absmax_regions(2, "cuda")
     hip.absmax(xin.cuda(), scal[0])
@@ -92,6 +84,24 @@ def test_conv2d_matches_float64(hip, case):
     # and an absolute gate that does not move with torch: observed <= 1.0e-6 of the largest output over all cases (MI355X)
     assert err < 3e-6 * float(want.abs().max()), (case, err)
     assert float(hip.absmax_value(scal[1])) == float(got.abs().max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CONV_TPW2_CASES + CONV_WIDE_CASES)
+def test_conv2d_two_tiles_per_wave_and_wide_outputs_match_float64(hip, case):
+    """conv_kernel<2 | 3 | 4, 2, false | true>: the instances a full frame launches (two pixel tiles per wave from 65 281 output
+    pixels on), and c_out 256 / 512 as blocks of 128 channels along grid.y - at the smallest odd sizes past the threshold, with a
+    ragged last workgroup; tests/test_launch_plans.py holds each case to its instance.  Same float64 reference, fp32 yardstick and
+    gates as test_conv2d_matches_float64.  Measured on MI355X, |err| / max|want| (fp32 CPU evaluation in brackets):
+      (1, 64, 64, 3, 1, 255, 257, False, False, 1.0, False): 7.0e-07 (3.4e-07)
+      (1, 64, 96, 3, 2, 509, 515, False, False, 1.0, False): 6.1e-07 (3.3e-07)
+      (1, 128, 128, 3, 1, 255, 257, False, False, 1.0, True): 1.0e-06 (3.0e-07)
+      (1, 128, 128, 3, 1, 255, 257, True, False, 1.0, True): 1.0e-06 (3.0e-07)
+      (1, 128, 128, 3, 1, 127, 129, True, True, 0.2, True): 9.4e-07 (2.7e-07)
+      (1, 64, 256, 1, 1, 255, 257, False, False, 1.0, True): 2.3e-07 (3.8e-07)
+      (2, 32, 256, 1, 1, 9, 11, False, False, 1.0, True): 1.5e-07 (1.5e-07)
+      (1, 32, 512, 1, 1, 9, 11, False, False, 1.0, False): 1.3e-07 (2.1e-07)"""
+    _conv2d_against_float64(hip, case)
 
 
 @pytest.mark.gpu

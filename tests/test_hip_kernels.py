@@ -13,6 +13,7 @@ import torch
 from gpu_helpers import (cond_with_stride, images_rgba, make_decoder_struct, make_rays_struct, make_scene_struct,
                          pair_feats_to_pair_major, ref_layout_to_pair_major)
 from helpers import golden_case, linf, split_poses
+from launch_plan_tables import WA_DTU_SHAPES
 from oracle import matchnerf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +133,7 @@ def test_window_attention_dtu_shape_matches_oracle(hip, math, monkeypatch):
     wildly different factors (the split-fp16 path's per-query / per-tile gains)."""
     monkeypatch.setenv("MNERF_WA_MATH", math)
     gen = torch.Generator().manual_seed(3)
-    for (b, h, w, splits) in ((2, 64, 80, 2), (1, 50, 50, 2)):
+    for (b, h, w, splits) in WA_DTU_SHAPES:
         q, k, v = (torch.randn(b, h * w, 128, generator=gen) for _ in range(3))
         for shifted in (False, True):
             ref = O.window_attention(q, k, v, h, w, splits, shifted)
@@ -144,6 +145,44 @@ def test_window_attention_dtu_shape_matches_oracle(hip, math, monkeypatch):
         ref = O.window_attention(q * sq, k, v * sv, h, w, splits, True)
         out = hip.window_attention((q * sq).cuda(), k.cuda(), (v * sv).cuda(), h, w, splits, True)
         assert torch.isfinite(out).all() and linf(out, ref) < 2e-5 * float(ref.abs().max()), (h, w, "scaled")
+
+
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("math", ["f16pre", "f16x3", "bf16x6", "f32"])
+def test_window_attention_128_query_instances_on_a_ragged_window(hip, math, shifted, monkeypatch):
+    """the <4> instances (128-query workgroups, taken from wa_min4 = 200 workgroups on: full frames) of all four arithmetics on
+    150-token windows under the wa_min4 knob: the second query block has 22 live rows of 128 and the third key tile 22 live keys
+    of 64, which the suite otherwise shows only to the <2> instances (the 1280-token windows of the DTU shape divide by both).
+    Measured on MI355X, max |out - oracle|: f16pre plain 8.94e-07; f16pre shifted 8.94e-07; f16x3 plain 6.56e-07; f16x3 shifted 1.01e-06; bf16x6 plain 1.01e-06; bf16x6 shifted 1.10e-06; f32 plain 1.01e-06; f32 shifted 1.28e-06"""
+    from launch_plan_tables import WA_FORCED4
+    monkeypatch.setenv("MNERF_WA_MATH", math)
+    b, h, w, splits, min4 = WA_FORCED4
+    gen = torch.Generator().manual_seed(11 + int(shifted))
+    q, k, v = (torch.randn(b, h * w, 128, generator=gen) for _ in range(3))
+    ref = O.window_attention(q, k, v, h, w, splits, shifted)
+    two = hip.window_attention(q.cuda(), k.cuda(), v.cuda(), h, w, splits, shifted)
+    with hip.knob("wa_min4", min4):
+        assert hip.launch_plan("window_attention", b, h, w, splits, n_plan=1) == (4,)
+        out = hip.window_attention(q.cuda(), k.cuda(), v.cuda(), h, w, splits, shifted)
+    print(f"\nwindow attention <4> {math} shifted={shifted}: {linf(out, ref):.2e} (<2>: {linf(two, ref):.2e})")
+    assert torch.isfinite(out).all() and linf(out, ref) < 2e-5
+    assert linf(two, ref) < 2e-5
+
+
+def test_window_attention_128_query_instances_at_their_own_threshold(hip):
+    """no knob: 6 x 4 windows of 33 x 35 = 1155 tokens are 240 workgroups of 128 queries, the last of each window with 3 live rows,
+    and 19 key tiles, the last with 3 live keys (800 x 800 frames: 2500-token windows, ragged the same way).  Default arithmetic.
+    Measured on MI355X, max |out - oracle|: plain 6.26e-07; shifted 8.34e-07"""
+    from launch_plan_tables import WA_NATURAL4
+    b, h, w, splits, _ = WA_NATURAL4
+    assert hip.launch_plan("window_attention", b, h, w, splits, n_plan=1) == (4,)
+    gen = torch.Generator().manual_seed(12)
+    q, k, v = (torch.randn(b, h * w, 128, generator=gen) for _ in range(3))
+    for shifted in (False, True):
+        ref = O.window_attention(q, k, v, h, w, splits, shifted)
+        out = hip.window_attention(q.cuda(), k.cuda(), v.cuda(), h, w, splits, shifted)
+        print(f"\nwindow attention natural <4> shifted={shifted}: {linf(out, ref):.2e}")
+        assert torch.isfinite(out).all() and linf(out, ref) < 2e-5, shifted
 
 
 @pytest.mark.parametrize("name", ["c1_default", "rect_wide", "nonlegacy", "v4", "inverse_depth", "demo_own_small", "demo_own"])

@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from launch_plan_tables import IN_FWD_SHAPES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,8 +25,7 @@ def _chain(x, res, inner, outer):
     return F.relu(v) if outer else v
 
 
-@pytest.mark.parametrize("shape", [(3, 64, 256, 320), (3, 96, 128, 160), (2, 128, 64, 80), (1, 5, 7, 9), (1, 3, 400, 400),
-                                   (2, 4, 50, 50)])
+@pytest.mark.parametrize("shape", IN_FWD_SHAPES)
 def test_instance_norm_matches_torch_and_float64(hip, shape):
     gen = torch.Generator().manual_seed(sum(shape))
     # planes with very different offsets and spreads (the centred variance must not cancel)

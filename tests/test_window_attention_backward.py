@@ -4,19 +4,13 @@ the reference)."""
 import pytest
 import torch
 
+from launch_plan_tables import WA_BWD_CASES
 from oracle import matchnerf_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("b,h,w,splits,shifted", [
-    (2, 16, 24, 2, False),   # 96-token windows: one and a half 64-row tiles
-    (2, 16, 24, 2, True),    # wrap-region mask
-    (1, 12, 20, 1, False),   # one window = the whole map (global attention), 240 tokens
-    (3, 24, 24, 2, True),    # 144-token windows, odd tile remainder
-    (2, 32, 40, 4, True),    # attn_splits 4 (rect_wide / IBRNet-style)
-    (6, 64, 80, 2, True),    # the DTU shape: 3 pairs x 2 directions, 1280-token windows
-])
+@pytest.mark.parametrize("b,h,w,splits,shifted", WA_BWD_CASES)
 @pytest.mark.parametrize("forward_stats", [False, True])
 @pytest.mark.parametrize("math", ["f16x3", "bf16x6"])
 def test_window_attention_backward_matches_float64_autograd(b, h, w, splits, shifted, forward_stats, math, monkeypatch):
@@ -50,6 +44,42 @@ def test_window_attention_backward_matches_float64_autograd(b, h, w, splits, shi
         assert torch.isfinite(got).all()
         worst[name] = float((got.cpu().double() - ref).abs().max() / ref.abs().max())
     print({kk: f"{vv:.1e}" for kk, vv in worst.items()})
+    assert all(vv < 2e-5 for vv in worst.values()), worst
+
+
+@pytest.mark.parametrize("shifted", [False, True])
+def test_statistics_of_the_128_query_instance_on_a_ragged_window_feed_the_backward(shifted):
+    """window_attention_pre_kernel<4, true> (the training forward of full frames) on 150-token windows under the wa_min4 knob: its
+    last query block has 22 live rows of 128.  Its output (and the <2> instance's) against the oracle, then the
+    statistics-consuming backward on its row statistics against float64 autograd.  The file's 2e-5 gates.  Measured on MI355X: plain: out 1.4e-07, gradients {q: 3.3e-07, k: 3.2e-07, v: 3.2e-07}; shifted: out 2.4e-07, gradients {q: 3.3e-07, k: 2.9e-07, v: 3.3e-07}"""
+    from launch_plan_tables import WA_FORCED4
+    from matchnerf_amd import hip
+    b, h, w, splits, min4 = WA_FORCED4
+    gen = torch.Generator().manual_seed(31 + int(shifted))
+    n, c = h * w, 128
+    q = torch.randn(b, n, c, generator=gen) * 0.6
+    k = torch.randn(b, n, c, generator=gen) * 0.8
+    v = torch.randn(b, n, c, generator=gen)
+    g = torch.randn(b, n, c, generator=gen)
+    qg, kg, vg, gg = q.cuda(), k.cuda(), v.cuda(), g.cuda()
+    out2 = hip.window_attention(qg, kg, vg, h, w, splits, shifted)
+    stats = torch.full((2, b * n), float("nan"), device="cuda")
+    with hip.knob("wa_min4", min4):
+        assert hip.launch_plan("window_attention", b, h, w, splits, n_plan=1) == (4,)
+        out = hip.window_attention(qg, kg, vg, h, w, splits, shifted, row_stats=stats)
+        assert torch.equal(out, hip.window_attention(qg, kg, vg, h, w, splits, shifted))  # the statistics instance computes the same output bits
+    assert torch.isfinite(stats).all() and float(stats[1].min()) >= 1.0   # every token's row was written
+    gq, gk, gv = hip.window_attention_backward(qg, kg, vg, out, gg, h, w, splits, shifted, row_stats=stats)
+    q64, k64, v64 = (t.double().requires_grad_(True) for t in (q, k, v))
+    o64 = O.window_attention(q64, k64, v64, h, w, splits, shifted)
+    e_out, e_out2 = (float((o.cpu().double() - o64.detach()).abs().max()) for o in (out, out2))
+    (o64 * g.double()).sum().backward()
+    worst = {}
+    for name, got, ref in (("q", gq, q64.grad), ("k", gk, k64.grad), ("v", gv, v64.grad)):
+        assert torch.isfinite(got).all()
+        worst[name] = float((got.cpu().double() - ref).abs().max() / ref.abs().max())
+    print(f"\n<4, stats> shifted={shifted}: out {e_out:.1e} (<2>: {e_out2:.1e})", {kk: f"{vv:.1e}" for kk, vv in worst.items()})
+    assert e_out < 2e-5 and e_out2 < 2e-5
     assert all(vv < 2e-5 for vv in worst.values()), worst
 
 
