@@ -50,6 +50,10 @@
  *       against the older layout is caught by mnerf_struct_size(1), which every binding is expected to compare before its first call.
  *       Added under v12 without a layout change: mnerf_debug_launch_plan (which kernel instance a problem size selects, host only);
  *       mnerf_debug_set_knob knows "wa_min4".
+ *       Added under v12 without a layout change: caller-supplied rays (matchnerf_amd/csrc/free_rays.hip) - ray bundles of
+ *       MNERF_RAY_FLOATS floats per ray, mnerf_cost_volume_rays, mnerf_ray_samples_rays, mnerf_render_rays_workspace_bytes,
+ *       mnerf_render_rays, and the camera models that fill a bundle on the device: mnerf_camera - struct index
+ *       MNERF_STRUCT_CAMERA -, mnerf_camera_rays.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -184,7 +188,8 @@ typedef struct mnerf_decoder {
 
 int mnerf_abi_version(void);
 const char* mnerf_last_error(void);
-/* sizeof() of the argument structs as compiled (0 view, 1 rays, 2 scene, 3 decoder, 4 encoder_layer, 5 conv; -1 else):
+/* sizeof() of the argument structs as compiled (0 view, 1 rays, 2 scene, 3 decoder, 4 encoder_layer, 5 conv, .. 10 lpips_weights: the
+ * structs that prototypes name by type, in the order a binding mirrors them; MNERF_STRUCT_CAMERA mnerf_camera; -1 else):
  * lets a foreign-language binding verify its struct mirrors before the first call. */
 int64_t mnerf_struct_size(int32_t which);
 
@@ -280,6 +285,75 @@ int mnerf_render_chunk_fused(const mnerf_scene* scene, const mnerf_decoder* dec,
  * the host gives the same bits.  1 <= k <= 8, channels in {1, 3}, h, w >= 0 (MNERF_E_RANGE otherwise).  Enqueue-only, one thread
  * per output value.  Replaces nothing in the reference, which renders at the views' size only. */
 int mnerf_box_downsample(const float* src, int32_t h, int32_t w, int32_t channels, int32_t k, float* dst, void* stream);
+
+/* CALLER-SUPPLIED RAYS (added under v12).  Everything above rebuilds a target ray in-kernel from a pixel index of a pinhole camera
+ * (kinv / c2w of mnerf_rays).  The entry points below take the rays themselves, as a RAY BUNDLE:
+ *   ray_od : device, [n_rays][MNERF_RAY_FLOATS] fp32, 32-byte rows, 16-byte aligned (MNERF_E_ALIGN otherwise); a row is
+ *            ox oy oz 0 | dx dy dz 0 = world origin and UN-NORMALISED world direction (the two pad floats are not read).
+ * A sample is o + t d, with t from the launch's near_ / far_ / n_samples / legacy_coord / depth_inverse / strat_u exactly as for
+ * pixel rays (MatchNeRF.sample_depth, models/matchnerf.py:163-181).  Compositing scales the intervals by |d| (nerf.py:101-124), so
+ * pinhole rows - camera-z = 1 - reproduce the pixel paths' numbers, and unit directions make t, and the returned depth, a
+ * Euclidean distance.
+ * Of the mnerf_rays argument only n_rays, n_samples, legacy_coord, depth_inverse, height, width (the SOURCE views), near_, far_
+ * and strat_u are read; ray_idx and pose_table must be NULL (MNERF_E_UNSUPPORTED); kinv, c2w, ray_begin and the target grid are
+ * ignored (the functions work on a canonical copy: the pixel-range check of the target grid does not apply).  Enqueue-only; every
+ * argument check precedes any HIP call (mnerf_render_rays: see there); n_rays == 0 is MNERF_OK and touches no buffer.  Forward only. */
+#define MNERF_RAY_FLOATS 8
+/* K1+K2 over a bundle: mnerf_cost_volume's rows (same layout, same bits for the same rays) by the 16-lane segment walk, whose
+ * RayGeom is read from ray_od (two 16-byte loads per ray) instead of rebuilt from a pixel.  Always the walk: a scene whose
+ * sum(cos_n_group) exceeds 16 is MNERF_E_UNSUPPORTED, scene->feat_op (the matrix form) is ignored.  Many views run in blocks of
+ * view pairs as mnerf_cost_volume does. */
+int mnerf_cost_volume_rays(const mnerf_scene* scene, const mnerf_rays* rays, const float* ray_od, int32_t cond_stride, float* cond,
+                           void* stream);
+/* The decoder's geometric inputs and the compositing's, per sample: x_ndc [R,S,3] sample coordinates w.r.t. source view 0
+ * (matchnerf.py:121-126), dir [R,S,3] the ray's unit direction d / max(|d|, 1e-12) rotated into view0's frame (matchnerf.py:129-132),
+ * depth_s [R,S] the sample parameters t, ray_len [R] = |d|.  Any output may be NULL; view0 is required for x_ndc and dir. */
+int mnerf_ray_samples_rays(const mnerf_rays* rays, const float* ray_od, const mnerf_view* view0, float* x_ndc, float* dir,
+                           float* depth_s, float* ray_len, void* stream);
+/* One render chunk over a bundle = mnerf_cost_volume_rays -> mnerf_ray_samples_rays -> mnerf_decoder_samples -> mnerf_composite on
+ * one stream (four launches, plus one per further pair block), through `workspace` (16-byte aligned,
+ * mnerf_render_rays_workspace_bytes(n_rays, n_samples, dec->cond_stride) bytes; -1 for a negative / zero size).  Workspace layout,
+ * every area starting 16-byte aligned (its float count rounded up to a multiple of 4), R = n_rays, S = n_samples:
+ *   cond [R S cond_stride] | x_ndc [R S 3] | dir [R S 3] | depth_s [R S] | rgb_s [R S 3] | sigma [R S] | ray_len [R]
+ * - the per-sample stages stay readable there after the call (parity tests).  Accepts the decoder shapes mnerf_decoder_samples
+ * accepts; rgb [R,3], depth [R], opacity [R] as mnerf_render_chunk.  The matrix-form cost volume and the one-launch form have no
+ * bundle instance.  Checked before the first launch: the structs, the bundle, the workspace, the outputs, the scene, and of the
+ * decoder its weight pointers, the sample count and the weight stream's size for its shape and format; what only the decoder's own
+ * dispatch can tell (a format without an instance for this shape) is answered by its step, after the first two were enqueued - as
+ * in mnerf_render_chunk. */
+int64_t mnerf_render_rays_workspace_bytes(int32_t n_rays, int32_t n_samples, int32_t cond_stride);
+int mnerf_render_rays(const mnerf_scene* scene, const mnerf_decoder* dec, const mnerf_rays* rays, const float* ray_od,
+                      void* workspace, float* rgb, float* depth, float* opacity, void* stream);
+
+/* Camera models that fill a bundle on the device, one thread per pixel of a height x width grid (row-major pixel index
+ * y * width + x; pixel centres (x, y) = integer coordinates with legacy_coord, + 0.5 otherwise, as for pixel rays):
+ *   PINHOLE  origin = c2w's translation, direction = c2w [kinv (x,y,1); 1] - origin: the rows are, bit for bit, the rays the pixel
+ *            entry points rebuild in-kernel (misc/camera.py:255-278)
+ *   FISHEYE  equidistant: (xn, yn, .) = kinv (x,y,1), theta = |(xn, yn)| radians off the optical axis, camera direction
+ *            (sin(theta) xn / theta, sin(theta) yn / theta, cos(theta)) ((0, 0, 1) at theta = 0), rotated by c2w: unit
+ *   SPHERE   equirectangular window: lon = lon0 + u (lon1 - lon0) over the columns, lat = lat0 + v (lat1 - lat0) over the rows,
+ *            (u, v) = (x / (width - 1), y / (height - 1)) with legacy_coord and (x / width, y / height) otherwise; lon_lat =
+ *            {lon0, lon1, lat0, lat1} in radians, a full panorama is -pi, pi, -pi/2, pi/2; camera direction (cos(lat) sin(lon),
+ *            sin(lat), cos(lat) cos(lon)) - x right, y down, z forward -, rotated by c2w: unit.  kinv is not read
+ *   ORTHO    origin = c2w (xn, yn, 0, 1), direction = c2w's z axis normalised: parallel rays, kinv scales pixels to world units
+ * Sines and cosines are the library's own (angles reduced in revolutions with a two-float 1 / (2 pi), abs error 3e-7), the
+ * camera -> world products the k-ordered FMA chains of the projection code.  lon_lat is read by SPHERE only. */
+#define MNERF_CAM_PINHOLE 0
+#define MNERF_CAM_FISHEYE 1
+#define MNERF_CAM_SPHERE 2
+#define MNERF_CAM_ORTHO 3
+typedef struct mnerf_camera {
+  int32_t model, height, width, legacy_coord;
+  float kinv[9];
+  float c2w[12];
+  float lon_lat[4];
+} mnerf_camera;
+#define MNERF_STRUCT_CAMERA 32 /* mnerf_struct_size(MNERF_STRUCT_CAMERA) = sizeof(mnerf_camera) */
+/* rows [0, n_pixels) of ray_od <- pixels [pixel_begin, pixel_begin + n_pixels) of the camera's grid (MNERF_E_RANGE outside it).
+ * `camera` points at a mnerf_camera (host memory, read during the call).  It travels as an untyped pointer: the structs that
+ * prototypes name by type stay the eleven of mnerf_struct_size(0..10), which existing bindings mirror and count; a binding checks
+ * its mirror of this one against mnerf_struct_size(MNERF_STRUCT_CAMERA). */
+int mnerf_camera_rays(const void* camera, int32_t pixel_begin, int32_t n_pixels, float* ray_od, void* stream);
 
 /* Backward kernels of the ray chunk (training through the HIP path; reference: autograd through the eager chain,
  * coach.py:215-243).

@@ -62,3 +62,67 @@ def resize_intrinsics(K, src_hw, tgt_hw, legacy=True):
         out[..., 0, :] += K[..., 2, :] * ox
         out[..., 1, :] += K[..., 2, :] * oy
     return out
+
+
+# ----------------------------------------------------------------------- camera models of caller-supplied rays (include/mnerf.h)
+CAMERA_MODELS = ("pinhole", "fisheye", "sphere", "ortho")  # index = mnerf_camera.model (MNERF_CAM_*)
+
+
+def camera_model(name, height, width, extr34, intr33=None, legacy=True, fov_deg=None, ortho_width=None, lon_lat=None):
+    """-> ``hip.Camera`` (struct mnerf_camera) of a ``height`` x ``width`` grid at the pose ``extr34`` (world -> camera, 3x4):
+
+    "pinhole"  ``intr33`` (of this grid): the rows are the pixel rays of the render path, bit for bit;
+    "fisheye"  equidistant, the angle off the axis grows linearly with the distance from the principal point: ``fov_deg`` across the
+               frame's width around its centre, or ``intr33`` (focal length = pixels per radian);
+    "sphere"   equirectangular window of ``fov_deg`` degrees of longitude centred on the optical axis, the latitude range in the
+               grid's aspect ratio (clipped to +-90), or ``lon_lat`` = (lon0, lon1, lat0, lat1) in radians; fov_deg=360 on a 1:2 grid
+               is the full panorama;
+    "ortho"    parallel rays along the optical axis through a plane at the camera centre, ``ortho_width`` world units across the
+               frame's width (square pixels).
+    Pixel centres follow ``legacy`` (integer coordinates / + 0.5), c2w is that of ``target_ray_consts``."""
+    from . import hip
+    if name not in CAMERA_MODELS:
+        raise ValueError(f"camera model {name!r}: one of {CAMERA_MODELS}")
+    height, width = int(height), int(width)
+    if min(height, width) < 1:
+        raise ValueError(f"camera_model: grid {height}x{width}")
+    cam = hip.Camera()
+    cam.model, cam.height, cam.width, cam.legacy_coord = CAMERA_MODELS.index(name), height, width, int(bool(legacy))
+    cx, cy = ((width - 1) / 2.0, (height - 1) / 2.0) if legacy else (width / 2.0, height / 2.0)  # the frame's centre in pixel coordinates
+    if name == "pinhole" or (name == "fisheye" and fov_deg is None):
+        if intr33 is None:
+            raise ValueError(f"camera_model({name!r}): needs intr33" + (" or fov_deg" if name == "fisheye" else ""))
+        intr = intr33
+    elif name == "fisheye":
+        f = width / np.deg2rad(float(fov_deg))  # pixels per radian
+        intr = [[f, 0, cx], [0, f, cy], [0, 0, 1]]
+    elif name == "ortho":
+        if ortho_width is None or float(ortho_width) <= 0:
+            raise ValueError("camera_model('ortho'): needs ortho_width > 0 (world units across the frame)")
+        f = width / float(ortho_width)  # pixels per world unit
+        intr = [[f, 0, cx], [0, f, cy], [0, 0, 1]]
+    else:
+        intr = np.eye(3)
+    kinv, c2w = target_ray_consts(extr34, np.asarray(intr, np.float32), legacy)
+    hip._fill(cam.kinv, kinv)
+    hip._fill(cam.c2w, c2w)
+    if name == "sphere":
+        if lon_lat is None:
+            if fov_deg is None:
+                raise ValueError("camera_model('sphere'): needs fov_deg or lon_lat")
+            half_lon = np.deg2rad(float(fov_deg)) / 2
+            half_lat = min(half_lon * (height / width), np.pi / 2)
+            lon_lat = (-half_lon, half_lon, -half_lat, half_lat)
+        hip._fill(cam.lon_lat, lon_lat)
+    return cam
+
+
+def ray_bundle(origins, dirs):
+    """[N,3] world origins + [N,3] un-normalised world directions (tensors on the device) -> the ray bundle [N, 8] fp32 the
+    free-ray entry points take: ox oy oz 0 | dx dy dz 0 (32-byte rows; a fresh tensor, so 16-byte aligned)."""
+    if origins.shape != dirs.shape or origins.dim() != 2 or origins.shape[1] != 3:
+        raise ValueError(f"ray_bundle: origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)} must both be [N, 3]")
+    out = torch.zeros(origins.shape[0], 8, dtype=torch.float32, device=origins.device)
+    out[:, 0:3] = origins
+    out[:, 4:7] = dirs
+    return out

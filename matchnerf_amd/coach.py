@@ -504,6 +504,15 @@ class Coach:
             if metrics.batch_owner(bi, world) == rank:
                 yield bi, batch
 
+    def _require_pinhole(self, what, batch=None):
+        """Scored evaluation compares with the batch's target image, a pinhole photograph: another camera model (the option
+        nerf.render_camera, or a batch.tgt_camera) has no ground truth to be scored against - test_model_video renders those."""
+        spec = batch.get("tgt_camera") if batch is not None else getattr(self.opts.nerf, "render_camera", None)
+        name = spec.get("model") if isinstance(spec, dict) else spec
+        if name not in (None, "", "pinhole"):
+            raise ValueError(f"{what}: the target camera is {name!r}, but the ground truth it would be scored against is a pinhole "
+                             "image; render other camera models with nerf.render_video (test_model_video) or MatchNeRF.forward")
+
     def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True, device_lpips=None):
         """Render this rank's batches of ``loader`` in ``mode`` and score them -> rows float64 [n, 5] of ALL ranks' images in the
         order one process evaluates them: (batch index, image within the batch, PSNR, SSIM, LPIPS or NaN).
@@ -514,6 +523,7 @@ class Coach:
         the host (``metrics.psnr`` / ``EvalTools``).
         ``mask_of(gt_depth)`` -> the depth the invalid mask (depth == 0) comes from, or None for the 80 % centre crop.
         With a process group of more than one rank (``shard``), the ranks' rows travel in one ragged ``dist.gather_blocks``."""
+        self._require_pinhole("evaluation")
         rank, world = self._eval_world() if shard else (0, 1)
         on_device = str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled()
         dev = metrics.DeviceEval(device_lpips) if on_device else None
@@ -523,6 +533,7 @@ class Coach:
                 break
             var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
             gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
+            self._require_pinhole("evaluation", var)
             b, _, _, h, w = var.images.shape
             # scored against a ground truth of the batch's size: the option nerf.render_hw (videos) is not read here, and a batch
             # that names another grid cannot be scored
@@ -566,6 +577,7 @@ class Coach:
         strip written by rank bi % W, rank 0 logs and prints the one-process report (``first_only``, the sanity check, is rank 0's
         alone and runs no collective)."""
         assert hasattr(self, "val_loader"), "load_dataset(['val']) first"
+        self._require_pinhole("validate_model")
         from PIL import Image
         self.model.eval()
         out_dir = os.path.join(self.opts.output_path, "validation")
@@ -592,6 +604,7 @@ class Coach:
         `lpips` package are on disk (metrics.load_lpips: $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN or torch hub's cache), LPIPS.
         With a process group of more than one rank every rank calls this and renders batch bi when bi % W is its rank; rank 0 alone
         writes the results files and prints, every rank returns the one-process report and writes the images of its own share."""
+        self._require_pinhole("test_model")
         self.model.eval()
         lpips_fn, device_lpips = None, None
         if str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled() and metrics.device_lpips_enabled():
@@ -643,7 +656,8 @@ class Coach:
         names them: `<scene>_view<tgt>_src<ids>.gif` at 12 fps when nerf.save_gif, `..._f<i>.jpg` frames when nerf.save_frames, and
         the strip of source views `<name>.jpg` (PIL instead of imageio; the reference's .mp4 needs scikit-video / ffmpeg, neither in
         this image, and is skipped).  Frames have the rendered size: the views', or nerf.render_hw (optionally
-        supersampled: nerf.render_ssaa).  Returns {set: frames [F,h,w,3] uint8 of its FIRST batch element}."""
+        supersampled: nerf.render_ssaa), through the batch's pinhole camera or the model nerf.render_camera names (fisheye / sphere
+        with nerf.render_fov degrees, ortho with nerf.render_ortho_width world units: MatchNeRF.target_camera).  Returns {set: frames [F,h,w,3] uint8 of its FIRST batch element}."""
         from PIL import Image
         self.model.eval()
         out_root = os.path.join(self.opts.output_path, "test_videos")

@@ -36,6 +36,7 @@ extern "C" int64_t mnerf_struct_size(int32_t which) {
     case 8: return (int64_t)sizeof(mnerf_optim_row);
     case 9: return (int64_t)sizeof(mnerf_optim_group);
     case 10: return (int64_t)sizeof(mnerf_lpips_weights);
+    case MNERF_STRUCT_CAMERA: return (int64_t)sizeof(mnerf_camera);
     default: return -1;
   }
 }
@@ -52,6 +53,26 @@ int mnerf_rays_canonical(const mnerf_rays* rays, mnerf_rays* out, const char* wh
     MNERF_REQUIRE(rays->ray_begin >= 0 && (long long)rays->ray_begin + rays->n_rays <= (long long)out->tgt_height * out->tgt_width,
                   MNERF_E_RANGE, "%s: pixels [%d, %d + %d) outside the %dx%d target grid", who, rays->ray_begin, rays->ray_begin,
                   rays->n_rays, out->tgt_height, out->tgt_width);
+  return MNERF_OK;
+}
+
+int mnerf_free_rays_canonical(const mnerf_rays* rays, const float* ray_od, mnerf_rays* out, const char* who) {
+  MNERF_REQUIRE(rays, MNERF_E_NULL, "%s: rays is NULL", who);
+  MNERF_REQUIRE(!rays->ray_idx && !rays->pose_table, MNERF_E_UNSUPPORTED,
+                "%s: a ray bundle excludes ray_idx / pose_table (the bundle's rows are the rays)", who);
+  MNERF_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 1, MNERF_E_RANGE, "%s: n_rays=%d S=%d", who, rays->n_rays, rays->n_samples);
+  MNERF_REQUIRE(rays->legacy_coord == 0 || rays->n_samples >= 2, MNERF_E_RANGE, "%s: legacy depth sampling needs S >= 2", who);
+  if (rays->n_rays > 0) {
+    MNERF_REQUIRE(ray_od, MNERF_E_NULL, "%s: ray_od is NULL", who);
+    MNERF_REQUIRE(mnerf_aligned16(ray_od), MNERF_E_ALIGN, "%s: ray_od not 16B aligned", who);
+  }
+  mnerf_rays c = {};
+  c.n_rays = rays->n_rays, c.n_samples = rays->n_samples;
+  c.legacy_coord = rays->legacy_coord ? 1 : 0, c.depth_inverse = rays->depth_inverse ? 1 : 0;
+  c.height = c.tgt_height = rays->height, c.width = c.tgt_width = rays->width;
+  c.near_ = rays->near_, c.far_ = rays->far_;
+  c.strat_u = rays->strat_u;
+  *out = c;
   return MNERF_OK;
 }
 

@@ -53,6 +53,9 @@ bool mnerf_once_per_device(std::atomic<unsigned long long>& mask);
 // *out = *rays with the target grid made explicit (tgt_height / tgt_width = height / width where the caller left them 0) after
 // the range checks of include/mnerf.h "TARGET GRID"; the kernels read tgt_* unconditionally (api.cpp)
 int mnerf_rays_canonical(const mnerf_rays* rays, mnerf_rays* out, const char* who);
+// caller-supplied rays (include/mnerf.h "CALLER-SUPPLIED RAYS"): the checks of the rays struct and the bundle, and *out = the
+// canonical copy the kernels get - only the fields those entry points read, the target grid = the views' size (api.cpp)
+int mnerf_free_rays_canonical(const mnerf_rays* rays, const float* ray_od, mnerf_rays* out, const char* who);
 // argument checks of the scene / rays structs (cost_volume.hip)
 int mnerf_scene_check(const mnerf_scene* sc, const mnerf_rays* rays, const char* who);
 // fused ray-chunk form (decoder_fused.hip), used by mnerf_render_chunk (render_chunk.hip)
@@ -126,6 +129,17 @@ __device__ __forceinline__ RayGeom make_ray(const mnerf_rays& R, int ray_local) 
   g.rx = dot4h_chain(c0, c1, c2, R.c2w + 0) - g.cx;
   g.ry = dot4h_chain(c0, c1, c2, R.c2w + 4) - g.cy;
   g.rz = dot4h_chain(c0, c1, c2, R.c2w + 8) - g.cz;
+  return g;
+}
+
+// One caller-supplied ray (include/mnerf.h "CALLER-SUPPLIED RAYS"): row `ray` of a bundle, [ox oy oz 0 | dx dy dz 0], as two
+// 16-byte loads.  Everything downstream of a RayGeom (sample_depth, ray_point, project) is the code of the pixel rays.
+__device__ __forceinline__ RayGeom ray_from_bundle(const float* __restrict__ ray_od, int ray) {
+  const float4* p = reinterpret_cast<const float4*>(ray_od) + (size_t)ray * 2;
+  const float4 o = p[0], d = p[1];
+  RayGeom g;
+  g.cx = o.x, g.cy = o.y, g.cz = o.z;
+  g.rx = d.x, g.ry = d.y, g.rz = d.z;
   return g;
 }
 

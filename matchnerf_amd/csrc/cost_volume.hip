@@ -185,6 +185,8 @@ __host__ __device__ inline size_t cvw_lean_lds_floats(int nslot, int seg, int vi
 
 // ============================================================================ segment walk (stand-alone kernel)
 // The walk itself lives in cv_walk.hpp (shared with the fused ray-chunk kernel); this kernel maps slots to rays.
+// TWIN: cost_volume_lean_rays_kernel below repeats this kernel's slot mapping, LDS carve-up and XCD run partition for rays that
+// come from a bundle.  A change to any of them is made in BOTH (tests/test_free_rays_gpu.py holds the two together bit for bit).
 template <int CPL, bool UVPAIR = false, bool POSES = false>  // POSES: pose table (mnerf_rays.pose_table), one pose per block of 16 rays
 __global__ __launch_bounds__(256, (CPL == 16 ? 2 : CVW_WAVES)) void cost_volume_lean_kernel(mnerf_scene sc, mnerf_rays R,
                                                                                    int cond_stride,
@@ -236,6 +238,61 @@ __global__ __launch_bounds__(256, (CPL == 16 ? 2 : CVW_WAVES)) void cost_volume_
       cv_walk_unit<CPL, CVW_SEG, true, UVPAIR>(sc, R, ray, ray_live, j0, cond + ((size_t)ray * S + jrow) * cond_stride, cond_stride,
                                          uv_lds, wrec_lds, cs_lds, sub, pair_begin, pair_end);
     }
+  }
+}
+
+// The walk over a caller-supplied ray bundle (mnerf_cost_volume_rays): cost_volume_lean_kernel<CPL, UVPAIR, false> with the RayGeom of a
+// unit read from row `ray` of ray_od - a kernel argument of its own, no field of mnerf_rays - instead of rebuilt from a pixel.
+// A second entry symbol whose mapping code is a COPY of the kernel above (keep the two in step).  Sharing it was tried three ways -
+// one body behind both symbols taking the kernel arguments by reference, the same by value, and two __forceinline__ helpers for
+// the per-thread set-up and the per-iteration unit - and each time the pixel instances compiled to other code than the parent
+// commit's (<8, false, false> 5457 / 5460 / 5463-but-reordered instructions against 5463, <8, true, false> 5736 / 5743 / 5726
+// against 5750): the same arithmetic, another register allocation and schedule of the library's hottest non-MFMA kernel, which
+// would have to be re-measured.  With the copy every pre-existing instance is the parent's code, instruction for instruction.
+template <int CPL, bool UVPAIR>
+__global__ __launch_bounds__(256, (CPL == 16 ? 2 : CVW_WAVES)) void cost_volume_lean_rays_kernel(mnerf_scene sc, mnerf_rays R,
+                                                                                   int cond_stride,
+                                                                                   float* __restrict__ cond,
+                                                                                   int pair_begin, int pair_end,
+                                                                                   const float* __restrict__ ray_od) {
+  constexpr int LPS = FEAT_C / CPL;     // lanes per sample slot (8 or 16)
+  constexpr int NSLOT = 256 / LPS;      // ray slots per workgroup (32 or 16)
+  extern __shared__ __attribute__((aligned(16))) float cvw_smem[];
+  const int V = UVPAIR ? 2 : sc.n_views;  // views per sample kept in the slot's projection scratch
+  const int sub = threadIdx.x % LPS;
+  const int slot = threadIdx.x / LPS;                               // NSLOT adjacent rays
+  const int sumG = sc.n_group[0] + (sc.n_scales > 1 ? sc.n_group[1] : 0);
+  const int cs_stride = (sumG + 3) & ~3;                            // cosine sums per segment sample in LDS
+  // LDS per slot: projections [js][view](u,v) | walk records [js][view a|b][idx|weights] (float4) | cosine sums [js][cs]
+  // (the slots of a wave read their walk records / projections / cosine sums at the same offsets in one instruction, and slot
+  // strides of 96, 256 and 192 floats are all = 0 mod 32: the 4.6 conflict cycles per LDS instruction of round 3's PMC.  Padding
+  // the areas apart measured slower, see cvw_lean_lds_floats.)
+  const int uv_str = CVW_SEG * V * 2, cs_str = CVW_SEG * cs_stride;
+  float* uv_lds = cvw_smem + (size_t)slot * uv_str;
+  float4* wrec_lds = reinterpret_cast<float4*>(cvw_smem + (size_t)NSLOT * uv_str) + (size_t)slot * (CVW_SEG * 4);
+  float* cs_lds = cvw_smem + (size_t)NSLOT * (uv_str + CVW_SEG * 4 * 4) + slot * cs_str;
+  const int S = R.n_samples;
+  const int n_seg = (S + CVW_SEG - 1) / CVW_SEG;
+
+  // XCD-major contiguous runs of ray blocks (see cost_volume_kernel)
+  const int nwg = gridDim.x;
+  const int xcd = blockIdx.x & 7, lin = blockIdx.x >> 3;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin;
+  const long long blocks_total = ((long long)R.n_rays + NSLOT - 1) / NSLOT;
+  const long long b_begin = (long long)chunk * blocks_total / nwg;  // balanced contiguous runs (see cost_volume_kernel)
+  const long long b_end = (long long)(chunk + 1) * blocks_total / nwg;
+
+  for (long long it = b_begin * n_seg; it < b_end * n_seg; ++it) {
+    const long long rb = it / n_seg;
+    const int j0 = (int)(it - rb * n_seg) * CVW_SEG;
+    long long ray_ll = rb * NSLOT + slot;
+    const bool ray_live = ray_ll < R.n_rays;
+    if (!ray_live) ray_ll = R.n_rays - 1;
+    const int ray = (int)ray_ll;
+    const int jrow = j0 < S ? j0 : S - 1;
+    cv_walk_unit<CPL, CVW_SEG, true, UVPAIR, true>(sc, R, ray, ray_live, j0, cond + ((size_t)ray * S + jrow) * cond_stride, cond_stride,
+                                             uv_lds, wrec_lds, cs_lds, sub, pair_begin, pair_end, ray_od);
   }
 }
 
@@ -481,6 +538,15 @@ int mnerf_scene_check(const mnerf_scene* sc, const mnerf_rays* rays, const char*
   return MNERF_OK;
 }
 
+// A workgroup's LDS is NSLOT x SEG x (2 V + 16 + cs) floats: 38 KiB at 3 views (four workgroups per CU, what 128 VGPRs
+// allow), 52 KiB at 10 views (three).  From the view count at which the fourth workgroup no longer fits, the 16-lane form
+// keeps only the current pair's projections (UVPAIR, cv_walk.hpp).
+static bool cv_walk16_uvpair(const mnerf_scene* scene, int sumG) {
+  bool uvpair = cvw_lean_lds_floats(16, CVW_SEG, scene->n_views, (sumG + 3) & ~3) * sizeof(float) > 40 * 1024;
+  if (mnerf_tune().cv_uvpair >= 0) uvpair = mnerf_tune().cv_uvpair != 0;
+  return uvpair;
+}
+
 // Which kernel a scene gets: variant 3 / 4 = segment walk with 16 / 8 lanes per sample, 5 = texel tiles, 0 = one sample per slot
 // iteration; uvpair = the 16-lane walk that keeps only the current pair's projections (many views).
 static void cv_pick_kernel(const mnerf_scene* scene, int sumG, int* variant_out, bool* uvpair_out) {
@@ -492,12 +558,7 @@ static void cv_pick_kernel(const mnerf_scene* scene, int sumG, int* variant_out,
     for (int s = 0; s < scene->n_scales; ++s) ok = ok && scene->n_group[s] >= 2;
     if (!ok) variant = 3;
   }
-  // A workgroup's LDS is NSLOT x SEG x (2 V + 16 + cs) floats: 38 KiB at 3 views (four workgroups per CU, what 128 VGPRs
-  // allow), 52 KiB at 10 views (three).  From the view count at which the fourth workgroup no longer fits, the 16-lane form
-  // keeps only the current pair's projections (UVPAIR, cv_walk.hpp).
-  bool uvpair = variant == 3 && cvw_lean_lds_floats(16, CVW_SEG, scene->n_views, (sumG + 3) & ~3) * sizeof(float) > 40 * 1024;
-  if (variant == 3 && mnerf_tune().cv_uvpair >= 0) uvpair = mnerf_tune().cv_uvpair != 0;
-  *variant_out = variant, *uvpair_out = uvpair;
+  *variant_out = variant, *uvpair_out = variant == 3 && cv_walk16_uvpair(scene, sumG);
 }
 
 // One instance of the segment walk.  Its dynamic-LDS cap is set once per device to the most the launch's own check admits (a
@@ -511,6 +572,16 @@ static void launch_lean(unsigned wgs, size_t lds, void* stream, const mnerf_scen
                               160 * 1024);
   hipLaunchKernelGGL((cost_volume_lean_kernel<CPL, UVPAIR, POSES>), dim3(wgs), dim3(256), lds, (hipStream_t)stream, *scene, *rays,
                      cond_stride, cond, pair_begin, pair_end);
+}
+template <int CPL, bool UVPAIR>
+static void launch_lean_rays(unsigned wgs, size_t lds, void* stream, const mnerf_scene* scene, const mnerf_rays* rays,
+                             int cond_stride, float* cond, int pair_begin, int pair_end, const float* ray_od) {
+  static std::atomic<unsigned long long> attr_set{0};
+  if (mnerf_once_per_device(attr_set))
+    (void)hipFuncSetAttribute((const void*)cost_volume_lean_rays_kernel<CPL, UVPAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+  hipLaunchKernelGGL((cost_volume_lean_rays_kernel<CPL, UVPAIR>), dim3(wgs), dim3(256), lds, (hipStream_t)stream, *scene, *rays,
+                     cond_stride, cond, pair_begin, pair_end, ray_od);
 }
 
 // the pose-table instance of the cost volume is the 16-lane walk with all views' projections resident (<= 5 views)
@@ -607,4 +678,40 @@ extern "C" int mnerf_cost_volume(const mnerf_scene* scene, const mnerf_rays* ray
                        *scene, *rays, cond_stride, cond);
   }
   return mnerf_check_launch("mnerf_cost_volume");
+}
+
+// K1+K2 over a caller-supplied bundle (include/mnerf.h "CALLER-SUPPLIED RAYS"): the 16-lane segment walk with its RayGeom read
+// from ray_od (cost_volume_lean_rays_kernel) - <8, false> with all views' projections resident, <8, true> in pair blocks for many
+// views, chosen by the rule of mnerf_cost_volume.  The rows are those of mnerf_cost_volume for the same rays, bit for bit.
+extern "C" int mnerf_cost_volume_rays(const mnerf_scene* scene, const mnerf_rays* rays_in, const float* ray_od,
+                                      int32_t cond_stride, float* cond, void* stream) {
+  mnerf_rays canon;
+  int rc = mnerf_free_rays_canonical(rays_in, ray_od, &canon, "mnerf_cost_volume_rays");
+  if (rc) return rc;
+  const mnerf_rays* rays = &canon;
+  rc = mnerf_scene_check(scene, rays, "mnerf_cost_volume_rays");
+  if (rc) return rc;
+  const int sumG = scene->n_group[0] + (scene->n_scales > 1 ? scene->n_group[1] : 0);
+  MNERF_REQUIRE(cond_stride >= sumG + 4 * scene->n_views + 1, MNERF_E_RANGE,
+                "mnerf_cost_volume_rays: cond_stride=%d < cond_dim+1=%d", cond_stride, sumG + 4 * scene->n_views + 1);
+  MNERF_REQUIRE(sumG <= CVW_CS_MAX, MNERF_E_UNSUPPORTED,
+                "mnerf_cost_volume_rays: the segment walk holds at most %d cosine sums per sample, the scene has %d", CVW_CS_MAX, sumG);
+  const bool uvpair = cv_walk16_uvpair(scene, sumG);
+  const size_t lds = cvw_lean_lds_floats(16, CVW_SEG, uvpair ? 2 : scene->n_views, (sumG + 3) & ~3) * sizeof(float);
+  MNERF_REQUIRE(lds <= 160 * 1024, MNERF_E_UNSUPPORTED, "mnerf_cost_volume_rays: %d views need %zu B of LDS", scene->n_views, lds);
+  if (rays->n_rays == 0) return MNERF_OK;
+  MNERF_REQUIRE(cond, MNERF_E_NULL, "mnerf_cost_volume_rays: cond is NULL");
+  long long wgs = ((long long)rays->n_rays + 15) / 16;  // one block of 16 rays per workgroup (see mnerf_cost_volume)
+  if (mnerf_tune().cv_grid > 0 && wgs > mnerf_tune().cv_grid) wgs = mnerf_tune().cv_grid;
+  const int n_pairs = scene->n_views * (scene->n_views - 1) / 2;
+  if (uvpair) {
+    const int pb = mnerf_tune().cv_pair_block;
+    const int blk = pb > 0 ? pb : (pb < 0 ? 8 : n_pairs);
+    for (int p0 = 0; p0 < n_pairs; p0 += blk)
+      launch_lean_rays<8, true>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, p0,
+                                p0 + blk < n_pairs ? p0 + blk : n_pairs, ray_od);
+  } else {
+    launch_lean_rays<8, false>((unsigned)wgs, lds, stream, scene, rays, cond_stride, cond, 0, n_pairs, ray_od);
+  }
+  return mnerf_check_launch("mnerf_cost_volume_rays");
 }

@@ -393,17 +393,28 @@ __device__ __forceinline__ void cv_store(float* p, float v) {
   *p = v;
 }
 
+// the ray of a walk unit.  FREE: row `ray` of a caller-supplied bundle (ray_from_bundle; `ray` is the already clamped index, so
+// a dead slot reads the last row) instead of the pixel ray rebuilt from R
+template <bool FREE>
+__device__ __forceinline__ RayGeom cv_ray(const mnerf_rays& R, int ray, const float* __restrict__ ray_od) {
+  if constexpr (FREE)
+    return ray_from_bundle(ray_od, ray);
+  else
+    return make_ray(R, ray);
+}
+
 // pass 1 of a walk unit: projections (to uv_lds), colours, masks and the constant column of SEG samples of one ray
-template <int CPL, int SEG, bool NT>
+template <int CPL, int SEG, bool NT, bool FREE = false>
 __device__ __forceinline__ void cv_pass1(const mnerf_scene& sc, const mnerf_rays& R, int ray, bool ray_live, int j0,
-                                         float* __restrict__ row0, int cond_stride, float* __restrict__ uv_lds, int sub) {
+                                         float* __restrict__ row0, int cond_stride, float* __restrict__ uv_lds, int sub,
+                                         const float* __restrict__ ray_od = nullptr) {
   constexpr int LPS = FEAT_C / CPL;
   constexpr int SPL = SEG / LPS > 0 ? SEG / LPS : 1;  // pass-1 samples per lane
   const int V = sc.n_views;
   const int S = R.n_samples;
   const int sumG = sc.n_group[0] + (sc.n_scales > 1 ? sc.n_group[1] : 0);
   const float wm1 = (float)(R.width - 1), hm1 = (float)(R.height - 1);
-  const RayGeom g = make_ray(R, ray);
+  const RayGeom g = cv_ray<FREE>(R, ray, ray_od);
   // ---- pass 1: projections, tap records, colours, masks.  Lane `sub` takes samples sub, sub+LPS, ..
 #pragma unroll
   for (int half = 0; half < SPL; ++half) {
@@ -470,11 +481,13 @@ __device__ __forceinline__ void cv_write_cosines(const mnerf_rays& R, bool ray_l
 // (cost_volume.hip: 8 pairs = 210 MB of maps): the first block also does pass 1, every block continues the per-sample cosine
 // sums where the previous one stopped — they travel through the rows' cosine columns as RAW sums, the last block scales them
 // by 1 / pairs — so every sum is still accumulated pair by pair in the reference's order: same bits as one launch.
-template <int CPL, int SEG, bool NT = false, bool UVPAIR = false>
+// FREE: the unit's ray comes from a caller-supplied bundle (cv_ray); everything after the RayGeom is the same code.
+template <int CPL, int SEG, bool NT = false, bool UVPAIR = false, bool FREE = false>
 __device__ __forceinline__ void cv_walk_unit(const mnerf_scene& sc, const mnerf_rays& R, int ray, bool ray_live, int j0,
                                              float* __restrict__ row0, int cond_stride, float* __restrict__ uv_lds,
                                              float4* __restrict__ wrec_lds, float* __restrict__ cs_lds, int sub,
-                                             int pair_begin = 0, int pair_end = 0x7fffffff) {
+                                             int pair_begin = 0, int pair_end = 0x7fffffff,
+                                             const float* __restrict__ ray_od = nullptr) {
   constexpr int LPS = FEAT_C / CPL;
   constexpr int SPL = SEG / LPS > 0 ? SEG / LPS : 1;  // pass-1 samples per lane
   const int V = sc.n_views;
@@ -487,7 +500,7 @@ __device__ __forceinline__ void cv_walk_unit(const mnerf_scene& sc, const mnerf_
 
   const bool first_block = pair_begin <= 0, last_block = pair_end >= V * (V - 1) / 2;
   if (first_block) {
-    cv_pass1<CPL, SEG, NT>(sc, R, ray, ray_live, j0, row0, cond_stride, UVPAIR ? nullptr : uv_lds, sub);
+    cv_pass1<CPL, SEG, NT, FREE>(sc, R, ray, ray_live, j0, row0, cond_stride, UVPAIR ? nullptr : uv_lds, sub, ray_od);
     for (int i = sub; i < SEG * cs_stride; i += LPS) cs_lds[i] = 0.0f;  // this slot's cosine sums
   } else {
     static_assert(UVPAIR || SEG > 0, "");
@@ -511,7 +524,7 @@ __device__ __forceinline__ void cv_walk_unit(const mnerf_scene& sc, const mnerf_
       if (p < pair_begin || p >= pair_end) continue;  // not in this launch's pair block
       if constexpr (UVPAIR) {  // this pair's two projections of every sample of the segment (cv_pass1's arithmetic)
         const float wm1 = (float)(R.width - 1), hm1 = (float)(R.height - 1);
-        const RayGeom g = make_ray(R, ray);
+        const RayGeom g = cv_ray<FREE>(R, ray, ray_od);
         cvw_handoff();  // the previous pair's records have been expanded
 #pragma unroll
         for (int half = 0; half < SPL; ++half) {

@@ -144,6 +144,15 @@ def _source_features(model, ref_images, encoder):
     raise ValueError(f"encoder={encoder!r}: expected 'recompute' or 'shared'")
 
 
+def _require_pinhole(model, batch, mode, who):
+    """Sharded rendering has no ray-bundle form: a target camera other than the batch's pinhole one (``batch.tgt_camera`` or the
+    option nerf.render_camera, ``MatchNeRF.target_camera``) is refused on every rank, before the encoder and any collective."""
+    spec = model.target_camera(batch, mode)
+    if spec is not None:
+        raise NotImplementedError(f"{who}: a {spec['model']} target camera renders a ray bundle, which is not sharded; "
+                                  "render it on one GPU (MatchNeRF.forward)")
+
+
 def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
     """BASELINE config[3], row-tile form: every rank renders its contiguous band of rows of the target view through the HIP
     path, and ONE all_gather returns the [rays_local, 5] tiles (rgb, depth, opacity) to all ranks.  -> edict(rgb [B,HW,3],
@@ -155,6 +164,7 @@ def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
         raise ValueError(f"encoder={encoder!r}: expected 'recompute' or 'shared'")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
+    _require_pinhole(model, batch, mode, "render_frame_sharded")
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)
     tgt_pose, ref_poses = model.extract_poses(batch)
@@ -182,6 +192,7 @@ def render_views_sharded(model, batch, poses, mode="test", encoder="shared"):
         raise ValueError(f"encoder={encoder!r}: expected 'recompute' or 'shared'")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
+    _require_pinhole(model, batch, mode, "render_views_sharded")
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)
     _, ref_poses = model.extract_poses(batch)

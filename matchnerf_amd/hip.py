@@ -17,6 +17,9 @@ import numpy as np
 
 MNERF_ABI_VERSION = 12
 MNERF_POSE_FLOATS = 24  # floats of one row of mnerf_rays.pose_table
+MNERF_RAY_FLOATS = 8  # floats of one row of a ray bundle: ox oy oz 0 | dx dy dz 0
+CAM_PINHOLE, CAM_FISHEYE, CAM_SPHERE, CAM_ORTHO = 0, 1, 2, 3  # mnerf_camera.model (MNERF_CAM_*)
+STRUCT_CAMERA = 32  # MNERF_STRUCT_CAMERA: mnerf_struct_size()'s index of mnerf_camera
 MNERF_OK, MNERF_E_NULL, MNERF_E_RANGE, MNERF_E_UNSUPPORTED, MNERF_E_ALIGN = 0, -1, -2, -3, -4  # include/mnerf.h
 MNERF_MAX_VIEWS = 16
 MNERF_COND_STRIDE_MAX, MNERF_COND_STRIDE_MAX_F32 = 96, 64
@@ -107,6 +110,13 @@ class LpipsWeightTable(C.Structure):
                 ("ew", C.c_int32 * LPIPS_LAYERS)]
 
 
+class Camera(C.Structure):
+    """struct mnerf_camera: a camera model that fills a ray bundle on the device (mnerf_camera_rays; camera.camera_model builds it).
+    The header passes it as an untyped pointer, so it is no member of STRUCTS; load() checks its size under STRUCT_CAMERA."""
+    _fields_ = [("model", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("legacy_coord", C.c_int32),
+                ("kinv", C.c_float * 9), ("c2w", C.c_float * 12), ("lon_lat", C.c_float * 4)]
+
+
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8  # MNERF_OPTIM_CHUNK, MNERF_OPTIM_MAX_GROUPS
 
 
@@ -154,6 +164,11 @@ SIGNATURES = {
     "mnerf_render_chunk": (_int, [_P(Scene), _P(Decoder), _P(Rays)] + [_vp] * 5),
     "mnerf_render_chunk_fused": (_int, [_P(Scene), _P(Decoder), _P(Rays)] + [_vp] * 4),
     "mnerf_box_downsample": (_int, [_vp] + [_i32] * 4 + [_vp] * 2),
+    "mnerf_cost_volume_rays": (_int, [_P(Scene), _P(Rays), _vp, _i32, _vp, _vp]),
+    "mnerf_ray_samples_rays": (_int, [_P(Rays), _vp, _P(View)] + [_vp] * 5),
+    "mnerf_render_rays_workspace_bytes": (_i64, [_i32] * 3),
+    "mnerf_render_rays": (_int, [_P(Scene), _P(Decoder), _P(Rays)] + [_vp] * 6),
+    "mnerf_camera_rays": (_int, [_vp, _i32, _i32, _vp, _vp]),  # const void* camera: a Camera by reference
     "mnerf_composite_backward": (_int, [_i32] * 2 + [_vp] * 4 + [_i32] * 2 + [_vp] * 6),
     "mnerf_cost_volume_backward": (_int, [_P(Scene), _P(Rays), _i32] + [_vp] * 4),
     "mnerf_debug_set_knob": (_int, [C.c_char_p, _int, _P(_int)]),
@@ -246,6 +261,8 @@ def load():
         if lib.mnerf_struct_size(which) != C.sizeof(st):
             raise MnerfError(f"struct {st.__name__}: library says {lib.mnerf_struct_size(which)} bytes, "
                              f"ctypes mirror has {C.sizeof(st)}")
+    if lib.mnerf_struct_size(STRUCT_CAMERA) != C.sizeof(Camera):
+        raise MnerfError(f"struct Camera: library says {lib.mnerf_struct_size(STRUCT_CAMERA)} bytes, ctypes mirror has {C.sizeof(Camera)}")
     _LIB = lib
     return lib
 
@@ -682,6 +699,94 @@ def render_chunk(scene, dec, rays, workspace, rgb, depth, opacity, stream=None, 
 
 def render_workspace_bytes(n_rays, n_samples, cond_stride):
     return int(load().mnerf_render_workspace_bytes(n_rays, n_samples, cond_stride))
+
+
+# ----------------------------------------------------------------------- caller-supplied rays (include/mnerf.h)
+
+
+def make_free_rays(n_rays, n_samples, height, width, near, far, legacy=True, depth_inverse=False, strat_u_ptr=None):
+    """The mnerf_rays of a launch over a ray bundle: only the fields those entry points read (``height`` / ``width``: the SOURCE
+    views' size; the sample parameters t come from near / far / n_samples as for pixel rays)."""
+    return make_rays(n_rays, n_samples, height, width, np.zeros(9, np.float32), np.zeros(12, np.float32), near, far, legacy=legacy,
+                     depth_inverse=depth_inverse, strat_u_ptr=strat_u_ptr)
+
+
+def _bundle(ray_od, n_rays):
+    _f32c(ray_od, "ray_od")
+    if ray_od.numel() < n_rays * MNERF_RAY_FLOATS:
+        raise MnerfError(f"ray_od {tuple(ray_od.shape)} holds fewer than {n_rays} rows of {MNERF_RAY_FLOATS} floats")
+    return ray_od
+
+
+def camera_rays(cam, pixel_begin=0, n_pixels=None, out=None, device=None, stream=None):
+    """Rows of a ray bundle for pixels [pixel_begin, pixel_begin + n_pixels) of a camera model (``camera.camera_model``;
+    mnerf_camera_rays) -> [n_pixels, 8] fp32 on the device: ox oy oz 0 | dx dy dz 0."""
+    import torch
+    lib = load()
+    if n_pixels is None:
+        n_pixels = cam.height * cam.width - int(pixel_begin)
+    if out is None:
+        out = torch.empty(int(n_pixels), MNERF_RAY_FLOATS, device=torch.device(device) if device is not None else _current_device())
+    _bundle(out, int(n_pixels))
+    with _on(out.device, stream) as st:
+        check(lib.mnerf_camera_rays(C.byref(cam), int(pixel_begin), int(n_pixels), _ptr(out), st), "mnerf_camera_rays")
+    return out
+
+
+def cost_volume_rays(scene, rays, ray_od, cond_stride, out=None, stream=None):
+    """K1+K2 over a ray bundle (mnerf_cost_volume_rays) -> cond [n_rays*S, cond_stride]: the rows of ``cost_volume``."""
+    import torch
+    lib = load()
+    _bundle(ray_od, rays.n_rays)
+    if out is None:
+        out = torch.empty(rays.n_rays * rays.n_samples, cond_stride, device=ray_od.device)
+    with _on(ray_od.device, stream) as st:
+        check(lib.mnerf_cost_volume_rays(C.byref(scene), C.byref(rays), _ptr(ray_od), int(cond_stride), _ptr(out), st),
+              "mnerf_cost_volume_rays")
+    return out
+
+
+def ray_samples_rays(rays, ray_od, view0, stream=None):
+    """Per-sample geometry of a bundle (mnerf_ray_samples_rays) -> x_ndc [R,S,3], dir [R,S,3], depth_s [R,S], ray_len [R]."""
+    import torch
+    lib = load()
+    _bundle(ray_od, rays.n_rays)
+    r, s, dev = rays.n_rays, rays.n_samples, ray_od.device
+    x_ndc, dirs = torch.empty(r, s, 3, device=dev), torch.empty(r, s, 3, device=dev)
+    depth_s, ray_len = torch.empty(r, s, device=dev), torch.empty(r, device=dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_ray_samples_rays(C.byref(rays), _ptr(ray_od), C.byref(view0), _ptr(x_ndc), _ptr(dirs), _ptr(depth_s),
+                                         _ptr(ray_len), st), "mnerf_ray_samples_rays")
+    return x_ndc, dirs, depth_s, ray_len
+
+
+def render_rays_workspace_bytes(n_rays, n_samples, cond_stride):
+    return int(load().mnerf_render_rays_workspace_bytes(int(n_rays), int(n_samples), int(cond_stride)))
+
+
+def render_rays_workspace_views(workspace, n_rays, n_samples, cond_stride):
+    """The areas of a ``render_rays`` workspace (a float32 tensor) as views, in the layout include/mnerf.h documents:
+    cond | x_ndc | dir | depth_s | rgb_s | sigma | ray_len, each area starting 16-byte aligned."""
+    n = n_rays * n_samples
+    out, at = {}, 0
+    for name, count, shape in (("cond", n * cond_stride, (n, cond_stride)), ("x_ndc", n * 3, (n_rays, n_samples, 3)),
+                               ("dir", n * 3, (n_rays, n_samples, 3)), ("depth_s", n, (n_rays, n_samples)),
+                               ("rgb_s", n * 3, (n_rays, n_samples, 3)), ("sigma", n, (n_rays, n_samples)),
+                               ("ray_len", n_rays, (n_rays,))):
+        out[name] = workspace[at:at + count].view(shape)
+        at += (count + 3) & ~3
+    assert at * 4 == render_rays_workspace_bytes(n_rays, n_samples, cond_stride), (at, n_rays, n_samples, cond_stride)
+    return out
+
+
+def render_rays(scene, dec, rays, ray_od, workspace, rgb, depth, opacity, stream=None):
+    """One render chunk over a ray bundle (mnerf_render_rays): writes rgb [R,3], depth [R], opacity [R] in place; the per-sample
+    stages stay in ``workspace`` (``render_rays_workspace_views``)."""
+    lib = load()
+    _bundle(ray_od, rays.n_rays)
+    with _on(rgb.device, stream) as st:
+        check(lib.mnerf_render_rays(C.byref(scene), C.byref(dec), C.byref(rays), _ptr(ray_od), _ptr(workspace), _ptr(rgb),
+                                    _ptr(depth), _ptr(opacity), st), "mnerf_render_rays")
 
 
 def wa_math():

@@ -84,6 +84,10 @@ class MatchNeRF(torch.nn.Module):
         if mode == "train" and (tgt_hw != (img_h, img_w) or ssaa != 1):  # (before the first launch)
             raise NotImplementedError(f"mode='train' renders at the views' size {(img_h, img_w)}, not at {tgt_hw} x ssaa {ssaa}: "
                                       "the ground truth has the batch's size")
+        tgt_camera = self.target_camera(batch, mode)  # None: the batch's pinhole camera, today's path
+        if tgt_camera is not None and mode == "train":  # (before the first launch)
+            raise NotImplementedError(f"a {tgt_camera['model']} target camera renders caller-supplied rays, which are inference only "
+                                      f"(mode={mode!r})")
         ref_feats_list = self.get_img_feat(ref_images, attn_splits_list=self.opts.encoder.attn_splits_list,
                                            cur_n_src_views=self.n_src_views)
 
@@ -99,7 +103,8 @@ class MatchNeRF(torch.nn.Module):
         if render_video and self.pose_batching:
             # small frames: as many poses per launch as fill one (mnerf_rays.pose_table); None where the kernels or the
             # frame size do not take a table -> the pose loop below
-            frames = None if ssaa > 1 else self.render_poses(self.opts, poses_paths, ref_poses=ref_poses, ref_images=ref_images,
+            # (a pose table holds pinhole constants: another camera model goes pose by pose through its ray bundle)
+            frames = None if (ssaa > 1 or tgt_camera is not None) else self.render_poses(self.opts, poses_paths, ref_poses=ref_poses, ref_images=ref_images,
                                                              ref_feats_list=ref_feats_list, tgt_hw=tgt_hw)
             if frames is not None:
                 for k, v in frames.items():  # [n_poses, B, N, C] -> the reference's frame-major [n_poses * B, N, C]
@@ -109,7 +114,10 @@ class MatchNeRF(torch.nn.Module):
                     frames_done[k] = v
                 poses_paths = []
         for cur_tgt_pose in poses_paths:
-            if mode_rand_rays and mode in ["train", "test-optim"]:
+            if tgt_camera is not None:
+                ret = self.render_camera(self.opts, cur_tgt_pose, tgt_camera, tgt_hw, ssaa=ssaa, mode=mode, ref_poses=ref_poses,
+                                         ref_images=ref_images, ref_feats_list=ref_feats_list)
+            elif mode_rand_rays and mode in ["train", "test-optim"]:
                 batch.ray_idx = torch.randperm(img_h * img_w, device=ref_images.device)[:mode_rand_rays // batch_size]
                 ret = self.render(self.opts, cur_tgt_pose, ray_idx=batch.ray_idx, mode=mode, ref_poses=ref_poses,
                                   ref_images=ref_images, ref_feats_list=ref_feats_list, tgt_hw=tgt_hw, ssaa=ssaa)
@@ -196,6 +204,28 @@ class MatchNeRF(torch.nn.Module):
         if min(tgt_hw) < 1 or not 1 <= ssaa <= 8:
             raise ValueError(f"target grid {tgt_hw}, ssaa={ssaa}: sizes >= 1 and 1 <= ssaa <= 8")
         return tgt_pose, tgt_hw, ssaa
+
+    def target_camera(self, batch, mode):
+        """The camera MODEL of the target view -> None for the batch's pinhole camera (the pixel path), else a dict(model=...,
+        fov_deg=..., ortho_width=..., lon_lat=...) for ``camera.camera_model``: ``batch.tgt_camera`` (a dict, or a model name), else
+        in modes 'test' / 'val' the options ``nerf.render_camera`` = pinhole | fisheye | sphere | ortho with ``nerf.render_fov``
+        (degrees, fisheye / sphere) and ``nerf.render_ortho_width`` (world units, ortho).  The pose, near / far and - for a fisheye
+        without a field of view - the intrinsics stay the batch's target view's."""
+        spec = batch.get("tgt_camera") if hasattr(batch, "get") else None
+        if spec is None and mode in ("test", "val"):
+            name = getattr(self.opts.nerf, "render_camera", None)
+            if name:
+                spec = dict(model=name, fov_deg=getattr(self.opts.nerf, "render_fov", None),
+                            ortho_width=getattr(self.opts.nerf, "render_ortho_width", None))
+        if spec is None:
+            return None
+        spec = dict(model=spec) if isinstance(spec, str) else dict(spec)
+        if spec.get("model") not in camera.CAMERA_MODELS:
+            raise ValueError(f"target camera model {spec.get('model')!r}: one of {camera.CAMERA_MODELS}")
+        unknown = set(spec) - {"model", "fov_deg", "ortho_width", "lon_lat"}
+        if unknown:
+            raise ValueError(f"target camera: unknown keys {sorted(unknown)}")
+        return None if spec["model"] == "pinhole" else spec
 
     # ------------------------------------------------------------------ encoder (matchnerf.py:183-207)
     def get_img_feat(self, imgs, attn_splits_list=None, cur_n_src_views=3):
@@ -413,6 +443,80 @@ class MatchNeRF(torch.nn.Module):
                          ray_range=(k * k * pix0, k * k * n), tgt_hw=(k * h, k * w))
         return edict({key: torch.stack([hip.box_downsample(v[b], rows, w, k).reshape(n, -1) for b in range(v.shape[0])], 0)
                       for key, v in hi.items()})
+
+    # ------------------------------------------------------------------ caller-supplied rays (include/mnerf.h)
+    def render_rays(self, opt, ray_o, ray_d, near_far, mode=None, ref_poses=None, ref_images=None, ref_feats_list=None):
+        """Arbitrary rays -> edict(rgb [B,N,3], depth [B,N,1], opacity [B,N,1]).  ``ray_o`` / ``ray_d``: world origins and
+        un-normalised world directions, [B,N,3] or [N,3] (shared by the batch), on the device; ``near_far`` [B,2] (or [2]): the
+        range of the sample parameter t along o + t d (with unit directions t, and the returned depth, are Euclidean distances).
+        Chunks of MAX_RAYS_PER_LAUNCH through one workspace (mnerf_render_rays); results do not depend on the chunking.  Honours
+        ``nerf_setbg_opaque``.  Inference only."""
+        batch_size = ref_images.shape[0]
+        self._inference_only(mode, ref_feats_list, "render_rays")
+        if not ref_images.is_cuda:
+            raise RuntimeError("MatchNeRF.render_rays: the HIP render path needs CUDA tensors (no CPU fallback)")
+        device = ref_images.device
+        ray_o, ray_d = (torch.as_tensor(t, dtype=torch.float32, device=device) for t in (ray_o, ray_d))
+        if ray_o.shape != ray_d.shape or ray_o.shape[-1] != 3 or ray_o.dim() not in (2, 3):
+            raise ValueError(f"render_rays: ray_o {tuple(ray_o.shape)} / ray_d {tuple(ray_d.shape)}: both [B,N,3] or [N,3]")
+        if ray_o.dim() == 3 and ray_o.shape[0] != batch_size:
+            raise ValueError(f"render_rays: {ray_o.shape[0]} ray sets for a batch of {batch_size}")
+        if ray_o.dim() == 2:
+            shared = camera.ray_bundle(ray_o, ray_d)
+            bundles = [shared] * batch_size
+        else:
+            bundles = [camera.ray_bundle(ray_o[b], ray_d[b]) for b in range(batch_size)]
+        nf = np.broadcast_to(self._host(torch.as_tensor(near_far)).reshape(-1, 2), (batch_size, 2))
+        return self._render_bundles(opt, bundles, nf, ref_poses, ref_images, ref_feats_list)
+
+    def _inference_only(self, mode, ref_feats_list, who):
+        needs_grad = torch.is_grad_enabled() and (any(f.requires_grad for f in ref_feats_list) or
+                                                  any(p.requires_grad for p in self._dec().parameters()))
+        if needs_grad or mode == "train":  # (before the first launch)
+            raise NotImplementedError(f"{who}: caller-supplied rays are inference only (no backward kernels over a ray bundle); "
+                                      "call it under torch.no_grad() and outside mode='train'")
+
+    def _render_bundles(self, opt, bundles, near_far_host, ref_poses, ref_images, ref_feats_list):
+        """``bundles``: per batch element a ray bundle [N, 8] on the device -> edict(rgb, depth, opacity)."""
+        batch_size, _, _, img_h, img_w = ref_images.shape
+        device = ref_images.device
+        n_samples = int(opt.nerf.sample_intvs)
+        n_rays = int(bundles[0].shape[0])
+        ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
+        dec = self._decoder(n_samples, device)
+        chunk = max(1, min(n_rays, MAX_RAYS_PER_LAUNCH))
+        ws = self._workspace(hip.render_rays_workspace_bytes(chunk, n_samples, dec.cond_stride) // 4, device)
+        rgb = torch.empty(batch_size, n_rays, 3, device=device)
+        depth = torch.empty(batch_size, n_rays, 1, device=device)
+        opacity = torch.empty(batch_size, n_rays, 1, device=device)
+        for b in range(batch_size):
+            sc = self._scene(b, ref_host, ref_feats_list, images_cl)
+            for c in range(0, n_rays, chunk):
+                m = min(chunk, n_rays - c)
+                rays = hip.make_free_rays(m, n_samples, img_h, img_w, near_far_host[b, 0], near_far_host[b, 1],
+                                          legacy=bool(opt.nerf.legacy_coord), depth_inverse=(opt.nerf.depth.param == "inverse"))
+                hip.render_rays(sc, dec, rays, bundles[b][c:c + m], ws, rgb[b, c:c + m], depth[b, c:c + m], opacity[b, c:c + m])
+        return edict(rgb=rgb, depth=depth, opacity=opacity)
+
+    def render_camera(self, opt, tgt_pose, tgt_camera, tgt_hw, ssaa=1, mode=None, ref_poses=None, ref_images=None,
+                      ref_feats_list=None):
+        """A full (h, w) frame of a target CAMERA MODEL (``target_camera``) at ``tgt_pose``: the camera fills a ray bundle on the
+        device (``hip.camera_rays``), the bundle is rendered as caller-supplied rays.  ``ssaa`` = k > 1: the bundle of the same
+        camera on the (k h, k w) grid, box-filtered on the device."""
+        self._inference_only(mode, ref_feats_list, "render_camera")
+        h, w = int(tgt_hw[0]), int(tgt_hw[1])
+        k = int(ssaa)
+        legacy = bool(opt.nerf.legacy_coord)
+        batch_size = ref_images.shape[0]
+        tgt_ex, tgt_in, tgt_nf = self._tgt_host(self.resize_pose(tgt_pose, (h, w), (k * h, k * w), legacy))
+        args = {key: tgt_camera.get(key) for key in ("fov_deg", "ortho_width", "lon_lat")}
+        bundles = [hip.camera_rays(camera.camera_model(tgt_camera["model"], k * h, k * w, tgt_ex[b], tgt_in[b], legacy, **args),
+                                   device=ref_images.device) for b in range(batch_size)]
+        out = self._render_bundles(opt, bundles, np.asarray(tgt_nf).reshape(batch_size, 2), ref_poses, ref_images, ref_feats_list)
+        if k == 1:
+            return out
+        return edict({key: torch.stack([hip.box_downsample(v[b], h, w, k).reshape(h * w, -1) for b in range(batch_size)], 0)
+                      for key, v in out.items()})
 
     def render_poses(self, opt, poses, ref_poses=None, ref_images=None, ref_feats_list=None, tgt_hw=None):
         """Full frames of SEVERAL target poses of one source set (the video loop of matchnerf.py:42-71) with as many poses per

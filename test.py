@@ -13,7 +13,14 @@ Several GPUs: in a process without ``WORLD_SIZE``, ``--gpu_ids`` longer than one
 through train.py's launcher (the launching process never touches a GPU); under ``torchrun`` the ranks it is given are used as they
 are.  Batch ``bi`` of every test set is rendered and scored by rank ``bi % W``; rank 0 assembles the report of a one-process run and
 alone writes ``0results_<set>.txt``; every rank writes the images of its own share.  ``MNERF_FORCE_DEVICE=0
-MNERF_DIST_BACKEND=gloo`` runs all ranks on one GPU (dry runs, tests).  Video paths (``nerf.render_video``) are not sharded."""
+MNERF_DIST_BACKEND=gloo`` runs all ranks on one GPU (dry runs, tests).  Video paths (``nerf.render_video``) are not sharded.
+
+Video frames may come from another camera model than the batch's pinhole camera (``MatchNeRF.target_camera``):
+
+    python test.py --yaml=demo_own --nerf.render_camera=sphere --nerf.render_fov=60 --nerf.render_hw=128,256
+
+``--nerf.render_camera=pinhole|fisheye|sphere|ortho``, ``--nerf.render_fov=<degrees>`` (fisheye / sphere),
+``--nerf.render_ortho_width=<world units>`` (ortho).  Scored evaluation refuses them: its ground truth is a pinhole image."""
 import os
 import sys
 
@@ -31,6 +38,10 @@ def run(argv):
     opt = options.set(opt_cmd=options.parse_arguments(argv), make_output_dir=rank == 0, verbose=rank == 0)
     if device is not None and not opt.cpu:
         opt.device = str(device)  # the rank's device is init_from_env's (MNERF_FORCE_DEVICE)
+    cam = getattr(opt.nerf, "render_camera", None)
+    if cam not in (None, "", "pinhole") and not opt.nerf.render_video:  # (before anything is built)
+        raise SystemExit(f"test.py: nerf.render_camera={cam} renders video frames (nerf.render_video); scored evaluation compares "
+                         "with pinhole ground truth")
     if rank == 0:
         options.save_options_file(opt)
     dist.barrier()  # the output directory exists before any rank goes on
