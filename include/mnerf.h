@@ -54,6 +54,8 @@
  *       MNERF_RAY_FLOATS floats per ray, mnerf_cost_volume_rays, mnerf_ray_samples_rays, mnerf_render_rays_workspace_bytes,
  *       mnerf_render_rays, and the camera models that fill a bundle on the device: mnerf_camera - struct index
  *       MNERF_STRUCT_CAMERA -, mnerf_camera_rays.
+ *       Added under v12 without a layout change: geometry export (matchnerf_amd/csrc/fusion.hip) - mnerf_depth_consistency,
+ *       mnerf_point_cloud_workspace_bytes, mnerf_point_cloud, mnerf_depth_colormap.  No new struct: poses travel as mnerf_view.
  */
 #ifndef MNERF_H_
 #define MNERF_H_
@@ -828,6 +830,71 @@ int64_t mnerf_lpips_head_slots(int32_t h, int32_t w);
 int mnerf_lpips_head(const float* feat_a, const float* feat_b, const float* head_w, int32_t channels, int32_t h, int32_t w,
                      double* slots, void* stream);
 int mnerf_lpips_sum(const double* slots, int64_t image_stride, int32_t n_slots, int32_t n_images, double* out, void* stream);
+
+/* GEOMETRY EXPORT (added under v12 without a layout change; matchnerf_amd/csrc/fusion.hip): depth maps rendered at several poses of
+ * one encoded scene, filtered by cross-view consistency (the MVSNet criterion) and back-projected into one coloured point cloud; and
+ * the colour map of the reference's depth panels.  The ray transformer makes a sample's density depend on all samples of its ray, so
+ * a density grid has no meaning here; a rendered depth map has.  The geometry is pinhole camera-z depth: what a render returns for
+ * pixel rays with depth.param = metric (their camera-z is 1).  Replaces nothing in the reference, which shows depth (coach.py:404-408,
+ * 497-505) but exports none.  Enqueue-only on `stream`; every argument check precedes any HIP call; no floating-point atomics and no
+ * atomic cursor: two runs give the same bits.  Poses travel as mnerf_view (HOST arrays, read during the call; in the kernel
+ * arguments by value): world->camera extr, the intr of THIS height x width grid, near_ / far_ = the valid depth range.  The host
+ * inverts intr and extr's [R|t] in double ([R^-1 | -R^-1 t], 3x3 adjugates) and casts to fp32; the device chain is fp32 with the
+ * k-ordered FMA products of the projection code:
+ *   lift(view, x, y, z)   cam = kinv (x, y, 1) as for pixel rays, each component times z, world = c2w [cam; 1]
+ *   proj(view, world)     c = extr [world; 1], q = intr c  ->  (q0 / q2, q1 / q2, q2): pixel coordinates and camera-z
+ * Pixel centres are the integer coordinates with legacy_coord and + 0.5 otherwise; pixel index = y * width + x.
+ *
+ * mnerf_depth_consistency - one thread per pixel p = (x, y) of view `ref`:
+ *   depth          device [n_views][height][width] fp32;  opacity: the same shape, or NULL
+ *   value of a pixel of view k: z = depth (opacity NULL) or depth / opacity, the normalised expected depth; VALID iff (opacity NULL
+ *   or opacity >= min_opacity) and z is finite and views[k].near_ <= z <= views[k].far_
+ *   p invalid: n_consistent = 0, fused_depth = 0.  Otherwise P = lift(ref, p, z) and, for every j != ref in ascending order:
+ *     (u, v, zj) = proj(j, P); j is skipped if zj <= 0 or (u, v) lies outside the rectangle of view j's pixel centres;
+ *     dj = the bilinear value of view j at (u, v): with (fx, fy) = (u, v) - centre offset, x0 = min(floor(fx), width - 2) (0 for a
+ *     width of 1), x1 = min(x0 + 1, width - 1), ax = fx - x0, rows alike; the FOUR taps (x0|x1, y0|y1) are normalised by their own
+ *     opacities and must all be valid (whatever their weights), else j is skipped; dj = top + ay (bot - top) with
+ *     top = z00 + ax (z10 - z00), bot = z01 + ax (z11 - z01), each a + t b one FMA;
+ *     (x', y', d') = proj(ref, lift(j, u, v, dj)); j is CONSISTENT iff hypot(x' - x, y' - y) < px_tol and |d' - z| < rel_tol z
+ *   n_consistent [height][width] int32 = the number of consistent j; fused_depth [height][width] = (z + sum of their d') / (1 + n),
+ *   added in the order of j.
+ * MNERF_E_RANGE: n_views outside 2..MNERF_MAX_VIEWS, ref outside the views, height or width below 1 or height x width >= 2^31, a
+ * px_tol or rel_tol that is not finite and positive, a min_opacity that is not finite (read only with opacity), a singular intr or
+ * extr.  MNERF_E_NULL: views, depth, fused_depth or n_consistent missing. */
+int mnerf_depth_consistency(const mnerf_view* views, int32_t n_views, int32_t ref, int32_t height, int32_t width, int32_t legacy_coord,
+                            const float* depth, const float* opacity, float px_tol, float rel_tol, float min_opacity,
+                            float* fused_depth, int32_t* n_consistent, void* stream);
+
+/* mnerf_point_cloud - the selected pixels of one view as rows of a point buffer, in pixel order (a stable compaction):
+ *   selected       n_consistent[i] >= min_consistent and depth[i] finite and > 0 (pass the fused depth)
+ *   points         device, rows of 32 bytes, 16-byte aligned (MNERF_E_ALIGN otherwise): x y z d | r g b n - the row size of a ray
+ *                  bundle -, xyz = lift(view, pixel centre, depth), d the depth, rgb the pixel's colour from rgb [height x width][3],
+ *                  n the count as a float
+ *   count          device, one int64: the number of selected pixels.  Rows at or beyond `capacity` are not written and the call is
+ *                  still MNERF_OK: a caller sizes one buffer (height x width rows always suffice), copies count once and trims
+ *   workspace      device, 4-byte aligned, mnerf_point_cloud_workspace_bytes(height x width) bytes; scratch only
+ * Four launches: every workgroup of 256 pixels counts its selected pixels with wave ballots; the counts are scanned in tiles of
+ * 1024 by one workgroup each; one workgroup scans the tile totals and writes count; every workgroup writes its rows at its base +
+ * the ballot prefix of each pixel.  Integer arithmetic only: the rows and their order are the same bits on every run.
+ * height x width == 0 is MNERF_OK and touches no buffer (count included).  MNERF_E_RANGE: a negative size, height x width >= 2^31, a
+ * negative capacity, a singular intr or extr.  MNERF_E_NULL: view, depth, rgb, n_consistent, count or workspace missing, or points with
+ * capacity > 0.
+ * mnerf_point_cloud_workspace_bytes: host only; 4 (ceil(n / 256) + ceil(n / 262144)) rounded up to 16; 0 for 0 pixels, -1 for a
+ * negative count. */
+int64_t mnerf_point_cloud_workspace_bytes(int64_t n_pixels);
+int mnerf_point_cloud(const mnerf_view* view, int32_t height, int32_t width, int32_t legacy_coord, const float* depth, const float* rgb,
+                      const int32_t* n_consistent, int32_t min_consistent, float* points, int64_t capacity, int64_t* count,
+                      void* workspace, void* stream);
+
+/* mnerf_depth_colormap - depth [n] fp32 -> rgb [n][3] bytes, the arithmetic of visualize_depth (misc/utils.py:323-341) in fp32:
+ *   NaN becomes 0;  t = (d - lo) / fp32(hi - lo + 1e-8) (the denominator formed in double);  index = 255 t truncated towards zero and
+ *   CLAMPED to 0..255 (anything not above 0 is 0).  numpy's cast to uint8 wraps out-of-range values instead; the clamp is deliberate.
+ * then the JET map as a formula, with s = index / 255:
+ *   r = clamp(1.5 - |4 s - 3|), g = clamp(1.5 - |4 s - 2|), b = clamp(1.5 - |4 s - 1|) on [0, 1], times 255 and rounded half up -
+ *   evaluated exactly in integers: r = clamp(383 - |4 index - 765|, 0, 255), g with 510, b with 255.
+ * This is the classic piecewise-linear JET, not OpenCV's 256-entry table (cv2.applyColorMap): parity with that table is unpinned.
+ * n == 0 is MNERF_OK and touches no buffer.  MNERF_E_RANGE: n < 0, lo or hi not finite.  MNERF_E_NULL: depth or rgb missing. */
+int mnerf_depth_colormap(const float* depth, int64_t n, float lo, float hi, uint8_t* rgb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -513,7 +513,8 @@ class Coach:
             raise ValueError(f"{what}: the target camera is {name!r}, but the ground truth it would be scored against is a pinhole "
                              "image; render other camera models with nerf.render_video (test_model_video) or MatchNeRF.forward")
 
-    def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True, device_lpips=None):
+    def _evaluate(self, loader, mode, mask_of, on_frame=None, lpips_fn=None, first_only=False, shard=True, device_lpips=None,
+                  depth_panels=False):
         """Render this rank's batches of ``loader`` in ``mode`` and score them -> rows float64 [n, 5] of ALL ranks' images in the
         order one process evaluates them: (batch index, image within the batch, PSNR, SSIM, LPIPS or NaN).
         On CUDA with ``metrics.device_metrics_enabled()`` PSNR / SSIM are rows of ``metrics.DeviceEval`` (csrc/metrics.hip) and reach
@@ -522,7 +523,9 @@ class Coach:
         fifth column of the same rows (csrc/lpips.hip) and no frame leaves the device for it.  Otherwise every frame is scored on
         the host (``metrics.psnr`` / ``EvalTools``).
         ``mask_of(gt_depth)`` -> the depth the invalid mask (depth == 0) comes from, or None for the 80 % centre crop.
-        With a process group of more than one rank (``shard``), the ranks' rows travel in one ragged ``dist.gather_blocks``."""
+        With a process group of more than one rank (``shard``), the ranks' rows travel in one ragged ``dist.gather_blocks``.
+        ``depth_panels`` (vis_depth): ``on_frame`` gets a sixth argument, the frame's colour-mapped depth [h, w, 3] uint8
+        (``_depth_panels``)."""
         self._require_pinhole("evaluation")
         rank, world = self._eval_world() if shard else (0, 1)
         on_device = str(self.opts.device).startswith("cuda") and metrics.device_metrics_enabled()
@@ -543,6 +546,8 @@ class Coach:
             var = self.model(var, mode=mode)
             depth = mask_of(gt_depth)
             frames = None
+            panels = self._depth_panels(var.depth.reshape(b, h, w), batch["near_fars"][:, -1]) if depth_panels and on_frame is not None \
+                else None
             if dev is None or on_frame is not None or lpips_fn is not None:
                 frames = (var.rgb.reshape(b, h, w, 3).cpu().numpy(), var.images[:, -1].permute(0, 2, 3, 1).cpu().numpy())
             if dev is not None:
@@ -559,7 +564,7 @@ class Coach:
                 if lpips_fn is not None:
                     lpips_of[(bi, i)] = tools.get_metrics(["LPIPS"])["LPIPS"]
                 if on_frame is not None:
-                    on_frame(batch, bi, i, pred, gt)
+                    on_frame(batch, bi, i, pred, gt, *(() if panels is None else (panels[i],)))
         if dev is not None:
             keys, got = dev.finish()  # the one copy of this loader
             last = got[:, 4:5] if dev.lpips is not None else np.full((len(keys), 1), np.nan)
@@ -569,6 +574,15 @@ class Coach:
         for j in range(len(rows) if lpips_of else 0):
             rows[j, 4] = lpips_of.get((int(rows[j, 0]), int(rows[j, 1])), np.nan)
         return metrics.gather_rows(rows, device=self.opts.device) if world > 1 else metrics.merge_rows(rows)
+
+    def _depth_panels(self, depth, near_fars):
+        """vis_depth: depth [B, ..., h, w] float32 on the device -> uint8 [B, ..., h, w, 3] on the host, colour-mapped on the device
+        (hip.depth_colormap: the arithmetic of the reference's visualize_depth, misc/utils.py:323-341) with minmax = element b's
+        ``near_fars[b]``, as coach.py:404-408 / 497-505 pass it."""
+        from . import hip
+        near_fars = torch.as_tensor(near_fars).detach().cpu().numpy()
+        return np.stack([hip.depth_colormap(depth[b].contiguous().float(), float(near_fars[b, 0]), float(near_fars[b, 1])).cpu().numpy()
+                         for b in range(depth.shape[0])], 0)
 
     @torch.no_grad()
     def validate_model(self, first_only=False):
@@ -602,6 +616,7 @@ class Coach:
     def test_model(self, save_images=False, **kwargs):
         """coach.py:368-453 -> {dataset: {image_id: psnr}}; the results file also lists SSIM and, when the two weight files of the
         `lpips` package are on disk (metrics.load_lpips: $MNERF_LPIPS_VGG16 / $MNERF_LPIPS_LIN or torch hub's cache), LPIPS.
+        ``save_images`` writes prediction | ground truth strips, with vis_depth depth | prediction | ground truth (coach.py:404-408).
         With a process group of more than one rank every rank calls this and renders batch bi when bi % W is its rank; rank 0 alone
         writes the results files and prints, every rank returns the one-process report and writes the images of its own share."""
         self._require_pinhole("test_model")
@@ -628,13 +643,15 @@ class Coach:
             name = loader.get_name()
             self.model.nerf_setbg_opaque = (name == "blender")  # coach.py:382-383
 
-            def save(batch, bi, i, pred, gt, name=name):
+            def save(batch, bi, i, pred, gt, depth_vis=None, name=name):
                 from PIL import Image
-                vis = np.concatenate([pred, gt], 1)
-                Image.fromarray((vis.clip(0, 1) * 255).astype("uint8")).save(os.path.join(out_root, f"{name}_{bi:03d}_{i}.png"))
+                vis = (np.concatenate([pred, gt], 1).clip(0, 1) * 255).astype("uint8")
+                if depth_vis is not None:  # vis_depth: depth | pred | gt (coach.py:404-408)
+                    vis = np.concatenate([depth_vis, vis], 1)
+                Image.fromarray(vis).save(os.path.join(out_root, f"{name}_{bi:03d}_{i}.png"))
 
             rows = self._evaluate(loader, "test", lambda d: d, on_frame=save if save_images else None, lpips_fn=lpips_fn,
-                                  device_lpips=device_lpips)
+                                  device_lpips=device_lpips, depth_panels=bool(getattr(self.opts, "vis_depth", False)))
             self.model.nerf_setbg_opaque = False
             report[name] = {f"{name}_{int(r[0]):03d}_{int(r[1])}": float(r[2]) for r in rows}
             ssims = [float(r[3]) for r in rows]
@@ -655,7 +672,7 @@ class Coach:
         interpolate, llff: spiral; white background for blender), written under <output_path>/test_videos/<set>/ as the reference
         names them: `<scene>_view<tgt>_src<ids>.gif` at 12 fps when nerf.save_gif, `..._f<i>.jpg` frames when nerf.save_frames, and
         the strip of source views `<name>.jpg` (PIL instead of imageio; the reference's .mp4 needs scikit-video / ffmpeg, neither in
-        this image, and is skipped).  Frames have the rendered size: the views', or nerf.render_hw (optionally
+        this image, and is skipped).  With vis_depth every frame is rgb | depth (coach.py:497-505).  Frames have the rendered size: the views', or nerf.render_hw (optionally
         supersampled: nerf.render_ssaa), through the batch's pinhole camera or the model nerf.render_camera names (fisheye / sphere
         with nerf.render_fov degrees, ortho with nerf.render_ortho_width world units: MatchNeRF.target_camera).  Returns {set: frames [F,h,w,3] uint8 of its FIRST batch element}."""
         from PIL import Image
@@ -686,14 +703,19 @@ class Coach:
                     self._warned_render_video = True
                 if getattr(self.opts, "vis_depth", False) and not getattr(self, "_warned_vis_depth", False):
                     import warnings
-                    warnings.warn("test_model_video: vis_depth (depth maps next to the frames, coach.py:497-505) and the .mp4 "
-                                  "container (skvideo, coach.py:511-525) are not written: frames / GIF / source strip only")
+                    warnings.warn("test_model_video: the .mp4 container (skvideo, coach.py:511-525) is not written: frames / GIF / "
+                                  "source strip only")
                     self._warned_vis_depth = True
                 b = var.images.shape[0]
                 h, w = self.model.target_grid(var, "test", self.model.extract_poses(var)[0], var.images.shape[-2:])[1]  # nerf.render_hw
                 var = self.model(var, mode="test", render_video=True, render_path_mode=mode)
                 # forward returns the reference's frame-major layout [n_frames * B, h*w, 3] at the rendered size
                 frames = (var.rgb.reshape(n_frames, b, h, w, 3).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+                if getattr(self.opts, "vis_depth", False):  # rgb | depth, the depth panel on the right (coach.py:497-505)
+                    # (forward hands video frames over on the host: the depths go back for the colour map, [B, F, h, w])
+                    depth = var.depth.reshape(n_frames, b, h, w).to(self.opts.device).transpose(0, 1)
+                    panels = self._depth_panels(depth, batch["near_fars"][:, -1])
+                    frames = np.concatenate([frames, panels.transpose(1, 0, 2, 3, 4)], axis=3)
                 for bi in range(b):
                     clip = frames[:, bi]
                     videos.setdefault(name, clip)
@@ -710,3 +732,51 @@ class Coach:
                     Image.fromarray(np.concatenate(list(src), axis=1)).save(os.path.join(out_dir, f"{stem}.jpg"))
             self.model.nerf_setbg_opaque = False
         return videos
+
+    @torch.no_grad()
+    def export_geometry(self, views=None, **kwargs):
+        """Every batch of every test set as a coloured point cloud (MatchNeRF.export_points: depth maps rendered at the fusion poses,
+        kept where other poses confirm them) -> <output_path>/geometry/<set>/<stem>.ply, binary little-endian, float xyz + uchar rgb,
+        with the stems of ``test_model_video``; with vis_depth also one colour-mapped depth map per fusion view, <stem>_depth<k>.png
+        (minmax = the target's near_fars, as the reference's depth panels).  ``views``: 'sources' | 'path' (default: the option
+        nerf.export_geometry, else 'sources'); thresholds from nerf.fuse_px_tol / fuse_rel_tol / fuse_min_opacity / fuse_min_views
+        where given.  One process (not sharded).  Returns {set: [path of every .ply]}."""
+        from PIL import Image
+
+        from . import fusion
+        self.model.eval()
+        views = views or getattr(self.opts.nerf, "export_geometry", None) or "sources"
+        if views is True:
+            views = "sources"
+        fuse_args = {arg: getattr(self.opts.nerf, name) for arg, name in (("px_tol", "fuse_px_tol"), ("rel_tol", "fuse_rel_tol"),
+                                                                          ("min_opacity", "fuse_min_opacity"),
+                                                                          ("min_consistent", "fuse_min_views"))
+                     if getattr(self.opts.nerf, name, None) is not None}
+        out_root = os.path.join(self.opts.output_path, "geometry")
+        written = {}
+        for loader in self.test_loaders:
+            name = loader.get_name()
+            out_dir = os.path.join(out_root, name)
+            os.makedirs(out_dir, exist_ok=True)
+            mode = "interpolate"
+            if name == "llff":
+                mode = "spiral"
+            elif name == "colmap":
+                mode = getattr(getattr(self.opts.data_test, "colmap", {}), "render_path_mode", "interpolate")
+            self.model.nerf_setbg_opaque = (name == "blender")
+            for batch in loader:
+                var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+                clouds, maps = self.model.export_points(var, views=views, render_path_mode=mode, return_maps=True, **fuse_args)
+                panels = self._depth_panels(maps.depth, batch["near_fars"][:, -1]) if getattr(self.opts, "vis_depth", False) else None
+                for bi, cloud in enumerate(clouds):
+                    ids = [int(x) for x in batch["view_ids"][bi]] if "view_ids" in batch else list(range(self.n_src_views + 1))
+                    scene = batch["scene"][bi] if "scene" in batch else f"scene{bi}"
+                    stem = f"{scene}_view{ids[-1]:02d}_src" + "_".join(f"{x:02d}" for x in ids[:self.n_src_views])
+                    path = os.path.join(out_dir, f"{stem}.ply")
+                    n = fusion.write_ply(path, cloud)
+                    written.setdefault(name, []).append(path)
+                    self.say(f"[coach] {name}: {n} points -> {path}")
+                    for k in range(panels.shape[1] if panels is not None else 0):
+                        Image.fromarray(panels[bi, k]).save(os.path.join(out_dir, f"{stem}_depth{k}.png"))
+            self.model.nerf_setbg_opaque = False
+        return written

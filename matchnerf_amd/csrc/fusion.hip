@@ -1,0 +1,364 @@
+// Geometry export (include/mnerf.h "GEOMETRY EXPORT"): cross-view consistency of rendered depth maps, the stable compaction of the
+// surviving pixels into a coloured point cloud, and the colour map of the depth panels.
+//
+// All three are memory-bound kernels of one thread per pixel, consecutive threads on consecutive pixels:
+//   depth_consistency_kernel   per pixel of the reference view and per partner: two projections, four taps, two more projections
+//   point_count / point_scan / point_total / point_scatter   wave ballots + a two-level scan of the workgroups' counts: the rows
+//                              come out in pixel order without an atomic cursor, so that two runs give the same bits
+//   depth_colormap_kernel      one load, three byte stores
+// The cameras travel by value in the kernel arguments (as mnerf_scene's views do): 16 x 44 floats.
+#include <math.h>
+
+#include "common.hpp"
+
+// every operation rounds on its own; the FMAs are the explicit ones of the helpers (common.hpp)
+#pragma clang fp contract(off)
+
+struct FusionCam {
+  mnerf_view v;     // world -> camera, intrinsics, valid depth range
+  float kinv[9];    // intr^-1, inverted in double on the host
+  float c2w[12];    // [R^-1 | -R^-1 t], inverted in double on the host
+};
+struct FusionCams {
+  FusionCam cam[MNERF_MAX_VIEWS];
+};
+
+// pixel-centre coordinates (x, y) at camera-z `z` -> world
+__device__ __forceinline__ void fusion_lift(const FusionCam& c, float x, float y, float z, float& wx, float& wy, float& wz) {
+  // cam = [x y 1] @ Kinv^T, the chain of make_ray; then every component times the depth
+  const float c0 = (__builtin_fmaf(y, c.kinv[1], x * c.kinv[0]) + c.kinv[2]) * z;
+  const float c1 = (__builtin_fmaf(y, c.kinv[4], x * c.kinv[3]) + c.kinv[5]) * z;
+  const float c2 = (__builtin_fmaf(y, c.kinv[7], x * c.kinv[6]) + c.kinv[8]) * z;
+  wx = dot4h_chain(c0, c1, c2, c.c2w + 0);
+  wy = dot4h_chain(c0, c1, c2, c.c2w + 4);
+  wz = dot4h_chain(c0, c1, c2, c.c2w + 8);
+}
+
+// world -> pixel coordinates and camera-z (project() of common.hpp without the normalisations)
+__device__ __forceinline__ void fusion_project(const FusionCam& c, float wx, float wy, float wz, float& u, float& v, float& z) {
+  const float c0 = dot4h_chain(wx, wy, wz, c.v.extr + 0);
+  const float c1 = dot4h_chain(wx, wy, wz, c.v.extr + 4);
+  const float c2 = dot4h_chain(wx, wy, wz, c.v.extr + 8);
+  const float q0 = dot3_chain(c0, c1, c2, c.v.intr + 0);
+  const float q1 = dot3_chain(c0, c1, c2, c.v.intr + 3);
+  const float q2 = dot3_chain(c0, c1, c2, c.v.intr + 6);
+  u = q0 / q2;
+  v = q1 / q2;
+  z = q2;
+}
+
+// the value of pixel `i` of view `k`'s map: normalised by the opacity where one is given; false = invalid
+__device__ __forceinline__ bool fusion_value(const float* __restrict__ depth, const float* __restrict__ opacity, size_t i,
+                                             float min_opacity, float near_, float far_, float& z) {
+  z = depth[i];
+  if (opacity) {
+    const float o = opacity[i];
+    if (!(o >= min_opacity)) return false;  // a NaN opacity is invalid
+    z = z / o;
+  }
+  return isfinite(z) && z >= near_ && z <= far_;
+}
+
+__global__ __launch_bounds__(256) void depth_consistency_kernel(FusionCams cams, int n_views, int ref, int height, int width,
+                                                                int legacy_coord, const float* __restrict__ depth,
+                                                                const float* __restrict__ opacity, float px_tol, float rel_tol,
+                                                                float min_opacity, float* __restrict__ fused_depth,
+                                                                int* __restrict__ n_consistent) {
+  const long long n = (long long)height * width;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int py = (int)(i / width), px = (int)(i - (long long)py * width);
+  const float off = legacy_coord ? 0.0f : 0.5f;
+  const float x = (float)px + off, y = (float)py + off;
+  const FusionCam& R = cams.cam[ref];
+  float z;
+  if (!fusion_value(depth, opacity, (size_t)ref * n + i, min_opacity, R.v.near_, R.v.far_, z)) {
+    n_consistent[i] = 0;
+    fused_depth[i] = 0.0f;
+    return;
+  }
+  float wx, wy, wz;
+  fusion_lift(R, x, y, z, wx, wy, wz);
+  const float u_hi = (float)(width - 1) + off, v_hi = (float)(height - 1) + off;
+  int count = 0;
+  float sum = z;
+  for (int j = 0; j < n_views; ++j) {  // (wave-uniform: the cameras are read through scalar loads)
+    if (j == ref) continue;
+    const FusionCam& J = cams.cam[j];
+    float u, v, zj;
+    fusion_project(J, wx, wy, wz, u, v, zj);
+    if (!(zj > 0.0f) || !(u >= off && u <= u_hi && v >= off && v <= v_hi)) continue;
+    const float fx = u - off, fy = v - off;
+    int x0 = min((int)floorf(fx), width - 2), y0 = min((int)floorf(fy), height - 2);
+    x0 = max(x0, 0), y0 = max(y0, 0);
+    const int x1 = min(x0 + 1, width - 1), y1 = min(y0 + 1, height - 1);
+    const float ax = fx - (float)x0, ay = fy - (float)y0;
+    const size_t base = (size_t)j * n;
+    float z00, z10, z01, z11;
+    bool ok = fusion_value(depth, opacity, base + (size_t)y0 * width + x0, min_opacity, J.v.near_, J.v.far_, z00);
+    ok &= fusion_value(depth, opacity, base + (size_t)y0 * width + x1, min_opacity, J.v.near_, J.v.far_, z10);
+    ok &= fusion_value(depth, opacity, base + (size_t)y1 * width + x0, min_opacity, J.v.near_, J.v.far_, z01);
+    ok &= fusion_value(depth, opacity, base + (size_t)y1 * width + x1, min_opacity, J.v.near_, J.v.far_, z11);
+    if (!ok) continue;
+    const float top = __builtin_fmaf(ax, z10 - z00, z00);
+    const float bot = __builtin_fmaf(ax, z11 - z01, z01);
+    const float dj = __builtin_fmaf(ay, bot - top, top);
+    float bx, by, bz, xr, yr, dr;
+    fusion_lift(J, u, v, dj, bx, by, bz);
+    fusion_project(R, bx, by, bz, xr, yr, dr);
+    const float ex = xr - x, ey = yr - y;
+    const float err = sqrtf(ex * ex + ey * ey);
+    if (err < px_tol && fabsf(dr - z) < rel_tol * z) {
+      ++count;
+      sum = sum + dr;
+    }
+  }
+  n_consistent[i] = count;
+  fused_depth[i] = sum / (float)(1 + count);
+}
+
+// ------------------------------------------------------------------------------------------------ host: inverse cameras
+static bool invert3(const double* m, double* inv) {  // row-major 3x3 by the adjugate
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+  if (!(fabs(det) > 0.0) || !std::isfinite(det)) return false;
+  const double r = 1.0 / det;
+  inv[0] = c00 * r, inv[1] = (m[2] * m[7] - m[1] * m[8]) * r, inv[2] = (m[1] * m[5] - m[2] * m[4]) * r;
+  inv[3] = c01 * r, inv[4] = (m[0] * m[8] - m[2] * m[6]) * r, inv[5] = (m[2] * m[3] - m[0] * m[5]) * r;
+  inv[6] = c02 * r, inv[7] = (m[1] * m[6] - m[0] * m[7]) * r, inv[8] = (m[0] * m[4] - m[1] * m[3]) * r;
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(inv[k])) return false;
+  return true;
+}
+
+static bool fusion_cam(const mnerf_view& v, FusionCam* out) {
+  double k[9], ki[9], r[9], ri[9];
+  for (int i = 0; i < 9; ++i) k[i] = v.intr[i];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) r[i * 3 + j] = v.extr[i * 4 + j];
+  if (!invert3(k, ki) || !invert3(r, ri)) return false;
+  out->v = v;
+  for (int i = 0; i < 9; ++i) out->kinv[i] = (float)ki[i];
+  for (int i = 0; i < 3; ++i) {
+    double t = 0.0;
+    for (int j = 0; j < 3; ++j) {
+      out->c2w[i * 4 + j] = (float)ri[i * 3 + j];
+      t -= ri[i * 3 + j] * (double)v.extr[j * 4 + 3];
+    }
+    out->c2w[i * 4 + 3] = (float)t;
+  }
+  return true;
+}
+
+extern "C" int mnerf_depth_consistency(const mnerf_view* views, int32_t n_views, int32_t ref, int32_t height, int32_t width,
+                                       int32_t legacy_coord, const float* depth, const float* opacity, float px_tol, float rel_tol,
+                                       float min_opacity, float* fused_depth, int32_t* n_consistent, void* stream) {
+  MNERF_REQUIRE(n_views >= 2 && n_views <= MNERF_MAX_VIEWS, MNERF_E_RANGE, "mnerf_depth_consistency: n_views=%d outside 2..%d", n_views,
+                MNERF_MAX_VIEWS);
+  MNERF_REQUIRE(ref >= 0 && ref < n_views, MNERF_E_RANGE, "mnerf_depth_consistency: ref=%d outside the %d views", ref, n_views);
+  MNERF_REQUIRE(height >= 1 && width >= 1 && (long long)height * width < (1ll << 31), MNERF_E_RANGE,
+                "mnerf_depth_consistency: grid %dx%d", height, width);
+  MNERF_REQUIRE(std::isfinite(px_tol) && px_tol > 0.0f && std::isfinite(rel_tol) && rel_tol > 0.0f, MNERF_E_RANGE,
+                "mnerf_depth_consistency: px_tol=%g rel_tol=%g must be finite and positive", (double)px_tol, (double)rel_tol);
+  MNERF_REQUIRE(!opacity || std::isfinite(min_opacity), MNERF_E_RANGE, "mnerf_depth_consistency: min_opacity=%g", (double)min_opacity);
+  MNERF_REQUIRE(views, MNERF_E_NULL, "mnerf_depth_consistency: views is NULL");
+  MNERF_REQUIRE(depth && fused_depth && n_consistent, MNERF_E_NULL, "mnerf_depth_consistency: NULL depth / fused_depth / n_consistent");
+  FusionCams cams = {};
+  for (int k = 0; k < n_views; ++k)
+    MNERF_REQUIRE(fusion_cam(views[k], &cams.cam[k]), MNERF_E_RANGE, "mnerf_depth_consistency: view %d has a singular intr or extr", k);
+  const long long n = (long long)height * width;
+  hipLaunchKernelGGL(depth_consistency_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cams, n_views, ref,
+                     height, width, legacy_coord ? 1 : 0, depth, opacity, px_tol, rel_tol, min_opacity, fused_depth, n_consistent);
+  return mnerf_check_launch("mnerf_depth_consistency");
+}
+
+// ------------------------------------------------------------------------------------------------ point cloud
+// Workspace: int32 counts[n_blocks] (after point_scan_kernel: the exclusive prefix inside the block's tile) | int32 tiles[n_tiles]
+// (the tiles' totals, after point_total_kernel their exclusive prefix).  Every prefix is below 2^31 (height x width is).
+constexpr int PC_BLOCK = 256;    // pixels per workgroup of the count / scatter kernels
+constexpr int PC_TILE = 1024;    // counts per workgroup of the scan: 256 threads x 4
+
+__device__ __forceinline__ bool point_selected(const float* __restrict__ depth, const int* __restrict__ n_consistent,
+                                               int min_consistent, long long i, long long n) {
+  if (i >= n) return false;
+  if (n_consistent[i] < min_consistent) return false;
+  const float d = depth[i];
+  return isfinite(d) && d > 0.0f;
+}
+
+// selected pixels before this lane in the workgroup (ballots + the waves' totals through LDS); `total` = the workgroup's count
+__device__ __forceinline__ int block_prefix(bool flag, int& total) {
+  __shared__ int wave_count[PC_BLOCK / 64];
+  const unsigned long long mask = __ballot(flag);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int before = __popcll(mask & ((1ull << lane) - 1ull));
+  if (lane == 0) wave_count[wave] = __popcll(mask);
+  __syncthreads();
+  int base = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < PC_BLOCK / 64; ++w) {
+    const int c = wave_count[w];
+    base += w < wave ? c : 0;
+    total += c;
+  }
+  return base + before;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void point_count_kernel(const float* __restrict__ depth, const int* __restrict__ n_consistent,
+                                                               int min_consistent, long long n, int* __restrict__ counts) {
+  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  int total;
+  block_prefix(point_selected(depth, n_consistent, min_consistent, i, n), total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// exclusive scan of up to PC_TILE values held four per thread; returns the thread's first prefix, `total` = the sum of all
+__device__ __forceinline__ int tile_scan(const int v[4], int& total) {
+  __shared__ int wave_sum[PC_BLOCK / 64];
+  const int mine = v[0] + v[1] + v[2] + v[3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  __syncthreads();  // (a caller's loop: the previous round's reads of wave_sum are over)
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  int base = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < PC_BLOCK / 64; ++w) {
+    const int c = wave_sum[w];
+    base += w < wave ? c : 0;
+    total += c;
+  }
+  return base + incl - mine;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void point_scan_kernel(int* __restrict__ counts, int n_blocks, int* __restrict__ tiles) {
+  const long long first = (long long)blockIdx.x * PC_TILE + threadIdx.x * 4;
+  int v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = first + k < n_blocks ? counts[first + k] : 0;
+  int total;
+  int p = tile_scan(v, total);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (first + k < n_blocks) counts[first + k] = p;
+    p += v[k];
+  }
+  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+
+// one workgroup: exclusive scan of the tile totals (rounds of PC_TILE with a carried sum) and the grand total
+__global__ __launch_bounds__(PC_BLOCK) void point_total_kernel(int* __restrict__ tiles, int n_tiles, long long* __restrict__ count) {
+  int carry = 0;
+  for (int begin = 0; begin < n_tiles; begin += PC_TILE) {
+    const int first = begin + threadIdx.x * 4;
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = first + k < n_tiles ? tiles[first + k] : 0;
+    int total;
+    int p = carry + tile_scan(v, total);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (first + k < n_tiles) tiles[first + k] = p;
+      p += v[k];
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) *count = (long long)carry;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void point_scatter_kernel(FusionCam cam, int width, int legacy_coord,
+                                                                 const float* __restrict__ depth, const float* __restrict__ rgb,
+                                                                 const int* __restrict__ n_consistent, int min_consistent, long long n,
+                                                                 const int* __restrict__ counts, const int* __restrict__ tiles,
+                                                                 float* __restrict__ points, long long capacity) {
+  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  const bool flag = point_selected(depth, n_consistent, min_consistent, i, n);
+  int total;
+  const int before = block_prefix(flag, total);
+  if (!flag) return;
+  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  if (row >= capacity) return;
+  const int py = (int)(i / width), px = (int)(i - (long long)py * width);
+  const float off = legacy_coord ? 0.0f : 0.5f;
+  const float d = depth[i];
+  float wx, wy, wz;
+  fusion_lift(cam, (float)px + off, (float)py + off, d, wx, wy, wz);
+  float4* out = reinterpret_cast<float4*>(points) + (size_t)row * 2;
+  out[0] = make_float4(wx, wy, wz, d);
+  out[1] = make_float4(rgb[i * 3 + 0], rgb[i * 3 + 1], rgb[i * 3 + 2], (float)n_consistent[i]);
+}
+
+extern "C" int64_t mnerf_point_cloud_workspace_bytes(int64_t n_pixels) {
+  if (n_pixels < 0) return -1;
+  const int64_t n_blocks = n_pixels / PC_BLOCK + (n_pixels % PC_BLOCK != 0);
+  const int64_t n_tiles = n_blocks / PC_TILE + (n_blocks % PC_TILE != 0);
+  return ((n_blocks + n_tiles) * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;
+}
+
+extern "C" int mnerf_point_cloud(const mnerf_view* view, int32_t height, int32_t width, int32_t legacy_coord, const float* depth,
+                                 const float* rgb, const int32_t* n_consistent, int32_t min_consistent, float* points,
+                                 int64_t capacity, int64_t* count, void* workspace, void* stream) {
+  MNERF_REQUIRE(height >= 0 && width >= 0 && (long long)height * width < (1ll << 31), MNERF_E_RANGE, "mnerf_point_cloud: grid %dx%d",
+                height, width);
+  MNERF_REQUIRE(capacity >= 0, MNERF_E_RANGE, "mnerf_point_cloud: capacity=%lld", (long long)capacity);
+  const long long n = (long long)height * width;
+  if (n == 0) return MNERF_OK;
+  MNERF_REQUIRE(view, MNERF_E_NULL, "mnerf_point_cloud: view is NULL");
+  MNERF_REQUIRE(depth && rgb && n_consistent && count && workspace, MNERF_E_NULL,
+                "mnerf_point_cloud: NULL depth / rgb / n_consistent / count / workspace");
+  MNERF_REQUIRE(capacity == 0 || points, MNERF_E_NULL, "mnerf_point_cloud: points is NULL");
+  MNERF_REQUIRE(mnerf_aligned16(points), MNERF_E_ALIGN, "mnerf_point_cloud: points not 16B aligned");
+  MNERF_REQUIRE((((uintptr_t)workspace) & 3u) == 0 && (((uintptr_t)count) & 7u) == 0, MNERF_E_ALIGN,
+                "mnerf_point_cloud: workspace / count not aligned to 4 / 8 bytes");
+  FusionCam cam;
+  MNERF_REQUIRE(fusion_cam(*view, &cam), MNERF_E_RANGE, "mnerf_point_cloud: the view has a singular intr or extr");
+  const int n_blocks = (int)((n + PC_BLOCK - 1) / PC_BLOCK);
+  const int n_tiles = (n_blocks + PC_TILE - 1) / PC_TILE;
+  int* counts = static_cast<int*>(workspace);
+  int* tiles = counts + n_blocks;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(point_count_kernel, dim3((unsigned)n_blocks), dim3(PC_BLOCK), 0, st, depth, n_consistent, min_consistent, n, counts);
+  hipLaunchKernelGGL(point_scan_kernel, dim3((unsigned)n_tiles), dim3(PC_BLOCK), 0, st, counts, n_blocks, tiles);
+  hipLaunchKernelGGL(point_total_kernel, dim3(1), dim3(PC_BLOCK), 0, st, tiles, n_tiles, reinterpret_cast<long long*>(count));
+  hipLaunchKernelGGL(point_scatter_kernel, dim3((unsigned)n_blocks), dim3(PC_BLOCK), 0, st, cam, width, legacy_coord ? 1 : 0, depth, rgb,
+                     n_consistent, min_consistent, n, counts, tiles, points, (long long)capacity);
+  return mnerf_check_launch("mnerf_point_cloud");
+}
+
+// ------------------------------------------------------------------------------------------------ colour map
+__device__ __forceinline__ unsigned char jet_channel(int index, int centre) {  // 255 clamp(1.5 - |4 s - c|) rounded half up, exactly
+  return (unsigned char)min(max(383 - abs(4 * index - centre), 0), 255);
+}
+
+__global__ __launch_bounds__(256) void depth_colormap_kernel(const float* __restrict__ depth, long long n, float lo, float denom,
+                                                             unsigned char* __restrict__ rgb) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    float d = depth[i];
+    if (d != d) d = 0.0f;
+    const float t = 255.0f * ((d - lo) / denom);
+    const int index = !(t > 0.0f) ? 0 : (t >= 255.0f ? 255 : (int)t);
+    rgb[i * 3 + 0] = jet_channel(index, 765);
+    rgb[i * 3 + 1] = jet_channel(index, 510);
+    rgb[i * 3 + 2] = jet_channel(index, 255);
+  }
+}
+
+extern "C" int mnerf_depth_colormap(const float* depth, int64_t n, float lo, float hi, uint8_t* rgb, void* stream) {
+  MNERF_REQUIRE(n >= 0, MNERF_E_RANGE, "mnerf_depth_colormap: n=%lld", (long long)n);
+  MNERF_REQUIRE(std::isfinite(lo) && std::isfinite(hi), MNERF_E_RANGE, "mnerf_depth_colormap: lo=%g hi=%g", (double)lo, (double)hi);
+  if (n == 0) return MNERF_OK;
+  MNERF_REQUIRE(depth && rgb, MNERF_E_NULL, "mnerf_depth_colormap: NULL depth / rgb");
+  const float denom = (float)((double)hi - (double)lo + 1e-8);
+  long long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(depth_colormap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, depth, (long long)n, lo, denom, rgb);
+  return mnerf_check_launch("mnerf_depth_colormap");
+}
+#pragma clang fp contract(fast)

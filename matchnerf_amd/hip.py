@@ -226,6 +226,10 @@ SIGNATURES = {
     "mnerf_lpips_head_slots": (_i64, [_i32] * 2),
     "mnerf_lpips_head": (_int, [_vp] * 3 + [_i32] * 3 + [_vp] * 2),
     "mnerf_lpips_sum": (_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "mnerf_depth_consistency": (_int, [_P(View)] + [_i32] * 5 + [_vp] * 2 + [_f32] * 3 + [_vp, _P(_i32), _vp]),  # views: a host array of View
+    "mnerf_point_cloud_workspace_bytes": (_i64, [_i64]),
+    "mnerf_point_cloud": (_int, [_P(View)] + [_i32] * 3 + [_vp] * 2 + [_P(_i32), _i32, _vp, _i64] + [_vp] * 3),
+    "mnerf_depth_colormap": (_int, [_vp, _i64, _f32, _f32, _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -361,6 +365,11 @@ def _on(device, stream=None):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptr_i32(t):
+    """a device tensor of int32 for a parameter the header types as int32_t*"""
+    return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_int32)) if t is not None else None
 
 
 def _f32c(t, name):
@@ -1548,4 +1557,100 @@ def lpips_vgg(pred, gt, invalid_mask, weights, workspace=None, stream=None):
         if stream is not None:
             workspace.record_stream(stream)
             out.record_stream(stream)
+    return out
+
+
+# ----------------------------------------------------------------------- geometry export (matchnerf_amd/csrc/fusion.hip)
+
+POINT_FLOATS = 8  # floats of one row of a point buffer: x y z d | r g b n
+
+
+def view_array(views):
+    """[View, ...] -> a host array of mnerf_view, as mnerf_depth_consistency reads it during the call"""
+    arr = (View * len(views))()
+    for i, v in enumerate(views):
+        arr[i] = v
+    return arr
+
+
+def depth_consistency(views, ref, depth, opacity=None, legacy=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, out=None, stream=None):
+    """Cross-view consistency of view ``ref``'s depth map against the other views' (mnerf_depth_consistency; the criterion is stated
+    in include/mnerf.h).  ``views``: a list of View - extr, the intr of the maps' grid, near_ / far_ = the valid depth range;
+    ``depth`` [K, h, w] float32 CUDA camera-z depths; ``opacity`` the same shape or None.  -> (fused_depth [h, w] float32,
+    n_consistent [h, w] int32), or the pair ``out`` filled."""
+    import torch
+    lib = load()
+    _f32c(depth, "depth")
+    if depth.dim() != 3 or depth.shape[0] != len(views):
+        raise MnerfError(f"depth_consistency: depth {tuple(depth.shape)} is not [{len(views)}, h, w]")
+    if opacity is not None and (_f32c(opacity, "opacity").shape != depth.shape or opacity.device != depth.device):
+        raise MnerfError(f"depth_consistency: opacity {tuple(opacity.shape)} on {opacity.device} does not match depth {tuple(depth.shape)}")
+    k, h, w = (int(x) for x in depth.shape)
+    if out is None:
+        out = (torch.empty(h, w, device=depth.device), torch.empty(h, w, dtype=torch.int32, device=depth.device))
+    fused, cnt = out
+    if _f32c(fused, "fused_depth").numel() != h * w or cnt.dtype != torch.int32 or cnt.numel() != h * w or not cnt.is_contiguous() \
+            or fused.device != depth.device or cnt.device != depth.device:
+        raise MnerfError(f"depth_consistency: out must be (float32, int32) of {h * w} elements on {depth.device}")
+    arr = views if isinstance(views, C.Array) else view_array(views)
+    with _on(depth.device, stream) as st:
+        check(lib.mnerf_depth_consistency(arr, k, int(ref), h, w, int(bool(legacy)), _ptr(depth), _ptr(opacity), float(px_tol),
+                                          float(rel_tol), float(min_opacity), _ptr(fused), _ptr_i32(cnt), st), "mnerf_depth_consistency")
+    return fused, cnt
+
+
+def point_cloud_workspace_bytes(n_pixels):
+    return int(load().mnerf_point_cloud_workspace_bytes(int(n_pixels)))
+
+
+def point_cloud(view, hw, depth, rgb, n_consistent, min_consistent, legacy=True, points=None, count=None, workspace=None,
+                stream=None):
+    """The selected pixels of one view as rows ``x y z d | r g b n`` in pixel order (mnerf_point_cloud: a stable compaction, no atomic
+    cursor).  ``depth`` [h*w] float32 CUDA (the fused depth), ``rgb`` [h*w, 3], ``n_consistent`` [h*w] int32.  ``points``
+    [capacity, 8] float32 (default: h*w rows), ``count`` a 1-element int64 tensor, ``workspace`` a uint8 tensor of
+    ``point_cloud_workspace_bytes(h*w)`` bytes - allocated when None.  Enqueue only: -> (points, count); rows at or beyond the
+    capacity are not written, ``count`` is the total either way."""
+    import torch
+    lib = load()
+    h, w = int(hw[0]), int(hw[1])
+    n = h * w
+    dev = depth.device
+    _f32c(depth, "depth"), _f32c(rgb, "rgb")
+    if depth.numel() != n or rgb.numel() != 3 * n or rgb.device != dev:
+        raise MnerfError(f"point_cloud: depth {tuple(depth.shape)} / rgb {tuple(rgb.shape)} are not [{n}] / [{n}, 3] on one device")
+    if n_consistent.dtype != torch.int32 or n_consistent.numel() != n or not n_consistent.is_contiguous() or n_consistent.device != dev:
+        raise MnerfError(f"point_cloud: n_consistent must be a contiguous int32 tensor of {n} elements on {dev}")
+    if points is None:
+        points = torch.empty(n, POINT_FLOATS, device=dev)
+    if _f32c(points, "points").device != dev or points.numel() % POINT_FLOATS:
+        raise MnerfError(f"point_cloud: points {tuple(points.shape)} on {points.device} is no [capacity, {POINT_FLOATS}] buffer on {dev}")
+    if count is None:
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
+        raise MnerfError("point_cloud: count must be a 1-element int64 tensor on the depth's device")
+    need = point_cloud_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
+        raise MnerfError(f"point_cloud: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
+                         f"{need} needed on {dev}")
+    with _on(dev, stream) as st:
+        check(lib.mnerf_point_cloud(C.byref(view), h, w, int(bool(legacy)), _ptr(depth), _ptr(rgb), _ptr_i32(n_consistent),
+                                    int(min_consistent), _ptr(points), points.numel() // POINT_FLOATS, _ptr(count), _ptr(workspace), st),
+              "mnerf_point_cloud")
+    return points, count
+
+
+def depth_colormap(depth, lo, hi, out=None, stream=None):
+    """Depth values -> JET colours, uint8 [..., 3] (mnerf_depth_colormap: the arithmetic of the reference's visualize_depth with the
+    index clamped and the map stated as a formula, include/mnerf.h)."""
+    import torch
+    lib = load()
+    _f32c(depth, "depth")
+    if out is None:
+        out = torch.empty(tuple(depth.shape) + (3,), dtype=torch.uint8, device=depth.device)
+    if out.dtype != torch.uint8 or out.numel() != 3 * depth.numel() or not out.is_contiguous() or out.device != depth.device:
+        raise MnerfError(f"depth_colormap: out must be a contiguous uint8 tensor of {3 * depth.numel()} elements on {depth.device}")
+    with _on(depth.device, stream) as st:
+        check(lib.mnerf_depth_colormap(_ptr(depth), depth.numel(), float(lo), float(hi), _ptr(out), st), "mnerf_depth_colormap")
     return out

@@ -518,6 +518,65 @@ class MatchNeRF(torch.nn.Module):
         return edict({key: torch.stack([hip.box_downsample(v[b], h, w, k).reshape(h * w, -1) for b in range(batch_size)], 0)
                       for key, v in out.items()})
 
+    # ------------------------------------------------------------------ geometry export (matchnerf_amd/fusion.py)
+    def export_points(self, batch, views="sources", render_path_mode="interpolate", return_maps=False, **fuse_args):
+        """The scene of ``batch`` as coloured point clouds -> a list over the batch of [M, 8] float32 device tensors, rows
+        ``x y z d | r g b n`` (``fusion.fuse``: depth maps rendered at several poses, kept where other poses confirm them).
+        ONE encoder pass; then ``render`` at each fusion pose, depth, opacity and colour staying on the device:
+          "sources"   the source views' own poses, at the views' size
+          "path"      the poses of the video path (``render_path_mode``, nerf.video_n_frames), on the target grid
+          [pose, ..]  dicts of extrinsics [B,3,4] / intrinsics [B,3,3] / near_fars [B,2], on the target grid
+        (the target grid: ``batch.tgt_hw`` / nerf.render_hw as in ``forward``; frames are not supersampled).  ``fuse_args``: px_tol,
+        rel_tol, min_opacity, min_consistent.  ``return_maps``: -> (clouds, edict(depth [B,K,h,w], opacity [B,K,h,w], rgb [B,K,h*w,3],
+        views [[hip.View] * K] * B, hw, counts [[rows of view k] * K] * B)).  The fusion geometry is pinhole z-depth: depth.param =
+        inverse and another target camera model are refused, and so are gradients - all before the first launch."""
+        from . import fusion
+        if self.opts.nerf.depth.param != "metric":
+            raise ValueError(f"export_points: nerf.depth.param={self.opts.nerf.depth.param!r}; the fusion geometry is metric camera-z depth")
+        if self.target_camera(batch, "test") is not None:
+            raise ValueError("export_points: the target camera is not a pinhole; the fusion geometry is pinhole camera-z depth")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("export_points is inference only; call it under torch.no_grad()")
+        unknown = set(fuse_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"}
+        if unknown:
+            raise TypeError(f"export_points: unknown arguments {sorted(unknown)}")
+        self._frame = None
+        self._cv_ops = None
+        ref_images = batch.images[:, :self.n_src_views]
+        tgt_pose, ref_poses = self.extract_poses(batch)
+        batch_size, _, _, img_h, img_w = ref_images.shape
+        if isinstance(views, str) and views == "sources":
+            hw = (img_h, img_w)
+            poses = [dict(extrinsics=ref_poses["extrinsics"][:, v], intrinsics=ref_poses["intrinsics"][:, v],
+                          near_fars=ref_poses["near_fars"][:, v]) for v in range(self.n_src_views)]
+        else:
+            tgt_pose, hw, _ = self.target_grid(batch, "test", tgt_pose, (img_h, img_w))
+            if isinstance(views, str) and views == "path":
+                poses = self.get_video_rendering_path(tgt_pose, ref_poses, render_path_mode, self.opts.nerf.video_n_frames, batch)
+            elif isinstance(views, str):
+                raise ValueError(f"export_points: views={views!r}: 'sources', 'path' or a list of pose dicts")
+            else:
+                poses = list(views)
+        if len(poses) < 2:
+            raise ValueError(f"export_points: {len(poses)} fusion pose(s); cross-view consistency needs at least 2")
+        ref_feats_list = self.get_img_feat(ref_images, attn_splits_list=self.opts.encoder.attn_splits_list,
+                                           cur_n_src_views=self.n_src_views)
+        rets = [self.render(self.opts, p, mode="test", ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=ref_feats_list,
+                            tgt_hw=hw) for p in poses]
+        hosts = [self._tgt_host(p) for p in poses]
+        depth = torch.stack([r.depth[..., 0] for r in rets], 1).reshape(batch_size, len(poses), hw[0], hw[1])
+        opacity = torch.stack([r.opacity[..., 0] for r in rets], 1).reshape(batch_size, len(poses), hw[0], hw[1])
+        rgb = torch.stack([r.rgb for r in rets], 1)
+        legacy = bool(self.opts.nerf.legacy_coord)
+        clouds, all_views, all_counts = [], [], []
+        for b in range(batch_size):
+            cams = [hip.make_view(ex[b], it[b], nf[b, 0], nf[b, 1]) for ex, it, nf in hosts]
+            cloud, rows = fusion.fuse(cams, depth[b], opacity[b], rgb[b], hw, legacy, return_counts=True, **fuse_args)
+            clouds.append(cloud), all_views.append(cams), all_counts.append(rows)
+        if return_maps:
+            return clouds, edict(depth=depth, opacity=opacity, rgb=rgb, views=all_views, hw=hw, counts=all_counts)
+        return clouds
+
     def render_poses(self, opt, poses, ref_poses=None, ref_images=None, ref_feats_list=None, tgt_hw=None):
         """Full frames of SEVERAL target poses of one source set (the video loop of matchnerf.py:42-71) with as many poses per
         launch as fit MAX_RAYS_PER_POSE_LAUNCH rays: the poses' camera constants travel as a table in HBM (mnerf_rays.pose_table,

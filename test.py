@@ -20,7 +20,15 @@ Video frames may come from another camera model than the batch's pinhole camera 
     python test.py --yaml=demo_own --nerf.render_camera=sphere --nerf.render_fov=60 --nerf.render_hw=128,256
 
 ``--nerf.render_camera=pinhole|fisheye|sphere|ortho``, ``--nerf.render_fov=<degrees>`` (fisheye / sphere),
-``--nerf.render_ortho_width=<world units>`` (ortho).  Scored evaluation refuses them: its ground truth is a pinhole image."""
+``--nerf.render_ortho_width=<world units>`` (ortho).  Scored evaluation refuses them: its ground truth is a pinhole image.
+
+Geometry instead of images: ``--nerf.export_geometry=sources|path`` writes one coloured point cloud per test batch under
+``<output_path>/geometry/<set>/`` (``Coach.export_geometry``: depth maps rendered at the source views' poses, or along the video
+path, kept where the other poses confirm them), with ``--vis_depth`` also the colour-mapped depth maps.  Thresholds:
+``--nerf.fuse_px_tol=<pixels>`` (1), ``--nerf.fuse_rel_tol=<relative depth>`` (0.01), ``--nerf.fuse_min_opacity`` (0.5),
+``--nerf.fuse_min_views=<confirming views>`` (min(2, K - 1)).
+
+    python test.py --yaml=demo_own --nerf.export_geometry=sources"""
 import os
 import sys
 
@@ -49,6 +57,10 @@ def run(argv):
     coach.build_networks()
     coach.restore_checkpoint()
     coach.load_dataset(splits=["test"])
+    if getattr(opt.nerf, "export_geometry", None):
+        if world > 1:
+            raise SystemExit("test.py: nerf.export_geometry is not sharded; run it with one GPU")
+        return coach.export_geometry()
     if opt.nerf.render_video:
         if world > 1:
             raise SystemExit("test.py: nerf.render_video is not sharded; run it with one GPU")
