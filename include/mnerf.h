@@ -896,6 +896,84 @@ int mnerf_point_cloud(const mnerf_view* view, int32_t height, int32_t width, int
  * n == 0 is MNERF_OK and touches no buffer.  MNERF_E_RANGE: n < 0, lo or hi not finite.  MNERF_E_NULL: depth or rgb missing. */
 int mnerf_depth_colormap(const float* depth, int64_t n, float lo, float hi, uint8_t* rgb, void* stream);
 
+/* MESH EXPORT (added under v12 without a layout change; matchnerf_amd/csrc/mesh.hip): truncated-signed-distance (TSDF) fusion of the
+ * depth maps of GEOMETRY EXPORT into a voxel volume, and a mesher that extracts a welded, indexed, coloured triangle mesh from it.
+ * The conventions are those of GEOMETRY EXPORT: pinhole camera-z depth, mnerf_view HOST arrays read during the call, proj() and the
+ * value of a texel as stated there, pixel centres by legacy_coord, enqueue-only on `stream`, every argument check before any HIP
+ * call, no atomics of any kind, every operation rounded on its own with one FMA where the text says so.
+ * The grid: nx x ny x nz voxels of side `voxel` (finite, > 0) from the corner (origin_x, origin_y, origin_z) (finite); voxel
+ * (i, j, k) has the linear index (k ny + j) nx + i - x fastest - and the centre origin + (index + 0.5) voxel, one FMA per axis.
+ * A grid with nx ny nz == 0 is MNERF_OK and touches no buffer.
+ *
+ * mnerf_tsdf_integrate - one thread per voxel, one launch; adds n_views (1..MNERF_MAX_VIEWS) depth maps to a volume that the caller
+ * owns and has zeroed before the first call:
+ *   sums           device [nz][ny][nx][4] fp32, 16-byte aligned (MNERF_E_ALIGN otherwise): S | R G B, the running sums of the
+ *                  truncated distance and of the colour
+ *   weight         device [nz][ny][nx] fp32: the number of views that updated the voxel
+ *   depth          device [n_views][height][width];  opacity: the same shape or NULL;  rgb [n_views][height x width][3]
+ *   n_consistent   device [n_views][height][width] int32 or NULL.  With it pass the FUSED depth of mnerf_depth_consistency and
+ *                  opacity = NULL; a texel then also needs n_consistent >= min_consistent
+ * With P the voxel's centre, for view j in ascending order:
+ *   (u, v, zc) = proj(j, P); skipped unless zc > 0;
+ *   the nearest texel xi = floor((u - off) + 0.5), yi alike (off = the centre offset); skipped outside 0 <= xi < width, 0 <= yi < height;
+ *   z = the texel's value; skipped when it is not VALID (or fails n_consistent);
+ *   sdf = z - zc; skipped if sdf < -trunc (the voxel is hidden behind the surface); t = min(1, sdf / trunc);
+ *   S += t, RGB += rgb[texel], weight += 1.
+ * Calls accumulate: more views are several calls on one volume, and the result depends on the order of the views only.
+ * MNERF_E_RANGE: n_views outside 1..MNERF_MAX_VIEWS, height or width below 1 or height x width >= 2^31, trunc not finite and
+ * positive, a min_opacity that is not finite (read only with opacity), a grid size below 0, nx ny nz >= 2^31, a voxel not finite and
+ * positive, an origin not finite, a singular intr or extr.  MNERF_E_NULL: views, depth, rgb, sums or weight missing.  MNERF_E_ALIGN: sums not
+ * 16-byte or weight not 4-byte aligned. */
+int mnerf_tsdf_integrate(const mnerf_view* views, int32_t n_views, int32_t height, int32_t width, int32_t legacy_coord,
+                         const float* depth, const float* opacity, const int32_t* n_consistent, int32_t min_consistent, const float* rgb,
+                         float min_opacity, float trunc, float origin_x, float origin_y, float origin_z, float voxel, int32_t nx,
+                         int32_t ny, int32_t nz, float* sums, float* weight, void* stream);
+
+/* mnerf_tsdf_mesh - marching tetrahedra over the Freudenthal split of every cell of the volume's lattice.
+ *   lattice        the lattice points are the voxel centres; the value at a point is d = S / weight; a point is VALID iff
+ *                  weight >= min_weight (finite, > 0); INSIDE is d < 0 (an exact 0 is outside; the zero-area triangles this can give
+ *                  are kept, so that the welded indices stay watertight)
+ *   cells          cell (i, j, k), 0 <= i < nx - 1 and alike, has the corners (i, j, k) + c, c in {0,1}^3; it is valid iff its 8
+ *                  corners are.  Cells are ordered by (k, j, i), x fastest.  A grid with an axis of 1 has no cell.
+ *   tets           a cell's six tets, in this order, are the axis permutations xyz xzy yxz yzx zxy zyx: tet (a b c) has the
+ *                  vertices v0 = 000, v1 = e_a, v2 = e_a + e_b, v3 = 111.  The even permutations (tets 0, 3, 4) are positively
+ *                  oriented, det[v1 - v0, v2 - v0, v3 - v0] = +1.
+ *   edges          every tet edge runs from a lattice point p to p + e, e a non-zero corner of {0,1}^3; p OWNS it under the
+ *                  direction index e_x + 2 e_y + 4 e_z - 1 = 0..6: +x, +y, +x+y, +z, +x+z, +y+z, +x+y+z.
+ *   vertices       one per owned edge whose ends differ in INSIDE and that at least one valid cell uses (the cells p - f, f a corner
+ *                  with f . e = 0).  With a = p, b = p + e:  s = da / (da - db);  position = pa + s (pb - pa), weight and colour
+ *                  (RGB / weight of each end) alike, every component one FMA.  A row is 32 bytes: x y z w | r g b 0.
+ *                  Order: ascending (owner's linear index, direction index).
+ *   triangles      int32 [T][3] vertex rows.  With I the inside and O the outside vertices of a tet, each ascending, and "pq" the
+ *                  vertex on the edge between tet vertices p and q:
+ *                    |I| = 1, I = {a}, O = {b c d}:   (ab ac ad)
+ *                    |I| = 3, O = {a}, I = {b c d}:   (ab ac ad)
+ *                    |I| = 2, I = {a b}, O = {c d}:   (ac ad bd) then (ac bd bc) - the quad ac ad bd bc cut along ac-bd
+ *                  The last two vertices of every triangle are swapped once if the permutation (I, O) of 0123 is odd and once if
+ *                  the tet is: the geometric normal then points from negative to positive d, towards the observed free space.
+ *                  Order: ascending (cell, tet, triangle).
+ *   vertices       device [vertex_capacity] rows, 16-byte aligned;  triangles: device [triangle_capacity][3] int32
+ *   counts         device int64[2], 8-byte aligned: the numbers of vertices and triangles.  Rows at or beyond a capacity are not
+ *                  written, the counts are the totals either way and the call is MNERF_OK (as mnerf_point_cloud)
+ *   workspace      device, 4-byte aligned, mnerf_tsdf_mesh_workspace_bytes(nx, ny, nz) bytes; scratch only.  With N = nx ny nz,
+ *                  B = ceil(N / 256), T = ceil(B / 1024):  int32 vertex base of every lattice point [N] | int32 [B] and [T]: the
+ *                  vertex counts of the workgroups and of their tiles, scanned | the same two for the triangles | uint8 flags [N]
+ *                  (1 valid, 2 inside, 4 origin of a valid cell) | uint8 masks [N] (bit = direction index of a live owned edge):
+ *                  4 (N + 2 B + 2 T) + 2 N bytes, rounded up to 16.
+ * Nine launches over the lattice points, 256 per workgroup: flags; edge masks and workgroup counts; the point cloud's two scans;
+ * vertex bases and rows; the triangle counts of the cells (a thread is the cell its point is the origin of); two scans; the index
+ * triples, each vertex looked up as its owner's base + the popcount of the lower mask bits.  The 16 tet cases are generated from the
+ * rule above at compile time.  Integer arithmetic decides every row's place: two runs give the same bytes.
+ * MNERF_E_RANGE: a grid size below 0, nx ny nz > (2^31 - 1) / 12 (what keeps 7 vertices per point and 12 triangles per cell below
+ * 2^31), a voxel not finite and positive, an origin not finite, min_weight not finite and positive, a negative capacity.
+ * MNERF_E_NULL: sums, weight, counts or workspace missing, vertices or triangles missing with a capacity > 0.  MNERF_E_ALIGN: sums or
+ * vertices not 16-byte, counts not 8-byte, weight, triangles or workspace not 4-byte aligned.
+ * mnerf_tsdf_mesh_workspace_bytes: host only; 0 for an empty grid, -1 for a size below 0 or above the bound. */
+int64_t mnerf_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int mnerf_tsdf_mesh(const float* sums, const float* weight, float origin_x, float origin_y, float origin_z, float voxel, int32_t nx,
+                    int32_t ny, int32_t nz, float min_weight, float* vertices, int64_t vertex_capacity, int32_t* triangles,
+                    int64_t triangle_capacity, int64_t* counts, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

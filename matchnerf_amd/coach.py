@@ -740,7 +740,9 @@ class Coach:
         with the stems of ``test_model_video``; with vis_depth also one colour-mapped depth map per fusion view, <stem>_depth<k>.png
         (minmax = the target's near_fars, as the reference's depth panels).  ``views``: 'sources' | 'path' (default: the option
         nerf.export_geometry, else 'sources'); thresholds from nerf.fuse_px_tol / fuse_rel_tol / fuse_min_opacity / fuse_min_views
-        where given.  One process (not sharded).  Returns {set: [path of every .ply]}."""
+        where given.  With the option nerf.export_mesh also <stem>_mesh.ply next to each cloud: the triangle mesh of the same maps
+        (``fusion.mesh``: TSDF fusion + marching tetrahedra; float xyz + uchar rgb vertices and a face list), with nerf.mesh_resolution /
+        mesh_voxel / mesh_trunc / mesh_min_weight where given.  One process (not sharded).  Returns {set: [path of every .ply]}."""
         from PIL import Image
 
         from . import fusion
@@ -752,6 +754,11 @@ class Coach:
                                                                           ("min_opacity", "fuse_min_opacity"),
                                                                           ("min_consistent", "fuse_min_views"))
                      if getattr(self.opts.nerf, name, None) is not None}
+        mesh_args = None
+        if getattr(self.opts.nerf, "export_mesh", None):
+            mesh_args = {arg: getattr(self.opts.nerf, name) for arg, name in (("resolution", "mesh_resolution"), ("voxel", "mesh_voxel"),
+                                                                              ("trunc", "mesh_trunc"), ("min_weight", "mesh_min_weight"))
+                         if getattr(self.opts.nerf, name, None) is not None}
         out_root = os.path.join(self.opts.output_path, "geometry")
         written = {}
         for loader in self.test_loaders:
@@ -776,6 +783,13 @@ class Coach:
                     n = fusion.write_ply(path, cloud)
                     written.setdefault(name, []).append(path)
                     self.say(f"[coach] {name}: {n} points -> {path}")
+                    if mesh_args is not None:  # the surface of the same maps, fused into a TSDF volume
+                        vertices, faces = fusion.mesh(maps.views[bi], maps.depth[bi], maps.opacity[bi], maps.rgb[bi], maps.hw,
+                                                      bool(self.opts.nerf.legacy_coord), **mesh_args, **fuse_args)
+                        path = os.path.join(out_dir, f"{stem}_mesh.ply")
+                        fusion.write_ply(path, vertices, faces)
+                        written[name].append(path)
+                        self.say(f"[coach] {name}: {vertices.shape[0]} vertices, {faces.shape[0]} triangles -> {path}")
                     for k in range(panels.shape[1] if panels is not None else 0):
                         Image.fromarray(panels[bi, k]).save(os.path.join(out_dir, f"{stem}_depth{k}.png"))
             self.model.nerf_setbg_opaque = False

@@ -6,6 +6,10 @@ point query has no meaning without a ray, whereas a depth map rendered at a pose
 (the MVSNet criterion, ``hip.depth_consistency``); its surviving pixels are compacted in pixel order into its own segment of one
 buffer of K h w rows (``hip.point_cloud``), the K counts reach the host in ONE copy, and the segments are trimmed and joined.
 Everything else stays on the device.  There is no CPU fallback.
+
+``mesh`` turns the same maps into a surface (include/mnerf.h "MESH EXPORT", matchnerf_amd/csrc/mesh.hip): the fused depths and their
+counts are integrated into a truncated-signed-distance volume over the cloud's box, and marching tetrahedra extract a welded,
+indexed, coloured triangle mesh whose vertex and face order is defined - two runs give the same bytes.
 """
 import numpy as np
 import torch
@@ -13,6 +17,7 @@ import torch
 from . import hip
 
 MAX_PARTNERS = hip.MNERF_MAX_VIEWS - 1  # a launch takes the reference and up to 15 partners
+MESH_GUESS_ROWS = 16  # the mesher's first buffers: vertex rows per voxel of the grid's three faces (twice as many triangles)
 
 
 def camera_centres(views):
@@ -79,9 +84,124 @@ def fuse(views, depths, opacities, rgbs, hw, legacy, px_tol=1.0, rel_tol=0.01, m
     return (cloud, rows) if return_counts else cloud
 
 
-def write_ply(path, points):
+def _auto_bounds(views, fused, counts, rgbs, hw, legacy, min_consistent):
+    """The axis-aligned box of the selected pixels' points -> float64 [2, 3] on the host (the ONE copy before the mesh): the K point
+    clouds of ``fuse`` in one buffer, a masked min / max over it on the device."""
+    h, w = hw
+    n, k_views = h * w, len(views)
+    dev = fused.device
+    points = torch.empty(k_views * n, hip.POINT_FLOATS, device=dev)
+    rows = torch.zeros(k_views, dtype=torch.int64, device=dev)
+    workspace = torch.empty(max(hip.point_cloud_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+    for k in range(k_views):
+        hip.point_cloud(views[k], (h, w), fused[k], rgbs[k], counts[k], min_consistent, legacy=legacy, points=points[k * n:(k + 1) * n],
+                        count=rows[k:k + 1], workspace=workspace)
+    written = torch.arange(n, device=dev)[None, :] < rows[:, None]
+    xyz = points.view(k_views, n, hip.POINT_FLOATS)[..., :3]
+    inf = torch.full((), float("inf"), device=dev)
+    lo = torch.where(written[..., None], xyz, inf).amin((0, 1))
+    hi = torch.where(written[..., None], xyz, -inf).amax((0, 1))
+    box = torch.stack([lo, hi]).double().cpu().numpy()
+    if not np.isfinite(box).all():
+        raise ValueError("mesh: no pixel survives the selection, so there is no box to mesh; pass bounds or loosen the thresholds")
+    return box
+
+
+def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
+         consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None):
+    """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
+    fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
+    (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
+      consistency   True: ``hip.depth_consistency`` per view as in ``fuse``; the integrator takes the fused depth and reads only
+                    texels that ``min_consistent`` other views confirm.  False: the maps as they are (depth / opacity, ``min_opacity``)
+      bounds        ((x0, y0, z0), (x1, y1, z1)), used as given; None: the box of the selected pixels' points, padded by ``trunc``
+      voxel         the voxel side; default: the longest side of the (unpadded) box / ``resolution``
+      trunc         the truncation distance in world units; default 4 voxels
+      min_weight    views that must have updated a lattice point for it to take part; default min(2, K - 1), at least 1
+    Views beyond 16 are integrated in groups of 16, in order.  Device->host copies: the box (with ``bounds=None`` only) before the
+    mesh launch and the two counts after it.  The vertex and face buffers are sized from a first guess (a few rows per voxel of the
+    grid's three faces); when the counts exceed it the mesher is RUN AGAIN ONCE with exact sizes - no further copy."""
+    h, w = int(hw[0]), int(hw[1])
+    n, k_views = h * w, len(views)
+    if k_views < 1 or (consistency and k_views < 2):
+        raise ValueError(f"mesh: {k_views} view(s); cross-view consistency needs at least 2")
+    if min_consistent is None:
+        min_consistent = min(2, k_views - 1)
+    if min_weight is None:
+        min_weight = max(1, min(2, k_views - 1))
+    depths = depths.reshape(k_views, h, w)
+    opacities = None if opacities is None else opacities.reshape(k_views, h, w)
+    rgbs = rgbs.reshape(k_views, n, 3)
+    dev = depths.device
+    if consistency:
+        fused = torch.empty(k_views, h, w, device=dev)
+        counts = torch.empty(k_views, h, w, dtype=torch.int32, device=dev)
+        all_views = hip.view_array(views) if k_views <= hip.MNERF_MAX_VIEWS else None
+        centres = None if all_views is not None else camera_centres(views)
+        for k in range(k_views):
+            if all_views is not None:
+                arr, ref, d, o = all_views, k, depths, opacities
+            else:
+                group = sorted(partners_of(centres, k) + [k])
+                index = torch.as_tensor(group, device=dev)
+                arr, ref = hip.view_array([views[j] for j in group]), group.index(k)
+                d = depths.index_select(0, index)
+                o = None if opacities is None else opacities.index_select(0, index)
+            hip.depth_consistency(arr, ref, d, o, legacy=legacy, px_tol=px_tol, rel_tol=rel_tol, min_opacity=min_opacity,
+                                  out=(fused[k], counts[k]))
+        maps, map_opacity = fused, None
+    else:
+        maps, map_opacity, counts, min_consistent = depths, opacities, None, 0
+    if bounds is None:
+        if consistency:
+            box = _auto_bounds(views, fused, counts, rgbs, (h, w), legacy, min_consistent)
+        else:  # the selection of the integrator, but for the near / far range
+            z = depths if opacities is None else torch.where(opacities >= min_opacity, depths / opacities, torch.zeros_like(depths))
+            box = _auto_bounds(views, z.contiguous(), torch.zeros(k_views, h, w, dtype=torch.int32, device=dev), rgbs, (h, w), legacy, 0)
+    else:
+        box = np.asarray(bounds, np.float64).reshape(2, 3)
+        if not (np.isfinite(box).all() and (box[1] >= box[0]).all()):
+            raise ValueError(f"mesh: bounds {bounds!r} are no box")
+    side = float((box[1] - box[0]).max())
+    if voxel is None:
+        voxel = side / int(resolution)
+    voxel = float(voxel)
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError(f"mesh: voxel={voxel}; the box {box.tolist()} has no extent")
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    if bounds is None:
+        box = np.stack([box[0] - trunc, box[1] + trunc])
+    dims = tuple(max(1, int(np.ceil((box[1, a] - box[0, a]) / voxel - 1e-9))) for a in range(3))
+    origin = tuple(float(x) for x in box[0])
+    need = hip.tsdf_mesh_workspace_bytes(dims)
+    if need < 0:
+        raise ValueError(f"mesh: a grid of {dims} voxels is too large; raise voxel or lower resolution")
+    nx, ny, nz = dims
+    sums = torch.zeros(nz, ny, nx, 4, device=dev)
+    weight = torch.zeros(nz, ny, nx, device=dev)
+    for first in range(0, k_views, hip.MNERF_MAX_VIEWS):
+        group = slice(first, min(first + hip.MNERF_MAX_VIEWS, k_views))
+        hip.tsdf_integrate(views[group], maps[group], rgbs[group], origin, voxel, dims, trunc, sums, weight,
+                           opacity=None if map_opacity is None else map_opacity[group],
+                           n_consistent=None if counts is None else counts[group], min_consistent=min_consistent, legacy=legacy,
+                           min_opacity=min_opacity)
+    workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    guess = min(7 * nx * ny * nz, max(1024, MESH_GUESS_ROWS * (nx * ny + ny * nz + nz * nx)))
+    vertices = torch.empty(guess, hip.VERTEX_FLOATS, device=dev)
+    faces = torch.empty(2 * guess, 3, dtype=torch.int32, device=dev)
+    _, _, totals = hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, workspace=workspace)
+    n_vertices, n_faces = (int(c) for c in totals.cpu())  # the one copy after the launch
+    if n_vertices > vertices.shape[0] or n_faces > faces.shape[0]:
+        vertices = torch.empty(n_vertices, hip.VERTEX_FLOATS, device=dev)
+        faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+        hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, counts=totals, workspace=workspace)
+    return vertices[:n_vertices], faces[:n_faces]
+
+
+def write_ply(path, points, faces=None):
     """points [M, >= 7] (x y z . r g b ..., colours in [0, 1]; a tensor or an array) -> a binary little-endian PLY of float xyz and
-    uchar rgb vertices."""
+    uchar rgb vertices; with ``faces`` [T, 3] (integer vertex rows) also ``element face`` with ``property list uchar int
+    vertex_indices``.  Without faces the file is the point cloud's, byte for byte."""
     pts = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
     pts = pts.reshape(-1, pts.shape[-1]) if pts.size else np.zeros((0, 8), np.float32)
     vertex = np.zeros(len(pts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
@@ -90,8 +210,18 @@ def write_ply(path, points):
     for i, name in enumerate(("red", "green", "blue")):
         vertex[name] = np.rint(np.clip(np.nan_to_num(pts[:, 4 + i]), 0.0, 1.0) * 255.0).astype(np.uint8)
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" \
-             "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pts)
+             "property uchar red\nproperty uchar green\nproperty uchar blue\n" % len(pts)
+    body = vertex.tobytes()
+    if faces is not None:
+        tri = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        tri = tri.reshape(-1, 3)
+        if tri.size and (tri.min() < 0 or tri.max() >= len(pts)):
+            raise ValueError(f"write_ply: face indices outside the {len(pts)} vertices")
+        face = np.zeros(len(tri), dtype=[("n", "u1"), ("v", "<i4", 3)])
+        face["n"], face["v"] = 3, tri
+        header += "element face %d\nproperty list uchar int vertex_indices\n" % len(tri)
+        body += face.tobytes()
     with open(path, "wb") as f:
-        f.write(header.encode("ascii"))
-        f.write(vertex.tobytes())
+        f.write((header + "end_header\n").encode("ascii"))
+        f.write(body)
     return len(pts)

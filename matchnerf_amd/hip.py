@@ -230,6 +230,9 @@ SIGNATURES = {
     "mnerf_point_cloud_workspace_bytes": (_i64, [_i64]),
     "mnerf_point_cloud": (_int, [_P(View)] + [_i32] * 3 + [_vp] * 2 + [_P(_i32), _i32, _vp, _i64] + [_vp] * 3),
     "mnerf_depth_colormap": (_int, [_vp, _i64, _f32, _f32, _vp, _vp]),
+    "mnerf_tsdf_integrate": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3 + [_vp] * 3),
+    "mnerf_tsdf_mesh_workspace_bytes": (_i64, [_i32] * 3),
+    "mnerf_tsdf_mesh": (_int, [_vp] * 2 + [_f32] * 4 + [_i32] * 3 + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -1654,3 +1657,91 @@ def depth_colormap(depth, lo, hi, out=None, stream=None):
     with _on(depth.device, stream) as st:
         check(lib.mnerf_depth_colormap(_ptr(depth), depth.numel(), float(lo), float(hi), _ptr(out), st), "mnerf_depth_colormap")
     return out
+
+
+# ----------------------------------------------------------------------- mesh export (matchnerf_amd/csrc/mesh.hip)
+
+VERTEX_FLOATS = 8  # floats of one row of a vertex buffer: x y z w | r g b 0
+
+
+def _grid(origin, voxel, dims):
+    """(origin xyz, voxel, (nx, ny, nz)) -> the seven scalars of the header's grid"""
+    if len(origin) != 3 or len(dims) != 3:
+        raise MnerfError(f"a grid is an origin of 3 floats and (nx, ny, nz), got {origin!r} / {dims!r}")
+    return [float(x) for x in origin] + [float(voxel)] + [int(x) for x in dims]
+
+
+def tsdf_integrate(views, depth, rgb, origin, voxel, dims, trunc, sums, weight, opacity=None, n_consistent=None, min_consistent=0,
+                   legacy=True, min_opacity=0.5, stream=None):
+    """Add the depth maps of up to MNERF_MAX_VIEWS views to a TSDF volume (mnerf_tsdf_integrate; the update is stated in
+    include/mnerf.h).  ``views``: a list of View as for ``depth_consistency``; ``depth`` [K, h, w] float32 CUDA, ``opacity`` the same
+    shape or None, ``rgb`` [K, h*w, 3]; ``n_consistent`` [K, h, w] int32 or None - with it ``depth`` is the fused depth and a texel
+    needs ``n_consistent >= min_consistent``.  The grid: ``origin`` (x, y, z), ``voxel``, ``dims`` = (nx, ny, nz).  ``sums``
+    [nz, ny, nx, 4] and ``weight`` [nz, ny, nx] float32 are the caller's, zeroed before the first call; calls accumulate.
+    Enqueue only: -> (sums, weight)."""
+    import torch
+    lib = load()
+    _f32c(depth, "depth"), _f32c(rgb, "rgb"), _f32c(sums, "sums"), _f32c(weight, "weight")
+    dev = depth.device
+    if depth.dim() != 3 or depth.shape[0] != len(views):
+        raise MnerfError(f"tsdf_integrate: depth {tuple(depth.shape)} is not [{len(views)}, h, w]")
+    k, h, w = (int(x) for x in depth.shape)
+    if rgb.numel() != 3 * depth.numel() or rgb.device != dev:
+        raise MnerfError(f"tsdf_integrate: rgb {tuple(rgb.shape)} on {rgb.device} is not [{k}, {h * w}, 3] on {dev}")
+    if opacity is not None and (_f32c(opacity, "opacity").shape != depth.shape or opacity.device != dev):
+        raise MnerfError(f"tsdf_integrate: opacity {tuple(opacity.shape)} on {opacity.device} does not match depth {tuple(depth.shape)}")
+    if n_consistent is not None and (n_consistent.dtype != torch.int32 or n_consistent.numel() != depth.numel()
+                                     or not n_consistent.is_contiguous() or n_consistent.device != dev):
+        raise MnerfError(f"tsdf_integrate: n_consistent must be a contiguous int32 tensor of {depth.numel()} elements on {dev}")
+    grid = _grid(origin, voxel, dims)
+    n = grid[4] * grid[5] * grid[6]
+    if sums.numel() != 4 * n or weight.numel() != n or sums.device != dev or weight.device != dev:
+        raise MnerfError(f"tsdf_integrate: sums {tuple(sums.shape)} / weight {tuple(weight.shape)} are not [nz, ny, nx, 4] / "
+                         f"[nz, ny, nx] of the grid {tuple(grid[4:])} on {dev}")
+    arr = views if isinstance(views, C.Array) else view_array(views)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_integrate(arr, k, h, w, int(bool(legacy)), _ptr(depth), _ptr(opacity), _ptr_i32(n_consistent),
+                                       int(min_consistent), _ptr(rgb), float(min_opacity), float(trunc), *grid, _ptr(sums), _ptr(weight),
+                                       st), "mnerf_tsdf_integrate")
+    return sums, weight
+
+
+def tsdf_mesh_workspace_bytes(dims):
+    return int(load().mnerf_tsdf_mesh_workspace_bytes(int(dims[0]), int(dims[1]), int(dims[2])))
+
+
+def tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, triangles, counts=None, workspace=None, stream=None):
+    """The triangle mesh of a TSDF volume (mnerf_tsdf_mesh: marching tetrahedra, welded vertices, a defined order and no atomics).
+    ``vertices`` [vertex capacity, 8] float32 rows ``x y z w | r g b 0``, ``triangles`` [triangle capacity, 3] int32, ``counts`` a
+    2-element int64 tensor (vertices, triangles), ``workspace`` a uint8 tensor of ``tsdf_mesh_workspace_bytes(dims)`` bytes - the last
+    two allocated when None.  Enqueue only: -> (vertices, triangles, counts); rows at or beyond a capacity are not written, the
+    counts are the totals either way."""
+    import torch
+    lib = load()
+    _f32c(sums, "sums"), _f32c(weight, "weight"), _f32c(vertices, "vertices")
+    dev = sums.device
+    grid = _grid(origin, voxel, dims)
+    n = grid[4] * grid[5] * grid[6]
+    if sums.numel() != 4 * n or weight.numel() != n or weight.device != dev:
+        raise MnerfError(f"tsdf_mesh: sums {tuple(sums.shape)} / weight {tuple(weight.shape)} are not [nz, ny, nx, 4] / [nz, ny, nx] "
+                         f"of the grid {tuple(grid[4:])} on {dev}")
+    if vertices.device != dev or vertices.numel() % VERTEX_FLOATS:
+        raise MnerfError(f"tsdf_mesh: vertices {tuple(vertices.shape)} on {vertices.device} is no [capacity, {VERTEX_FLOATS}] buffer on {dev}")
+    if triangles.dtype != torch.int32 or not triangles.is_contiguous() or triangles.device != dev or triangles.numel() % 3:
+        raise MnerfError(f"tsdf_mesh: triangles must be a contiguous int32 [capacity, 3] tensor on {dev}")
+    if counts is None:
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    if counts.dtype != torch.int64 or counts.numel() != 2 or counts.device != dev or not counts.is_contiguous():
+        raise MnerfError("tsdf_mesh: counts must be a contiguous 2-element int64 tensor on the volume's device")
+    need = tsdf_mesh_workspace_bytes(grid[4:])
+    if need < 0:
+        raise MnerfError(f"tsdf_mesh: the grid {tuple(grid[4:])} is too large to mesh")
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
+        raise MnerfError(f"tsdf_mesh: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
+                         f"{need} needed on {dev}")
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_mesh(_ptr(sums), _ptr(weight), *grid, float(min_weight), _ptr(vertices), vertices.numel() // VERTEX_FLOATS,
+                                  _ptr_i32(triangles), triangles.numel() // 3, _ptr(counts), _ptr(workspace), st), "mnerf_tsdf_mesh")
+    return vertices, triangles, counts

@@ -531,15 +531,43 @@ class MatchNeRF(torch.nn.Module):
         views [[hip.View] * K] * B, hw, counts [[rows of view k] * K] * B)).  The fusion geometry is pinhole z-depth: depth.param =
         inverse and another target camera model are refused, and so are gradients - all before the first launch."""
         from . import fusion
-        if self.opts.nerf.depth.param != "metric":
-            raise ValueError(f"export_points: nerf.depth.param={self.opts.nerf.depth.param!r}; the fusion geometry is metric camera-z depth")
-        if self.target_camera(batch, "test") is not None:
-            raise ValueError("export_points: the target camera is not a pinhole; the fusion geometry is pinhole camera-z depth")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("export_points is inference only; call it under torch.no_grad()")
         unknown = set(fuse_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"}
+        maps, cams_of = self._fusion_maps("export_points", batch, views, render_path_mode, unknown)
+        legacy = bool(self.opts.nerf.legacy_coord)
+        clouds, all_counts = [], []
+        for b, cams in enumerate(cams_of):
+            cloud, rows = fusion.fuse(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, return_counts=True, **fuse_args)
+            clouds.append(cloud), all_counts.append(rows)
+        if return_maps:
+            return clouds, edict(depth=maps.depth, opacity=maps.opacity, rgb=maps.rgb, views=cams_of, hw=maps.hw, counts=all_counts)
+        return clouds
+
+    MESH_ARGS = ("bounds", "resolution", "voxel", "trunc", "min_weight", "consistency")
+
+    def export_mesh(self, batch, views="sources", render_path_mode="interpolate", **mesh_args):
+        """The scene of ``batch`` as coloured triangle meshes -> a list over the batch of (vertices [V, 8] float32 rows
+        ``x y z w | r g b 0``, faces [T, 3] int32) on the device (``fusion.mesh``: the depth maps of ``export_points`` fused into a
+        truncated-signed-distance volume, its zero surface extracted by marching tetrahedra).  ``views`` and the one encoder pass as
+        in ``export_points``; ``mesh_args``: bounds, resolution, voxel, trunc, min_weight, consistency and the thresholds of
+        ``export_points``.  The same refusals, before the first launch."""
+        from . import fusion
+        unknown = set(mesh_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"} - set(self.MESH_ARGS)
+        maps, cams_of = self._fusion_maps("export_mesh", batch, views, render_path_mode, unknown)
+        legacy = bool(self.opts.nerf.legacy_coord)
+        return [fusion.mesh(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, **mesh_args)
+                for b, cams in enumerate(cams_of)]
+
+    def _fusion_maps(self, who, batch, views, render_path_mode, unknown):
+        """What ``export_points`` and ``export_mesh`` share: the refusals, ONE encoder pass, a render at each fusion pose ->
+        (edict(depth [B,K,h,w], opacity [B,K,h,w], rgb [B,K,h*w,3], hw), [[hip.View] * K] * B)."""
+        if self.opts.nerf.depth.param != "metric":
+            raise ValueError(f"{who}: nerf.depth.param={self.opts.nerf.depth.param!r}; the fusion geometry is metric camera-z depth")
+        if self.target_camera(batch, "test") is not None:
+            raise ValueError(f"{who}: the target camera is not a pinhole; the fusion geometry is pinhole camera-z depth")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(f"{who} is inference only; call it under torch.no_grad()")
         if unknown:
-            raise TypeError(f"export_points: unknown arguments {sorted(unknown)}")
+            raise TypeError(f"{who}: unknown arguments {sorted(unknown)}")
         self._frame = None
         self._cv_ops = None
         ref_images = batch.images[:, :self.n_src_views]
@@ -554,11 +582,11 @@ class MatchNeRF(torch.nn.Module):
             if isinstance(views, str) and views == "path":
                 poses = self.get_video_rendering_path(tgt_pose, ref_poses, render_path_mode, self.opts.nerf.video_n_frames, batch)
             elif isinstance(views, str):
-                raise ValueError(f"export_points: views={views!r}: 'sources', 'path' or a list of pose dicts")
+                raise ValueError(f"{who}: views={views!r}: 'sources', 'path' or a list of pose dicts")
             else:
                 poses = list(views)
         if len(poses) < 2:
-            raise ValueError(f"export_points: {len(poses)} fusion pose(s); cross-view consistency needs at least 2")
+            raise ValueError(f"{who}: {len(poses)} fusion pose(s); cross-view consistency needs at least 2")
         ref_feats_list = self.get_img_feat(ref_images, attn_splits_list=self.opts.encoder.attn_splits_list,
                                            cur_n_src_views=self.n_src_views)
         rets = [self.render(self.opts, p, mode="test", ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=ref_feats_list,
@@ -567,15 +595,8 @@ class MatchNeRF(torch.nn.Module):
         depth = torch.stack([r.depth[..., 0] for r in rets], 1).reshape(batch_size, len(poses), hw[0], hw[1])
         opacity = torch.stack([r.opacity[..., 0] for r in rets], 1).reshape(batch_size, len(poses), hw[0], hw[1])
         rgb = torch.stack([r.rgb for r in rets], 1)
-        legacy = bool(self.opts.nerf.legacy_coord)
-        clouds, all_views, all_counts = [], [], []
-        for b in range(batch_size):
-            cams = [hip.make_view(ex[b], it[b], nf[b, 0], nf[b, 1]) for ex, it, nf in hosts]
-            cloud, rows = fusion.fuse(cams, depth[b], opacity[b], rgb[b], hw, legacy, return_counts=True, **fuse_args)
-            clouds.append(cloud), all_views.append(cams), all_counts.append(rows)
-        if return_maps:
-            return clouds, edict(depth=depth, opacity=opacity, rgb=rgb, views=all_views, hw=hw, counts=all_counts)
-        return clouds
+        cams_of = [[hip.make_view(ex[b], it[b], nf[b, 0], nf[b, 1]) for ex, it, nf in hosts] for b in range(batch_size)]
+        return edict(depth=depth, opacity=opacity, rgb=rgb, hw=hw), cams_of
 
     def render_poses(self, opt, poses, ref_poses=None, ref_images=None, ref_feats_list=None, tgt_hw=None):
         """Full frames of SEVERAL target poses of one source set (the video loop of matchnerf.py:42-71) with as many poses per

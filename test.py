@@ -26,9 +26,13 @@ Geometry instead of images: ``--nerf.export_geometry=sources|path`` writes one c
 ``<output_path>/geometry/<set>/`` (``Coach.export_geometry``: depth maps rendered at the source views' poses, or along the video
 path, kept where the other poses confirm them), with ``--vis_depth`` also the colour-mapped depth maps.  Thresholds:
 ``--nerf.fuse_px_tol=<pixels>`` (1), ``--nerf.fuse_rel_tol=<relative depth>`` (0.01), ``--nerf.fuse_min_opacity`` (0.5),
-``--nerf.fuse_min_views=<confirming views>`` (min(2, K - 1)).
+``--nerf.fuse_min_views=<confirming views>`` (min(2, K - 1)).  With ``--nerf.export_mesh`` also a coloured triangle mesh of the same
+maps, ``<stem>_mesh.ply`` (TSDF fusion, marching tetrahedra): ``--nerf.mesh_resolution=<voxels along the longest side>`` (256),
+``--nerf.mesh_voxel=<world units>`` (instead of the resolution), ``--nerf.mesh_trunc=<world units>`` (4 voxels),
+``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)).
 
-    python test.py --yaml=demo_own --nerf.export_geometry=sources"""
+    python test.py --yaml=demo_own --nerf.export_geometry=sources
+    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192"""
 import os
 import sys
 
