@@ -352,7 +352,7 @@ class Coach:
         for bi, batch in enumerate(self.train_loader):
             if getattr(self.opts, "resume", False) and self.ep * n + bi < skip_to:
                 continue  # iterations the resumed run has already done
-            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+            var = self._to_device(batch)
             loss = self.train_iteration(var)
             if self.sched_type == "OneCycleLR":
                 self.sched.step()
@@ -504,6 +504,29 @@ class Coach:
             if metrics.batch_owner(bi, world) == rank:
                 yield bi, batch
 
+    def _to_device(self, batch):
+        """a loader's batch as an edict with its tensors on the run's device"""
+        return edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+
+    def _stem(self, batch, bi):
+        """`<scene>_view<tgt>_src<ids>` of batch element bi: the reference's name of its video (coach.py:507-509)"""
+        ids = [int(x) for x in batch["view_ids"][bi]] if "view_ids" in batch else list(range(self.n_src_views + 1))
+        scene = batch["scene"][bi] if "scene" in batch else f"scene{bi}"
+        return f"{scene}_view{ids[-1]:02d}_src" + "_".join(f"{x:02d}" for x in ids[:self.n_src_views])
+
+    def _path_mode(self, name, default=None):
+        """The video path of test set ``name``: llff spiral, colmap by its config, dtu / blender interpolate.  The reference has no
+        rule for the other sets (ibrnet, tnt, ...; coach.py:480-481): ``default`` where one is given, else an exception."""
+        if name == "llff":
+            return "spiral"
+        if name == "colmap":
+            return getattr(getattr(self.opts.data_test, "colmap", {}), "render_path_mode", "interpolate")
+        if name in ("dtu", "blender"):
+            return "interpolate"
+        if default is None:
+            raise Exception(f"Unknown dataset for rendering video {name}")
+        return default
+
     def _require_pinhole(self, what, batch=None):
         """Scored evaluation compares with the batch's target image, a pinhole photograph: another camera model (the option
         nerf.render_camera, or a batch.tgt_camera) has no ground truth to be scored against - test_model_video renders those."""
@@ -534,7 +557,7 @@ class Coach:
         for bi, batch in self._own_batches(loader, rank, world):
             if first_only and bi > 0:
                 break
-            var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+            var = self._to_device(batch)
             gt_depth = var.pop("depth") if "depth" in var else None  # forward overwrites 'depth'
             self._require_pinhole("evaluation", var)
             b, _, _, h, w = var.images.shape
@@ -683,18 +706,11 @@ class Coach:
             name = loader.get_name()
             out_dir = os.path.join(out_root, name)
             os.makedirs(out_dir, exist_ok=True)
-            if name == "llff":
-                mode = "spiral"
-            elif name == "colmap":
-                mode = getattr(getattr(self.opts.data_test, "colmap", {}), "render_path_mode", "interpolate")
-            elif name in ("dtu", "blender"):
-                mode = "interpolate"
-            else:  # coach.py:480-481: the reference has no video rule for the other sets (ibrnet, tnt, ...)
-                raise Exception(f"Unknown dataset for rendering video {name}")
+            mode = self._path_mode(name)
             self.model.nerf_setbg_opaque = (name == "blender")
             n_frames = int(self.opts.nerf.video_n_frames)
             for batch in loader:
-                var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+                var = self._to_device(batch)
                 # (coach.py:487-488 passes opts.nerf.render_video; this method IS the video test, so a config that leaves the
                 # switch off still gets the frames - and is told so once)
                 if not getattr(self.opts.nerf, "render_video", True) and not getattr(self, "_warned_render_video", False):
@@ -719,9 +735,7 @@ class Coach:
                 for bi in range(b):
                     clip = frames[:, bi]
                     videos.setdefault(name, clip)
-                    ids = [int(x) for x in batch["view_ids"][bi]] if "view_ids" in batch else list(range(self.n_src_views + 1))
-                    scene = batch["scene"][bi] if "scene" in batch else f"scene{bi}"
-                    stem = f"{scene}_view{ids[-1]:02d}_src" + "_".join(f"{x:02d}" for x in ids[:self.n_src_views])
+                    stem = self._stem(batch, bi)
                     if getattr(self.opts.nerf, "save_frames", False):
                         for fi, fr in enumerate(clip):
                             Image.fromarray(fr).save(os.path.join(out_dir, f"{stem}_f{fi}.jpg"))
@@ -765,20 +779,14 @@ class Coach:
             name = loader.get_name()
             out_dir = os.path.join(out_root, name)
             os.makedirs(out_dir, exist_ok=True)
-            mode = "interpolate"
-            if name == "llff":
-                mode = "spiral"
-            elif name == "colmap":
-                mode = getattr(getattr(self.opts.data_test, "colmap", {}), "render_path_mode", "interpolate")
+            mode = self._path_mode(name, default="interpolate")
             self.model.nerf_setbg_opaque = (name == "blender")
             for batch in loader:
-                var = edict({k: (v.to(self.opts.device) if torch.is_tensor(v) else v) for k, v in batch.items()})
+                var = self._to_device(batch)
                 clouds, maps = self.model.export_points(var, views=views, render_path_mode=mode, return_maps=True, **fuse_args)
                 panels = self._depth_panels(maps.depth, batch["near_fars"][:, -1]) if getattr(self.opts, "vis_depth", False) else None
                 for bi, cloud in enumerate(clouds):
-                    ids = [int(x) for x in batch["view_ids"][bi]] if "view_ids" in batch else list(range(self.n_src_views + 1))
-                    scene = batch["scene"][bi] if "scene" in batch else f"scene{bi}"
-                    stem = f"{scene}_view{ids[-1]:02d}_src" + "_".join(f"{x:02d}" for x in ids[:self.n_src_views])
+                    stem = self._stem(batch, bi)
                     path = os.path.join(out_dir, f"{stem}.ply")
                     n = fusion.write_ply(path, cloud)
                     written.setdefault(name, []).append(path)

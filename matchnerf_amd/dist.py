@@ -162,8 +162,7 @@ def render_frame_sharded(model, batch, mode="test", encoder="recompute"):
     from .edict import EasyDict as edict
     if encoder not in ("recompute", "shared"):
         raise ValueError(f"encoder={encoder!r}: expected 'recompute' or 'shared'")
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank, world = rank_world()
     _require_pinhole(model, batch, mode, "render_frame_sharded")
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)
@@ -190,8 +189,7 @@ def render_views_sharded(model, batch, poses, mode="test", encoder="shared"):
     from .edict import EasyDict as edict
     if encoder not in ("recompute", "shared"):
         raise ValueError(f"encoder={encoder!r}: expected 'recompute' or 'shared'")
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank, world = rank_world()
     _require_pinhole(model, batch, mode, "render_views_sharded")
     ref_images = batch.images[:, :model.n_src_views]
     feats = _source_features(model, ref_images, encoder)

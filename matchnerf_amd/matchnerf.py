@@ -15,6 +15,9 @@ fed by pair-major channel-last feature maps that stay resident in HBM for the wh
 
 The HIP path is the ONLY path: there is no eager fallback.  Without the shared library or
 without a GPU, rendering raises ``hip.MnerfError`` / ``RuntimeError``.
+
+Every inference path (pixel rays, ray bundles, pose tables) takes its scenes from ONE per-source-set context
+(``SourceSet``, through ``MatchNeRF._sources``) and walks batch elements and ray chunks in ONE loop (``launch_chunks``).
 """
 import os
 
@@ -38,6 +41,67 @@ MAX_RAYS_PER_POSE_LAUNCH = int(os.environ.get("MNERF_MAX_RAYS_PER_POSE_LAUNCH", 
 GRAD_RAYS_PER_CALL = 8192
 
 
+def launch_chunks(batch_size, n_rays, chunk, device, launch):
+    """The one batch-by-chunk loop of the render paths: allocates rgb [B,n_rays,3], depth [B,n_rays,1], opacity [B,n_rays,1] on
+    ``device`` and calls ``launch(b, first, count, rgb, depth, opacity)`` - the last three are the [count, C] slices of element b
+    to write - for every batch element and every run of at most ``chunk`` rays, in increasing order.  No rays: empty outputs and no
+    call, so a caller that builds scenes, operand images and workspaces from inside ``launch`` builds none."""
+    out = edict(rgb=torch.empty(batch_size, n_rays, 3, device=device), depth=torch.empty(batch_size, n_rays, 1, device=device),
+                opacity=torch.empty(batch_size, n_rays, 1, device=device))
+    for b in range(batch_size):
+        for c in range(0, n_rays, chunk):
+            m = min(chunk, n_rays - c)
+            launch(b, c, m, out.rgb[b, c:c + m], out.depth[b, c:c + m], out.opacity[b, c:c + m])
+    return out
+
+
+class SourceSet:
+    """Launch context of one source set, built once and shared by every target pose rendered from it (all frames of a video, all
+    chunks of a frame): host copies of the source cameras (they travel by value in the kernel arguments), the channel-last RGBA
+    copy of the source images and, per batch element on first use, the ``hip.Scene`` and - for a matrix-form launch - the
+    split-fp16 operand image of the feature maps (``hip.cost_volume_operands``: two short launches, ~the bytes of the maps).
+    ``key`` is the identity, version and shape of ``keyed`` = (images, extrinsics, intrinsics, near_fars, *feature maps), so
+    in-place edits or a new batch rebuild the context; it holds the keyed tensors themselves, so their storage cannot be freed and
+    handed to a NEW batch at the same address while it lives (the caching allocator does exactly that in the reference's coach
+    loop), and ``forward`` drops it at its top: a context is shared by the poses and chunks of ONE forward, never by two batches."""
+
+    def __init__(self, key, keyed, n_views, groups):
+        self.key, self.keyed, self.n_views = key, keyed, n_views
+        ref_images, self.feats = keyed[0], list(keyed[4:])
+        self.groups = [groups] if isinstance(groups, int) else list(groups)
+        self.host = tuple(MatchNeRF._host(t) for t in keyed[1:4])  # extrinsics [B,V,3,4], intrinsics [B,V,3,3], near_fars [B,V,2]
+        b, v, _, h, w = ref_images.shape
+        self.images_cl = torch.zeros(b, v, h, w, 4, device=ref_images.device)
+        self.images_cl[..., :3] = ref_images.detach().permute(0, 1, 3, 4, 2)
+        self._scenes, self._ops = {}, {}
+
+    def build(self, b, feats_b):
+        """A fresh ``hip.Scene`` of batch element b over the per-scale maps ``feats_b`` [P,2,h,w,128] (the cached scenes pass
+        slices of the keyed maps, the training path the tensors autograd hands it)."""
+        sc = hip.Scene()
+        sc.n_views, sc.n_scales = self.n_views, len(feats_b)
+        assert len(self.groups) == len(feats_b), "cos_n_group needs one entry per feature scale"
+        for s, f in enumerate(feats_b):
+            assert f.is_contiguous()
+            sc.fh[s], sc.fw[s] = f.shape[2], f.shape[3]
+            sc.n_group[s] = self.groups[s]
+            sc.feat[s] = f.data_ptr()
+        sc.images = self.images_cl[b].data_ptr()
+        ex, it, nf = self.host
+        for v in range(self.n_views):
+            sc.views[v] = hip.make_view(ex[b, v], it[b, v], nf[b, v, 0], nf[b, v, 1])
+        return sc
+
+    def scene(self, b, matrix_form=False):
+        """The scene of batch element b, built on first use.  ``matrix_form``: the one whose ``feat_op`` names the operand image,
+        which sends the cost volume to the matrix pipe; without it a struct of its own, whose ``feat_op`` stays unset (the walk)."""
+        if (b, matrix_form) not in self._scenes:
+            sc = self._scenes[b, matrix_form] = self.build(b, [f[b] for f in self.feats])
+            if matrix_form:
+                self._ops[b] = hip.cost_volume_operands(sc, device=self.feats[0].device)
+        return self._scenes[b, matrix_form]
+
+
 class MatchNeRF(torch.nn.Module):
     def __init__(self, opts):
         super().__init__()
@@ -58,7 +122,7 @@ class MatchNeRF(torch.nn.Module):
         self._ws = None
         self._enc_graphs = {}     # captured encoder passes (get_img_feat), keyed by input shape and weight versions
         self.encoder_graph = os.environ.get("MNERF_ENCODER_GRAPH", "0") == "1"  # opt-in: measured no gain (see _encoder_graph_replay)
-        self._frame = None        # per-source-set launch context (host camera copies, RGBA images): see _frame_ctx
+        self._src = None          # the SourceSet of the forward in flight: see _sources
         self.kernel_timer = None  # hip.KernelTimer: per-kernel event timing (bench.py)
         self.fused_render = False  # True: ray chunks take the one-launch form where it exists (slower on MI355X: DESIGN.md)
         # video of small frames: several poses per launch through a pose table (mnerf_rays.pose_table).  OFF by default since
@@ -67,7 +131,6 @@ class MatchNeRF(torch.nn.Module):
         # (DESIGN.md section 4).  MNERF_POSE_BATCHING=1 brings it back; tests/test_pose_table_gpu.py keeps it bit-identical.
         self.pose_batching = os.environ.get("MNERF_POSE_BATCHING", "0") == "1"
         self.cv_matrix_form = os.environ.get("MNERF_CV_MM", "1") != "0"  # full-frame renders: the cost volume on the matrix pipe
-        self._cv_ops = None
 
     def _dec(self):
         """the CondNeRF module, also when the reference's coach wrapped it in nn.DataParallel (coach.py:83-85)"""
@@ -75,8 +138,7 @@ class MatchNeRF(torch.nn.Module):
 
     # ------------------------------------------------------------------ forward (matchnerf.py:32-73)
     def forward(self, batch, mode=None, render_video=False, render_path_mode="interpolate"):
-        self._frame = None  # the launch context below never outlives one forward (see _frame_ctx)
-        self._cv_ops = None
+        self._src = None  # the launch context never outlives one forward (see SourceSet)
         ref_images = batch.images[:, :self.n_src_views]
         tgt_pose, ref_poses = self.extract_poses(batch)
         batch_size, _, _, img_h, img_w = ref_images.shape
@@ -284,44 +346,13 @@ class MatchNeRF(torch.nn.Module):
         return [o.clone() for o in static_out]
 
     # ------------------------------------------------------------------ C-ABI argument structs
-    def _scene(self, b, ref_poses_host, ref_feats_list, images_cl, feats_b=None):
-        """``feats_b``: per-scale maps [P,2,h,w,128] of batch element b (default: slices of
-        ``ref_feats_list``)."""
-        if feats_b is None:
-            feats_b = [f[b] for f in ref_feats_list]
-        sc = hip.Scene()
-        sc.n_views, sc.n_scales = self.n_src_views, len(feats_b)
-        groups = self.opts.encoder.cos_n_group
-        groups = [groups] if isinstance(groups, int) else list(groups)
-        assert len(groups) == len(feats_b), "cos_n_group needs one entry per feature scale"
-        for s, f in enumerate(feats_b):
-            assert f.is_contiguous()
-            sc.fh[s], sc.fw[s] = f.shape[2], f.shape[3]
-            sc.n_group[s] = groups[s]
-            sc.feat[s] = f.data_ptr()
-        sc.images = images_cl[b].data_ptr()
-        ex, it, nf = ref_poses_host
-        for v in range(self.n_src_views):
-            sc.views[v] = hip.make_view(ex[b, v], it[b, v], nf[b, v, 0], nf[b, v, 1])
-        return sc
-
-    def _scene_mm(self, b, ref_poses_host, ref_feats_list, images_cl):
-        """``_scene`` + the split-fp16 operand image of the feature maps (``hip.cost_volume_operands``, ABI v9) that the matrix
-        form of the cost volume reads: built once per source set and batch element (two short launches, ~the bytes of the maps),
-        shared by every pose and ray chunk rendered from it.  Keyed on the identity and version of the maps; the entry holds the
-        maps themselves (see ``_frame_ctx`` for why) and ``forward`` drops it at its top.  MNERF_CV_MM=0 keeps the walk."""
-        sc = self._scene(b, ref_poses_host, ref_feats_list, images_cl)
-        if not self.cv_matrix_form:
-            return sc
-        key = tuple((f.data_ptr(), f._version, tuple(f.shape)) for f in ref_feats_list)
-        if self._cv_ops is None or self._cv_ops[0] != key:
-            self._cv_ops = (key, {}, list(ref_feats_list))
-        ops = self._cv_ops[1]
-        if b not in ops:
-            ops[b] = hip.cost_volume_operands(sc, device=ref_feats_list[0].device)
-        else:
-            sc.feat_op = ops[b].data_ptr()
-        return sc
+    def _sources(self, ref_poses, ref_images, ref_feats_list):
+        """The ``SourceSet`` of these source views, cameras and feature maps: the cached one while its key matches."""
+        keyed = (ref_images, ref_poses["extrinsics"], ref_poses["intrinsics"], ref_poses["near_fars"], *ref_feats_list)
+        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in keyed)
+        if self._src is None or self._src.key != key:
+            self._src = SourceSet(key, keyed, self.n_src_views, self.opts.encoder.cos_n_group)
+        return self._src
 
     def _decoder(self, n_samples, device):
         return self._dec().decoder_struct(n_samples, device, self.nerf_setbg_opaque)
@@ -335,24 +366,23 @@ class MatchNeRF(torch.nn.Module):
     def _host(t):
         return t.detach().float().cpu().numpy()
 
-    def _frame_ctx(self, ref_poses, ref_images):
-        """Launch context of one source set, built once and shared by every target pose rendered from it (all
-        frames of a video, all chunks of a frame): host copies of the source cameras (they travel by value in the
-        kernel arguments) and the channel-last RGBA copy of the source images.  Keyed on the identity and version
-        of the tensors, so in-place edits or a new batch rebuild it; the entry holds the keyed tensors themselves, so
-        their storage cannot be freed and handed to a NEW batch at the same address while the entry lives (the caching
-        allocator does exactly that in the reference's coach loop), and ``forward`` drops the entry at its top: a
-        context is shared by the poses and chunks of ONE forward, never by two batches."""
-        keyed = (ref_images, ref_poses["extrinsics"], ref_poses["intrinsics"], ref_poses["near_fars"])
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in keyed)
-        if self._frame is None or self._frame[0] != key:
-            b, v, _, h, w = ref_images.shape
-            ref_host = (self._host(ref_poses["extrinsics"]), self._host(ref_poses["intrinsics"]),
-                        self._host(ref_poses["near_fars"]))
-            images_cl = torch.zeros(b, v, h, w, 4, device=ref_images.device)
-            images_cl[..., :3] = ref_images.detach().permute(0, 1, 3, 4, 2)
-            self._frame = (key, ref_host, images_cl, keyed)
-        return self._frame[1], self._frame[2]
+    def _needs_grad(self, ref_feats_list):
+        return torch.is_grad_enabled() and (any(f.requires_grad for f in ref_feats_list) or
+                                            any(p.requires_grad for p in self._dec().parameters()))
+
+    @staticmethod
+    def _ray_opts(opt, ref_images, n_samples=None):
+        """What every ray struct takes from the options and the source views -> ((n_samples, height, width), dict(legacy=...,
+        depth_inverse=...)): the arguments of ``hip.make_rays`` / ``hip.make_free_rays`` after the ray count, and their keywords."""
+        n_samples = int(opt.nerf.sample_intvs) if n_samples is None else int(n_samples)
+        return (n_samples, ref_images.shape[-2], ref_images.shape[-1]), dict(legacy=bool(opt.nerf.legacy_coord),
+                                                                             depth_inverse=(opt.nerf.depth.param == "inverse"))
+
+    @staticmethod
+    def _box_filter(out, h, w, k):
+        """The k x k supersampled rows of a (h, w) frame, per output [B, k h k w, C] -> [B, h w, C] (``hip.box_downsample``)."""
+        return edict({key: torch.stack([hip.box_downsample(v[b], h, w, k).reshape(h * w, v.shape[-1]) for b in range(v.shape[0])], 0)
+                      for key, v in out.items()})
 
     def _tgt_host(self, tgt_pose):
         """(extrinsics, intrinsics, near_fars) of the target pose on the host; poses generated on the host
@@ -377,8 +407,8 @@ class MatchNeRF(torch.nn.Module):
         batch_size, _, _, img_h, img_w = ref_images.shape
         tgt_h, tgt_w = (img_h, img_w) if tgt_hw is None else (int(tgt_hw[0]), int(tgt_hw[1]))
         device = ref_images.device
-        n_samples = int(opt.nerf.sample_intvs)
-        legacy = bool(opt.nerf.legacy_coord)
+        size, ray_kw = self._ray_opts(opt, ref_images)
+        n_samples, legacy = size[0], ray_kw["legacy"]
         assert ray_idx is None or ray_range is None
         if int(ssaa) > 1:
             return self._render_ssaa(opt, tgt_pose, int(ssaa), (tgt_h, tgt_w), ray_idx, ray_range, mode, ref_poses, ref_images,
@@ -389,10 +419,8 @@ class MatchNeRF(torch.nn.Module):
         idx32 = None if ray_idx is None else ray_idx.to(device=device, dtype=torch.int32).contiguous()
         stratified = mode == "train" and bool(opt.nerf.sample_stratified)
 
-        dec_mod = self._dec()
-        needs_grad = torch.is_grad_enabled() and (any(f.requires_grad for f in ref_feats_list) or
-                                                  any(p.requires_grad for p in dec_mod.parameters()))
-        ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
+        needs_grad = self._needs_grad(ref_feats_list)
+        src = self._sources(ref_poses, ref_images, ref_feats_list)
         tgt_ex, tgt_in, tgt_nf = self._tgt_host(tgt_pose)
         if (needs_grad or mode == "train") and (tgt_h, tgt_w) != (img_h, img_w):
             raise NotImplementedError(f"a target grid {(tgt_h, tgt_w)} other than the views' {(img_h, img_w)} is inference only "
@@ -400,32 +428,25 @@ class MatchNeRF(torch.nn.Module):
         if needs_grad:
             if ray_range is not None:
                 ray_idx = torch.arange(pix0, pix0 + n_rays, device=device)
-            return self._render_with_grad(opt, ref_host, (tgt_ex, tgt_in, tgt_nf), ray_idx, stratified, ref_images,
-                                          ref_feats_list, images_cl, n_rays, n_samples, img_h, img_w)
+            return self._render_with_grad(opt, src, (tgt_ex, tgt_in, tgt_nf), ray_idx, stratified, ref_images, ref_feats_list, n_rays)
         dec = self._decoder(n_samples, device)
-        chunk = min(n_rays, MAX_RAYS_PER_LAUNCH)
-        ws = None  # [rays*S, cond_stride] hand-off buffer of the staged form
-        rgb = torch.empty(batch_size, n_rays, 3, device=device)
-        depth = torch.empty(batch_size, n_rays, 1, device=device)
-        opacity = torch.empty(batch_size, n_rays, 1, device=device)
-        for b in range(batch_size):
-            sc = self._scene(b, ref_host, ref_feats_list, images_cl) if idx32 is not None else \
-                self._scene_mm(b, ref_host, ref_feats_list, images_cl)
-            kinv, c2w = camera.target_ray_consts(tgt_ex[b], tgt_in[b], legacy)
-            strat = torch.rand(n_rays, n_samples, device=device) if stratified else None
-            for c in range(0, n_rays, chunk):
-                m = min(chunk, n_rays - c)
-                rays = hip.make_rays(
-                    m, n_samples, img_h, img_w, kinv, c2w, tgt_nf[b, 0], tgt_nf[b, 1], ray_begin=pix0 + c, legacy=legacy,
-                    depth_inverse=(opt.nerf.depth.param == "inverse"),
-                    ray_idx_ptr=None if idx32 is None else idx32[c:].data_ptr(),
-                    strat_u_ptr=None if strat is None else strat[c:].data_ptr(), tgt_hw=(tgt_h, tgt_w))
-                fused = self.fused_render and hip.render_is_fused(sc, dec, rays)
-                if ws is None and not fused:
-                    ws = self._workspace(hip.render_workspace_bytes(chunk, n_samples, dec.cond_stride) // 4, device)
-                hip.render_chunk(sc, dec, rays, ws, rgb[b, c:c + m], depth[b, c:c + m], opacity[b, c:c + m],
-                                 timer=self.kernel_timer, fused=fused)
-        return edict(rgb=rgb, depth=depth, opacity=opacity)
+        # [rays*S, cond_stride] hand-off buffer of the staged form: sized for the largest chunk, requested by the first chunk that
+        # needs it
+        ws_floats = hip.render_workspace_bytes(min(n_rays, MAX_RAYS_PER_LAUNCH), n_samples, dec.cond_stride) // 4
+        consts = [camera.target_ray_consts(tgt_ex[b], tgt_in[b], legacy) for b in range(batch_size)]
+        strats = [torch.rand(n_rays, n_samples, device=device) for _ in range(batch_size)] if stratified else None
+
+        def launch(b, c, m, *outs):
+            # contiguous pixel runs take the matrix form of the cost volume (MNERF_CV_MM=0 keeps the walk); a ray_idx list walks
+            sc = src.scene(b, matrix_form=self.cv_matrix_form and idx32 is None)
+            rays = hip.make_rays(m, *size, *consts[b], tgt_nf[b, 0], tgt_nf[b, 1], ray_begin=pix0 + c,
+                                 ray_idx_ptr=None if idx32 is None else idx32[c:].data_ptr(),
+                                 strat_u_ptr=None if strats is None else strats[b][c:].data_ptr(), tgt_hw=(tgt_h, tgt_w), **ray_kw)
+            fused = self.fused_render and hip.render_is_fused(sc, dec, rays)
+            hip.render_chunk(sc, dec, rays, None if fused else self._workspace(ws_floats, device), *outs,
+                             timer=self.kernel_timer, fused=fused)
+
+        return launch_chunks(batch_size, n_rays, MAX_RAYS_PER_LAUNCH, device, launch)
 
     def _render_ssaa(self, opt, tgt_pose, k, tgt_hw, ray_idx, ray_range, mode, ref_poses, ref_images, ref_feats_list):
         """``render`` with k x k rays per pixel: rows [r0, r1) of the (h, w) frame are rows [k r0, k r1) of the (k h, k w) frame of the
@@ -437,12 +458,10 @@ class MatchNeRF(torch.nn.Module):
         pix0, n = (0, h * w) if ray_range is None else (int(ray_range[0]), int(ray_range[1]))
         if pix0 % w or n % w:
             raise ValueError(f"render: ssaa > 1 needs a ray_range of whole rows, got ({pix0}, {n}) at width {w}")
-        rows = n // w
         hi = self.render(opt, self.resize_pose(tgt_pose, (h, w), (k * h, k * w), bool(opt.nerf.legacy_coord)), mode=mode,
                          ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=ref_feats_list,
                          ray_range=(k * k * pix0, k * k * n), tgt_hw=(k * h, k * w))
-        return edict({key: torch.stack([hip.box_downsample(v[b], rows, w, k).reshape(n, -1) for b in range(v.shape[0])], 0)
-                      for key, v in hi.items()})
+        return self._box_filter(hi, n // w, w, k)
 
     # ------------------------------------------------------------------ caller-supplied rays (include/mnerf.h)
     def render_rays(self, opt, ray_o, ray_d, near_far, mode=None, ref_poses=None, ref_images=None, ref_feats_list=None):
@@ -470,33 +489,25 @@ class MatchNeRF(torch.nn.Module):
         return self._render_bundles(opt, bundles, nf, ref_poses, ref_images, ref_feats_list)
 
     def _inference_only(self, mode, ref_feats_list, who):
-        needs_grad = torch.is_grad_enabled() and (any(f.requires_grad for f in ref_feats_list) or
-                                                  any(p.requires_grad for p in self._dec().parameters()))
-        if needs_grad or mode == "train":  # (before the first launch)
+        if self._needs_grad(ref_feats_list) or mode == "train":  # (before the first launch)
             raise NotImplementedError(f"{who}: caller-supplied rays are inference only (no backward kernels over a ray bundle); "
                                       "call it under torch.no_grad() and outside mode='train'")
 
     def _render_bundles(self, opt, bundles, near_far_host, ref_poses, ref_images, ref_feats_list):
-        """``bundles``: per batch element a ray bundle [N, 8] on the device -> edict(rgb, depth, opacity)."""
-        batch_size, _, _, img_h, img_w = ref_images.shape
+        """``bundles``: per batch element a ray bundle [N, 8] on the device -> edict(rgb, depth, opacity).  Bundles stay on the
+        segment walk of the cost volume."""
         device = ref_images.device
-        n_samples = int(opt.nerf.sample_intvs)
+        size, ray_kw = self._ray_opts(opt, ref_images)
         n_rays = int(bundles[0].shape[0])
-        ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
-        dec = self._decoder(n_samples, device)
-        chunk = max(1, min(n_rays, MAX_RAYS_PER_LAUNCH))
-        ws = self._workspace(hip.render_rays_workspace_bytes(chunk, n_samples, dec.cond_stride) // 4, device)
-        rgb = torch.empty(batch_size, n_rays, 3, device=device)
-        depth = torch.empty(batch_size, n_rays, 1, device=device)
-        opacity = torch.empty(batch_size, n_rays, 1, device=device)
-        for b in range(batch_size):
-            sc = self._scene(b, ref_host, ref_feats_list, images_cl)
-            for c in range(0, n_rays, chunk):
-                m = min(chunk, n_rays - c)
-                rays = hip.make_free_rays(m, n_samples, img_h, img_w, near_far_host[b, 0], near_far_host[b, 1],
-                                          legacy=bool(opt.nerf.legacy_coord), depth_inverse=(opt.nerf.depth.param == "inverse"))
-                hip.render_rays(sc, dec, rays, bundles[b][c:c + m], ws, rgb[b, c:c + m], depth[b, c:c + m], opacity[b, c:c + m])
-        return edict(rgb=rgb, depth=depth, opacity=opacity)
+        src = self._sources(ref_poses, ref_images, ref_feats_list)
+        dec = self._decoder(size[0], device)
+        ws_floats = hip.render_rays_workspace_bytes(min(n_rays, MAX_RAYS_PER_LAUNCH), size[0], dec.cond_stride) // 4
+
+        def launch(b, c, m, *outs):
+            rays = hip.make_free_rays(m, *size, near_far_host[b, 0], near_far_host[b, 1], **ray_kw)
+            hip.render_rays(src.scene(b), dec, rays, bundles[b][c:c + m], self._workspace(ws_floats, device), *outs)
+
+        return launch_chunks(ref_images.shape[0], n_rays, MAX_RAYS_PER_LAUNCH, device, launch)
 
     def render_camera(self, opt, tgt_pose, tgt_camera, tgt_hw, ssaa=1, mode=None, ref_poses=None, ref_images=None,
                       ref_feats_list=None):
@@ -513,10 +524,7 @@ class MatchNeRF(torch.nn.Module):
         bundles = [hip.camera_rays(camera.camera_model(tgt_camera["model"], k * h, k * w, tgt_ex[b], tgt_in[b], legacy, **args),
                                    device=ref_images.device) for b in range(batch_size)]
         out = self._render_bundles(opt, bundles, np.asarray(tgt_nf).reshape(batch_size, 2), ref_poses, ref_images, ref_feats_list)
-        if k == 1:
-            return out
-        return edict({key: torch.stack([hip.box_downsample(v[b], h, w, k).reshape(h * w, -1) for b in range(batch_size)], 0)
-                      for key, v in out.items()})
+        return out if k == 1 else self._box_filter(out, h, w, k)
 
     # ------------------------------------------------------------------ geometry export (matchnerf_amd/fusion.py)
     def export_points(self, batch, views="sources", render_path_mode="interpolate", return_maps=False, **fuse_args):
@@ -568,8 +576,7 @@ class MatchNeRF(torch.nn.Module):
             raise NotImplementedError(f"{who} is inference only; call it under torch.no_grad()")
         if unknown:
             raise TypeError(f"{who}: unknown arguments {sorted(unknown)}")
-        self._frame = None
-        self._cv_ops = None
+        self._src = None
         ref_images = batch.images[:, :self.n_src_views]
         tgt_pose, ref_poses = self.extract_poses(batch)
         batch_size, _, _, img_h, img_w = ref_images.shape
@@ -614,7 +621,8 @@ class MatchNeRF(torch.nn.Module):
         per_launch = MAX_RAYS_PER_POSE_LAUNCH // n_pix
         if per_launch < 2 or len(poses) < 2 or not ref_images.is_cuda or self.fused_render:
             return None
-        n_samples = int(opt.nerf.sample_intvs)
+        size, ray_kw = self._ray_opts(opt, ref_images)
+        n_samples = size[0]
         # the hand-off rows of a launch are rays x S x cond_stride floats (3.2 GB for 262 144 rays at S = 128): never more than
         # a quarter of what the device has free, so that a smaller card renders with fewer poses per launch instead of failing
         if ref_images.is_cuda:
@@ -623,55 +631,38 @@ class MatchNeRF(torch.nn.Module):
             per_launch = max(1, min(per_launch, int(free // 4 // max(row_bytes, 1))))
             if per_launch < 2:
                 return None
-        legacy = bool(opt.nerf.legacy_coord)
-        ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
+        src = self._sources(ref_poses, ref_images, ref_feats_list)
         dec = self._decoder(n_samples, device)
-        scenes = [self._scene(b, ref_host, ref_feats_list, images_cl) for b in range(batch_size)]
-        if not all(hip.render_takes_pose_table(sc, dec, n_samples, n_pix) for sc in scenes):
+        if not all(hip.render_takes_pose_table(src.scene(b), dec, n_samples, n_pix) for b in range(batch_size)):  # (the walk)
             return None
         n_poses = len(poses)
         hosts = [self._tgt_host(p) for p in poses]
         rows = np.zeros((batch_size, n_poses, hip.MNERF_POSE_FLOATS), np.float32)
         for b in range(batch_size):
-            rows[b] = hip.pose_table_rows([camera.target_ray_consts(ex[b], it[b], legacy) + (nf[b, 0], nf[b, 1])
+            rows[b] = hip.pose_table_rows([camera.target_ray_consts(ex[b], it[b], ray_kw["legacy"]) + (nf[b, 0], nf[b, 1])
                                            for ex, it, nf in hosts])
         table = torch.from_numpy(rows).to(device)  # one small copy per video; stream-ordered before the launches
-        rgb = torch.empty(n_poses, batch_size, n_pix, 3, device=device)
-        depth = torch.empty(n_poses, batch_size, n_pix, 1, device=device)
-        opacity = torch.empty(n_poses, batch_size, n_pix, 1, device=device)
-        # outputs of a launch are [poses of the group] x [pixels]: a contiguous scratch block per launch, then one strided copy
-        # into the frame-major result (the batch dimension sits between pose and pixel there)
-        ws = self._workspace(hip.render_workspace_bytes(per_launch * n_pix, n_samples, dec.cond_stride) // 4, device)
-        contiguous_out = batch_size == 1
-        if not contiguous_out:
-            tmp = [torch.empty(per_launch * n_pix, c, device=device) for c in (3, 1, 1)]
-        for b in range(batch_size):
-            kinv, c2w = rows[b, 0, :9], rows[b, 0, 9:21]
-            for p0 in range(0, n_poses, per_launch):
-                g = min(per_launch, n_poses - p0)
-                rays = hip.make_rays(g * n_pix, n_samples, img_h, img_w, kinv, c2w, rows[b, 0, 21], rows[b, 0, 22],
-                                     ray_begin=p0 * n_pix, legacy=legacy, depth_inverse=(opt.nerf.depth.param == "inverse"),
-                                     pose_table_ptr=table[b].data_ptr(), rays_per_pose=n_pix, tgt_hw=tgt_hw)
-                if contiguous_out:
-                    outs = (rgb[p0:p0 + g, 0].reshape(-1, 3), depth[p0:p0 + g, 0].reshape(-1, 1),
-                            opacity[p0:p0 + g, 0].reshape(-1, 1))
-                else:
-                    outs = tuple(t[:g * n_pix] for t in tmp)
-                hip.render_chunk(scenes[b], dec, rays, ws, *outs, timer=self.kernel_timer, fused=False)
-                if not contiguous_out:
-                    for dst, src in zip((rgb, depth, opacity), outs):
-                        dst[p0:p0 + g, b] = src.view(g, n_pix, -1)
-        return edict(rgb=rgb, depth=depth, opacity=opacity)
+        chunk = per_launch * n_pix
+        ws_floats = hip.render_workspace_bytes(min(n_poses * n_pix, chunk), n_samples, dec.cond_stride) // 4
 
-    def _render_with_grad(self, opt, ref_host, tgt_host, ray_idx, stratified, ref_images, ref_feats_list, images_cl,
-                          n_rays, n_samples, img_h, img_w):
+        def launch(b, c, m, *outs):  # "rays" = poses x pixels: the outputs of a launch are [poses of the group] x [pixels]
+            rays = hip.make_rays(m, *size, rows[b, 0, :9], rows[b, 0, 9:21], rows[b, 0, 21], rows[b, 0, 22], ray_begin=c,
+                                 pose_table_ptr=table[b].data_ptr(), rays_per_pose=n_pix, tgt_hw=tgt_hw, **ray_kw)
+            hip.render_chunk(src.scene(b), dec, rays, self._workspace(ws_floats, device), *outs, timer=self.kernel_timer, fused=False)
+
+        out = launch_chunks(batch_size, n_poses * n_pix, chunk, device, launch)
+        # [B, n_poses * N, C] -> the pose-major result (the batch dimension sits between pose and pixel there; no copy at B = 1)
+        return edict({k: v.view(batch_size, n_poses, n_pix, -1).transpose(0, 1).contiguous() for k, v in out.items()})
+
+    def _render_with_grad(self, opt, src, tgt_host, ray_idx, stratified, ref_images, ref_feats_list, n_rays):
         """Training path (matchnerf_amd/autograd.py): forward through the HIP kernels; backward = HIP kernels end to end for the
         ray chunk (mnerf_composite_backward -> mnerf_decoder_backward -> mnerf_cost_volume_backward).  Rays go through in
         chunks of GRAD_RAYS_PER_CALL so that a full-image call under autograd keeps the decoder backward's workspace (11.2 KB
-        per sample) bounded."""
+        per sample) bounded.  Scenes are built (``SourceSet.build``) over the feature tensors autograd hands each node."""
         from . import autograd as ag
         device = ref_images.device
-        legacy = bool(opt.nerf.legacy_coord)
+        size, ray_kw = self._ray_opts(opt, ref_images)
+        n_samples = size[0]
         tgt_ex, tgt_in, tgt_nf = tgt_host
         batch_size = ref_images.shape[0]
         idx_all = torch.arange(n_rays, device=device) if ray_idx is None else ray_idx.to(device)
@@ -679,7 +670,7 @@ class MatchNeRF(torch.nn.Module):
         outs = []
         for b in range(batch_size):
             strat_all = torch.rand(n_rays, n_samples, device=device) if stratified else None
-            kinv, c2w = camera.target_ray_consts(tgt_ex[b], tgt_in[b], legacy)
+            kinv, c2w = camera.target_ray_consts(tgt_ex[b], tgt_in[b], ray_kw["legacy"])
             parts = []
             for c in range(0, n_rays, GRAD_RAYS_PER_CALL):
                 idx = idx_all[c:c + GRAD_RAYS_PER_CALL]
@@ -688,15 +679,14 @@ class MatchNeRF(torch.nn.Module):
                 m = int(idx.numel())
 
                 def make_rays(strat=strat, kinv=kinv, c2w=c2w, idx32=idx32, m=m, b=b):
-                    r = hip.make_rays(m, n_samples, img_h, img_w, kinv, c2w, tgt_nf[b, 0], tgt_nf[b, 1], legacy=legacy,
-                                      depth_inverse=(opt.nerf.depth.param == "inverse"), ray_idx_ptr=idx32.data_ptr(),
-                                      strat_u_ptr=None if strat is None else strat.data_ptr())
+                    r = hip.make_rays(m, *size, kinv, c2w, tgt_nf[b, 0], tgt_nf[b, 1], ray_idx_ptr=idx32.data_ptr(),
+                                      strat_u_ptr=None if strat is None else strat.data_ptr(), **ray_kw)
                     return r, (idx32, strat)  # the struct holds raw pointers: keep the tensors alive with it
 
                 launch = ag.RayChunkLaunch(
-                    opt, dec_mod, make_scene=lambda feats, b=b: self._scene(b, ref_host, None, images_cl, feats_b=feats),
+                    opt, dec_mod, make_scene=lambda feats, b=b: src.build(b, feats),
                     make_rays=make_rays, make_decoder=lambda: self._decoder(n_samples, device),
-                    view0_extr=ref_host[0][b, 0], kinv=kinv, c2w=c2w, ray_idx=idx, width=img_w, n_views=self.n_src_views,
+                    view0_extr=src.host[0][b, 0], kinv=kinv, c2w=c2w, ray_idx=idx, width=size[2], n_views=self.n_src_views,
                     setbg_opaque=bool(self.nerf_setbg_opaque))
                 parts.append(ag.render_ray_chunk(launch, [f[b] for f in ref_feats_list]))
             outs.append([torch.cat([p[k] for p in parts], 0) for k in range(3)])
@@ -734,24 +724,21 @@ class MatchNeRF(torch.nn.Module):
         if tgt_pose is None:
             raise NotImplementedError("query_cond_info needs tgt_pose: the HIP kernel regenerates the 3D samples")
         b_n, n_rays, n_samples = point_samples.shape[:3]
-        _, v, _, img_h, img_w = ref_images.shape
+        v = ref_images.shape[1]
         device = ref_images.device
-        ref_host, images_cl = self._frame_ctx(ref_poses, ref_images)
+        size, ray_kw = self._ray_opts(self.opts, ref_images, n_samples)
+        src = self._sources(ref_poses, ref_images, ref_feats_list)
         dc = self._dec().cond_dim
         stride = ((dc + 1 + 7) // 8) * 8
         sum_g = dc - 4 * v
         out = torch.empty(b_n, n_rays * n_samples, stride, device=device)
         idx32 = None if ray_idx is None else ray_idx.to(device=device, dtype=torch.int32).contiguous()
+        t_ex, t_in, t_nf = self._tgt_host(tgt_pose)
         for b in range(b_n):
-            sc = self._scene(b, ref_host, ref_feats_list, images_cl)
-            t_ex, t_in, t_nf = self._tgt_host(tgt_pose)
-            kinv, c2w = camera.target_ray_consts(t_ex[b], t_in[b], bool(self.opts.nerf.legacy_coord))
-            nf = t_nf[b]
-            rays = hip.make_rays(n_rays, n_samples, img_h, img_w, kinv, c2w, nf[0], nf[1],
-                                 legacy=bool(self.opts.nerf.legacy_coord),
-                                 depth_inverse=(self.opts.nerf.depth.param == "inverse"),
-                                 ray_idx_ptr=None if idx32 is None else idx32.data_ptr())
-            hip.cost_volume(sc, rays, stride, out=out[b])
+            kinv, c2w = camera.target_ray_consts(t_ex[b], t_in[b], ray_kw["legacy"])
+            rays = hip.make_rays(n_rays, *size, kinv, c2w, t_nf[b, 0], t_nf[b, 1],
+                                 ray_idx_ptr=None if idx32 is None else idx32.data_ptr(), **ray_kw)
+            hip.cost_volume(src.scene(b), rays, stride, out=out[b])
         out = out.reshape(b_n, n_rays, n_samples, stride)
         return dict(feat_info=out[..., :sum_g], color_info=out[..., sum_g:sum_g + 3 * v],
                     mask_info=out[..., sum_g + 3 * v:dc])

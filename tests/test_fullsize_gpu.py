@@ -187,9 +187,7 @@ def test_fullsize_opacity_closed_form_and_cost_volume_range(full_frame):
     with torch.no_grad():
         feats = model.get_img_feat(batch.images[:, :3], cur_n_src_views=3)
     host = lambda t: t.detach().float().cpu().numpy()
-    images_cl = torch.zeros(1, 3, 512, 640, 4, device="cuda")
-    images_cl[..., :3] = batch.images[:, :3].permute(0, 1, 3, 4, 2)
-    sc = model._scene_mm(0, (host(ref["extrinsics"]), host(ref["intrinsics"]), host(ref["near_fars"])), feats, images_cl)
+    sc = model._sources(ref, batch.images[:, :3], feats).scene(0, matrix_form=model.cv_matrix_form)
     dec = model._decoder(64, torch.device("cuda"))
     kinv, c2w = camera.target_ray_consts(host(tgt["extrinsics"])[0], host(tgt["intrinsics"])[0], True)
     nf = host(tgt["near_fars"])[0]
@@ -303,8 +301,7 @@ def test_big_frame_opacity_closed_form(big_frame):
     v, S = c["n_views"], c["S"]
     n0, n = (h // 3) * w, 2048
     tgt, ref = model.extract_poses(batch)
-    ref_host, images_cl = model._frame_ctx(ref, batch.images[:, :v])
-    sc = model._scene_mm(0, ref_host, feats, images_cl)
+    sc = model._sources(ref, batch.images[:, :v], feats).scene(0, matrix_form=model.cv_matrix_form)
     dec = model._decoder(S, torch.device("cuda"))
     t_ex, t_in, t_nf = model._tgt_host(tgt)
     kinv, c2w = camera.target_ray_consts(t_ex[0], t_in[0], True)

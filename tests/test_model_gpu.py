@@ -380,10 +380,64 @@ def test_two_same_shaped_batches_do_not_share_launch_context():
         ref_b = fresh(to_batch(gb), mode="test")
     assert torch.equal(out_b.rgb, ref_b.rgb) and torch.equal(out_b.depth, ref_b.depth), same_address
     # and the context is dropped at the top of every forward
-    model._frame = ("stale",)
+    model._src = ("stale",)
     with torch.no_grad():
         again = model(batch_b, mode="test")
     assert torch.equal(again.rgb, ref_b.rgb)
+
+
+def test_poses_of_one_source_set_share_one_context_and_one_operand_image(monkeypatch):
+    """Two poses rendered from one source set: the same ``SourceSet`` serves both, its scene of the batch element and the operand
+    image of the matrix form are built once (not per pose or chunk); a ``forward`` on another batch gets a context of its own."""
+    from matchnerf_amd import hip, matchnerf as M
+    g, cfg, sd, _ = golden_case("c1_default")
+    opt, model = build_model(g["meta"])
+    assert model.cv_matrix_form
+    batch = to_batch(g)
+    built, scenes = [], []
+    operands, build = hip.cost_volume_operands, M.SourceSet.build
+    monkeypatch.setattr(hip, "cost_volume_operands", lambda sc, *a, **k: (built.append(sc), operands(sc, *a, **k))[1])
+    monkeypatch.setattr(M.SourceSet, "build", lambda self, b, feats: (scenes.append(b), build(self, b, feats))[1])
+    monkeypatch.setattr(M, "MAX_RAYS_PER_LAUNCH", 1000)  # several chunks per pose
+    with torch.no_grad():
+        tgt, ref_poses = model.extract_poses(batch)
+        ref_images = batch.images[:, :3]
+        feats = model.get_img_feat(ref_images, cur_n_src_views=3)
+        kw = dict(mode="test", ref_poses=ref_poses, ref_images=ref_images, ref_feats_list=feats)
+        first = model.render(opt, tgt, **kw)
+        ctx = model._src
+        moved = dict(tgt, extrinsics=tgt["extrinsics"].clone())
+        moved["extrinsics"][:, 0, 3] += 0.05
+        second = model.render(opt, moved, **kw)
+        assert model._src is ctx and isinstance(ctx, M.SourceSet)
+        assert len(built) == 1 and scenes == [0]
+        assert built[0] is ctx.scene(0, matrix_form=True) and built[0].feat_op == ctx._ops[0].data_ptr()
+        assert not torch.equal(first.rgb, second.rgb)
+        other = {k: np.array(g[k]) for k in ("images", "extrinsics", "intrinsics", "near_fars")}
+        other["images"] = np.ascontiguousarray(other["images"][..., ::-1, :])
+        model(to_batch(other), mode="test")
+    assert model._src is not ctx and isinstance(model._src, M.SourceSet) and len(built) == 2
+
+
+@pytest.mark.parametrize("ssaa", [1, 2])
+def test_an_empty_ray_range_renders_nothing(ssaa):
+    """``render(ray_range=(first, 0))`` - the band of a rank beyond the target's rows in ``dist.render_frame_sharded`` - returns
+    empty outputs on the device and sizes no workspace, with and without supersampling."""
+    g, cfg, sd, _ = golden_case("c1_default")
+    opt, model = build_model(g["meta"])
+    batch = to_batch(g)
+    w = batch.images.shape[-1]
+    with torch.no_grad():
+        tgt, ref_poses = model.extract_poses(batch)
+        ref_images = batch.images[:, :3]
+        feats = model.get_img_feat(ref_images, cur_n_src_views=3)
+        ws = model._ws
+        out = model.render(opt, tgt, ray_range=(2 * w, 0), mode="test", ref_poses=ref_poses, ref_images=ref_images,
+                           ref_feats_list=feats, ssaa=ssaa)
+    assert model._ws is ws
+    assert sorted(out) == ["depth", "opacity", "rgb"]
+    assert out.rgb.shape == (1, 0, 3) and out.depth.shape == (1, 0, 1) and out.opacity.shape == (1, 0, 1)
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in out.values())
 
 
 def test_encoder_graph_replay_equals_the_eager_pass_and_follows_weight_updates():

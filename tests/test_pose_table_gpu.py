@@ -101,8 +101,7 @@ def test_c_abi_refuses_what_a_table_cannot_do():
         ref_images = batch.images[:, :3]
         feats = model.get_img_feat(ref_images, cur_n_src_views=3)
         tgt, ref_poses = model.extract_poses(batch)
-        ref_host, images_cl = model._frame_ctx(ref_poses, ref_images)
-        sc = model._scene(0, ref_host, feats, images_cl)
+        sc = model._sources(ref_poses, ref_images, feats).scene(0)
         dec = model._decoder(S, ref_images.device)
     assert hip.render_takes_pose_table(sc, dec, S, h * w)
     assert not hip.render_takes_pose_table(sc, dec, S, h * w + 1)  # frames must be whole wavefronts

@@ -61,9 +61,8 @@ def test_fused_bench_frame_is_bit_identical_to_staged_over_50_launches():
     with torch.no_grad():
         feats = model.get_img_feat(batch.images[:, :3], cur_n_src_views=3)
     tgt_pose, ref_poses = model.extract_poses(batch)
-    ref_host, images_cl = model._frame_ctx(ref_poses, batch.images[:, :3])
     tgt_ex, tgt_in, tgt_nf = model._tgt_host(tgt_pose)
-    sc = model._scene(0, ref_host, feats, images_cl)
+    sc = model._sources(ref_poses, batch.images[:, :3], feats).scene(0)
     dec = model._decoder(bench.S, dev)
     kinv, c2w = camera.target_ray_consts(tgt_ex[0], tgt_in[0], True)
     n_rays, chunk = bench.H * bench.W, 65536
@@ -178,9 +177,8 @@ def test_other_kernels_next_to_the_f16_decoder_on_a_second_stream():
     with torch.no_grad():
         solo = [f.clone() for f in model.get_img_feat(batch.images[:, :3], cur_n_src_views=3)]
     tgt_pose, ref_poses = model.extract_poses(batch)
-    ref_host, images_cl = model._frame_ctx(ref_poses, batch.images[:, :3])
     tgt_ex, tgt_in, tgt_nf = model._tgt_host(tgt_pose)
-    sc = model._scene(0, ref_host, solo, images_cl)
+    sc = model._sources(ref_poses, batch.images[:, :3], solo).scene(0)
     dec = model._decoder(bench.S, dev)
     kinv, c2w = camera.target_ray_consts(tgt_ex[0], tgt_in[0], True)
     rays = hip.make_rays(65536, bench.S, bench.H, bench.W, kinv, c2w, tgt_nf[0, 0], tgt_nf[0, 1], ray_begin=0, legacy=True)

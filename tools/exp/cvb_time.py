@@ -15,8 +15,7 @@ with torch.no_grad():
     ref_images = batch.images[:, :3]
     feats = model.get_img_feat(ref_images, cur_n_src_views=3)
     tgt, ref_poses = model.extract_poses(batch)
-    ref_host, images_cl = model._frame_ctx(ref_poses, ref_images)
-    sc = model._scene(0, ref_host, feats, images_cl)
+    sc = model._sources(ref_poses, ref_images, feats).scene(0)
     dec = model._decoder(64, dev)
 ex, it, nf = model._tgt_host(tgt)
 kinv, c2w = camera.target_ray_consts(ex[0], it[0], True)

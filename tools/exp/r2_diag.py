@@ -83,8 +83,7 @@ if which in ("all", "overlap"):
     with torch.no_grad():
         feats = model.get_img_feat(batch.images[:, :3], cur_n_src_views=3)
         tgt, ref = model.extract_poses(batch)
-        ref_host, images_cl = model._frame_ctx(ref, batch.images[:, :3])
-        sc = model._scene(0, ref_host, feats, images_cl)
+        sc = model._sources(ref, batch.images[:, :3], feats).scene(0)
         dec = model._decoder(n_samples, dev)
         t_ex, t_in, t_nf = model._tgt_host(tgt)
         kinv, c2w = camera.target_ray_consts(t_ex[0], t_in[0], True)

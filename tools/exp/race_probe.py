@@ -29,9 +29,8 @@ with torch.no_grad():
     feats = model.get_img_feat(batch.images[:, :3], cur_n_src_views=3)
 tgt_pose, ref_poses = model.extract_poses(batch)
 ref_images = batch.images[:, :3]
-ref_host, images_cl = model._frame_ctx(ref_poses, ref_images)
 tgt_ex, tgt_in, tgt_nf = model._tgt_host(tgt_pose)
-sc = model._scene(0, ref_host, feats, images_cl)
+sc = model._sources(ref_poses, ref_images, feats).scene(0)
 dec = model._decoder(S, dev)
 kinv, c2w = camera.target_ray_consts(tgt_ex[0], tgt_in[0], True)
 H, W = bench.H, bench.W
