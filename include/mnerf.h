@@ -974,6 +974,93 @@ int mnerf_tsdf_mesh(const float* sums, const float* weight, float origin_x, floa
                     int32_t ny, int32_t nz, float min_weight, float* vertices, int64_t vertex_capacity, int32_t* triangles,
                     int64_t triangle_capacity, int64_t* counts, void* workspace, void* stream);
 
+/* MESH FINISHING (MESH EXPORT, continued; added under v12 without a layout change; matchnerf_amd/csrc/mesh_finish.hip): the clean-up
+ * between the mesher's raw zero set and a mesh one can use - adjacency, removal of small connected components, Taubin smoothing,
+ * vertex normals.  The functions take ANY indexed triangle mesh in the mesher's layout:
+ *   vertices       device [V][8] fp32 rows x y z w | r g b 0, 16-byte aligned (MNERF_E_ALIGN otherwise)
+ *   triangles      device [T][3] int32 vertex rows, every index in [0, V).  (No kernel reads or writes outside a buffer for an index
+ *                  out of that range: such a corner joins no row, such a triangle joins no component and contributes no normal,
+ *                  its vertices are boundary vertices, and the compaction drops it.)
+ *   0 <= V < 2^31 and 0 <= 3 T < 2^31 (MNERF_E_RANGE otherwise).  V == 0 is MNERF_OK and touches no buffer; T == 0 is the mesh of V
+ *   unreferenced vertices (empty rows, no triangle out), and the triangle pointers may then be NULL.
+ *   workspace      device, 16-byte aligned, mnerf_mesh_finish_workspace_bytes(V, T) bytes, scratch only; one size serves all calls
+ * Enqueue-only on `stream`; every argument check precedes any HIP call (MNERF_E_RANGE, then _NULL, then _ALIGN; int32 buffers are
+ * 4-byte aligned).  DETERMINISM: two runs give the same bytes in every output.  No floating-point atomic is used; every float sum
+ * runs over a vertex's corners in ascending order inside one thread.  Integer atomics appear only where the final memory contents
+ * do not depend on their order: counts (add), the largest component (max), the union-find hooks, and the row fill that is sorted
+ * afterwards.  Every operation is rounded on its own, with one FMA where the text says fma().
+ *
+ * mnerf_mesh_adjacency - the vertex -> corner table in CSR form.  Corner c = 3 t + k is vertex k of triangle t; next(c) and prev(c)
+ * are vertices (k + 1) mod 3 and (k + 2) mod 3 of the same triangle.
+ *   offsets        device int32 [V + 1], corners: device int32 [3 T].  corners[offsets[v] .. offsets[v + 1]) lists, ASCENDING, the
+ *                  corners c with triangles[c] == v.
+ *   vertex_class   device uint8 [V]: 1 INTERIOR - the row is not empty and every neighbour (every next and prev vertex of the row's
+ *                  corners) is the next vertex of exactly one corner of the row and the prev vertex of exactly one; 0 BOUNDARY -
+ *                  everything else: open borders, non-manifold fans, unreferenced vertices.
+ * Eight launches: the corner counts (integer atomic add), the mesher's two-level scan over the vertices, the rows filled through an
+ * integer cursor, one thread per vertex sorting its own row in place (insertion sort, any length) and classifying it.
+ * MNERF_E_NULL: offsets, vertex_class or workspace missing; triangles or corners missing with T > 0.
+ *
+ * mnerf_mesh_components - connected components (two vertices are connected when a triangle contains both; an unreferenced vertex is
+ * a component of its own) by a lock-free union-find over the edges (v0 v1) and (v0 v2) of every triangle: the larger root is hooked
+ * under the smaller with a compare-and-swap, a second launch flattens.  No host loop and no copy.
+ *   labels         device int32 [V]: the smallest vertex row of the vertex's component
+ *   keep           device uint8 [V]: 1 iff the component's triangle count n (triangles counted at the label of their first vertex)
+ *                  satisfies n >= min_triangles AND (double) n >= min_fraction * (double) largest, largest = the largest count
+ * MNERF_E_RANGE also: min_triangles < 0, min_fraction not finite or outside [0, 1].  MNERF_E_NULL: labels, keep or workspace missing;
+ * triangles missing with T > 0.
+ *
+ * mnerf_mesh_compact - the mesh of the kept vertices.  A triangle is kept iff its FIRST vertex is (all three share a component).
+ *   vertices_out   device [vertex_capacity] rows, 16-byte aligned: the kept rows, bit for bit, in their original order
+ *   triangles_out  device [triangle_capacity][3] int32: the kept triangles in their original order, indices re-numbered (-1 for
+ *                  a vertex that is not kept - none where keep is constant on every component, as mnerf_mesh_components writes it)
+ *   counts         device int64 [2], 8-byte aligned: kept vertices, kept triangles.  Rows at or beyond a capacity are not written,
+ *                  the counts are the totals either way and the call is MNERF_OK (as mnerf_tsdf_mesh)
+ * The mesher's count / scan / scatter, once over the vertices and once over the triangles; no atomics.  The outputs must not
+ * overlap the inputs.  MNERF_E_RANGE also: a negative capacity.  MNERF_E_NULL: vertices, keep, counts or workspace missing; triangles
+ * missing with T > 0; an output missing with its capacity > 0 (triangles_out only with T > 0).
+ *
+ * mnerf_mesh_smooth - `iterations` rounds of Taubin smoothing; a round is two Jacobi steps, p <- p + lambda L(p), then
+ * p <- p + mu L(p), each one launch of one thread per vertex that reads all positions of the previous step.  For an INTERIOR vertex
+ * with the row c_1 < ... < c_n:   s = 0;  s = s + (p[next(c_i)] + p[prev(c_i)]) for i = 1..n, per component;  m = s / (float)(2 n);
+ * p' = fma(factor, m - p, p).  That is the uniform umbrella operator: every neighbour of an interior vertex occurs twice.  BOUNDARY
+ * vertices do not move (an open border would creep inwards).  Only x y z change: w | r g b 0 are copied bit for bit.
+ *   offsets, corners, vertex_class    as mnerf_mesh_adjacency wrote them for THIS mesh
+ *   vertices_out   may be vertices_in: the steps ping-pong through the workspace.  iterations == 0: the bytes of vertices_in.
+ *                  mu == 0 is plain Laplacian smoothing (the second step copies).
+ * MNERF_E_RANGE also: iterations < 0, lambda not in (0, 1], mu not finite or > 0.  MNERF_E_NULL: vertices_in, vertices_out, offsets,
+ * vertex_class or workspace missing; triangles or corners missing with T > 0.
+ *
+ * mnerf_mesh_normals - area-weighted vertex normals, one thread per vertex.
+ *   normals        device [V][4] fp32, 16-byte aligned: nx ny nz a.  For the row's corners in ascending order, with (p0, p1, p2) the
+ *                  corner's triangle in its stored winding:  u = p1 - p0, v = p2 - p0;  c = u x v with every component
+ *                  fma(u_a, v_b, -(u_b v_a)) (x: a b = y z, y: z x, z: x y);  S = S + c;  A = A + |c|,
+ *                  |c| = sqrt(fma(c_z, c_z, fma(c_y, c_y, c_x c_x))).  n = S / |S| per component, or 0 0 0 where |S| is not > 0 (an
+ *                  unreferenced vertex, zero-area triangles only) - never a NaN for finite input.  a = A / 6: one third of the
+ *                  incident area.  On the mesher's output n points towards the observed free space.
+ * MNERF_E_NULL: vertices, offsets or normals missing; triangles or corners missing with T > 0.
+ *
+ * mnerf_mesh_finish_workspace_bytes: host only; -1 beyond the bounds above, 0 for V == 0.  With Bv = ceil(V / 256),
+ * Tv = ceil(Bv / 1024) and Bt, Tt alike from T, the workspace is 16 bytes (int64 [2]: the scans' totals / the largest component)
+ * followed by the larger of
+ *   int32 [V] (adjacency: the fill cursor; components: the triangle counts; compact: the new vertex rows) | int32 [Bv] | [Tv]: the
+ *   vertex scan's workgroup and tile counts | int32 [Bt] | [Tt]: the same for the triangle scan        4 (V + Bv + Tv + Bt + Tt) bytes
+ *   fp32 [V][8] (smooth: the intermediate positions)                                                     32 V bytes
+ * rounded up to 16. */
+int64_t mnerf_mesh_finish_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+int mnerf_mesh_adjacency(const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, int32_t* offsets, int32_t* corners,
+                         uint8_t* vertex_class, void* workspace, void* stream);
+int mnerf_mesh_components(const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, int64_t min_triangles, double min_fraction,
+                          int32_t* labels, uint8_t* keep, void* workspace, void* stream);
+int mnerf_mesh_compact(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, const uint8_t* keep,
+                       float* vertices_out, int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity, int64_t* counts,
+                       void* workspace, void* stream);
+int mnerf_mesh_smooth(const float* vertices_in, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const int32_t* offsets,
+                      const int32_t* corners, const uint8_t* vertex_class, int32_t iterations, float lambda, float mu,
+                      float* vertices_out, void* workspace, void* stream);
+int mnerf_mesh_normals(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const int32_t* offsets,
+                       const int32_t* corners, float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

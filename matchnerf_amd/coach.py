@@ -756,7 +756,10 @@ class Coach:
         nerf.export_geometry, else 'sources'); thresholds from nerf.fuse_px_tol / fuse_rel_tol / fuse_min_opacity / fuse_min_views
         where given.  With the option nerf.export_mesh also <stem>_mesh.ply next to each cloud: the triangle mesh of the same maps
         (``fusion.mesh``: TSDF fusion + marching tetrahedra; float xyz + uchar rgb vertices and a face list), with nerf.mesh_resolution /
-        mesh_voxel / mesh_trunc / mesh_min_weight where given.  One process (not sharded).  Returns {set: [path of every .ply]}."""
+        mesh_voxel / mesh_trunc / mesh_min_weight where given, cleaned up by nerf.mesh_min_component / mesh_min_component_fraction
+        (small connected components dropped) and nerf.mesh_smooth (rounds of Taubin smoothing) where given; with nerf.mesh_normals
+        the vertices also carry float nx ny nz (``fusion.vertex_normals``).  One process (not sharded).
+        Returns {set: [path of every .ply]}."""
         from PIL import Image
 
         from . import fusion
@@ -771,8 +774,12 @@ class Coach:
         mesh_args = None
         if getattr(self.opts.nerf, "export_mesh", None):
             mesh_args = {arg: getattr(self.opts.nerf, name) for arg, name in (("resolution", "mesh_resolution"), ("voxel", "mesh_voxel"),
-                                                                              ("trunc", "mesh_trunc"), ("min_weight", "mesh_min_weight"))
+                                                                              ("trunc", "mesh_trunc"), ("min_weight", "mesh_min_weight"),
+                                                                              ("min_component", "mesh_min_component"),
+                                                                              ("min_component_fraction", "mesh_min_component_fraction"),
+                                                                              ("smooth", "mesh_smooth"))
                          if getattr(self.opts.nerf, name, None) is not None}
+        mesh_normals = bool(getattr(self.opts.nerf, "mesh_normals", None))
         out_root = os.path.join(self.opts.output_path, "geometry")
         written = {}
         for loader in self.test_loaders:
@@ -795,7 +802,7 @@ class Coach:
                         vertices, faces = fusion.mesh(maps.views[bi], maps.depth[bi], maps.opacity[bi], maps.rgb[bi], maps.hw,
                                                       bool(self.opts.nerf.legacy_coord), **mesh_args, **fuse_args)
                         path = os.path.join(out_dir, f"{stem}_mesh.ply")
-                        fusion.write_ply(path, vertices, faces)
+                        fusion.write_ply(path, vertices, faces, fusion.vertex_normals(vertices, faces) if mesh_normals else None)
                         written[name].append(path)
                         self.say(f"[coach] {name}: {vertices.shape[0]} vertices, {faces.shape[0]} triangles -> {path}")
                     for k in range(panels.shape[1] if panels is not None else 0):

@@ -10,6 +10,10 @@ Everything else stays on the device.  There is no CPU fallback.
 ``mesh`` turns the same maps into a surface (include/mnerf.h "MESH EXPORT", matchnerf_amd/csrc/mesh.hip): the fused depths and their
 counts are integrated into a truncated-signed-distance volume over the cloud's box, and marching tetrahedra extract a welded,
 indexed, coloured triangle mesh whose vertex and face order is defined - two runs give the same bytes.
+
+``finish`` and ``vertex_normals`` clean such a mesh - or any indexed mesh in the same layout - up on the device (include/mnerf.h "MESH
+FINISHING", matchnerf_amd/csrc/mesh_finish.hip): small connected components dropped, Taubin smoothing of the positions,
+area-weighted vertex normals; ``write_ply`` takes the normals.
 """
 import numpy as np
 import torch
@@ -108,7 +112,8 @@ def _auto_bounds(views, fused, counts, rgbs, hw, legacy, min_consistent):
 
 
 def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
-         consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None):
+         consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None, min_component=0,
+         min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
     """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
     fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
     (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
@@ -120,7 +125,9 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
       min_weight    views that must have updated a lattice point for it to take part; default min(2, K - 1), at least 1
     Views beyond 16 are integrated in groups of 16, in order.  Device->host copies: the box (with ``bounds=None`` only) before the
     mesh launch and the two counts after it.  The vertex and face buffers are sized from a first guess (a few rows per voxel of the
-    grid's three faces); when the counts exceed it the mesher is RUN AGAIN ONCE with exact sizes - no further copy."""
+    grid's three faces); when the counts exceed it the mesher is RUN AGAIN ONCE with exact sizes - no further copy.
+      min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu    ``finish`` applied to the result (one more copy
+                    when a component threshold is set)"""
     h, w = int(hw[0]), int(hw[1])
     n, k_views = h * w, len(views)
     if k_views < 1 or (consistency and k_views < 2):
@@ -195,22 +202,68 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
         vertices = torch.empty(n_vertices, hip.VERTEX_FLOATS, device=dev)
         faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
         hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, counts=totals, workspace=workspace)
-    return vertices[:n_vertices], faces[:n_faces]
+    return finish(vertices[:n_vertices], faces[:n_faces], min_component=min_component, min_component_fraction=min_component_fraction,
+                  smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
 
 
-def write_ply(path, points, faces=None):
+def finish(vertices, faces, *, min_component=0, min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+    """Clean an indexed mesh up on the device (include/mnerf.h "MESH FINISHING") -> (vertices [V', 8], faces [T', 3]):
+      min_component, min_component_fraction   drop every connected component with fewer than ``min_component`` triangles or fewer
+                    than ``min_component_fraction`` of the largest component's (the floaters next to the surface); the kept rows
+                    and faces keep their order.  The two counts of the result cost ONE device->host copy
+      smooth        rounds of Taubin smoothing (``smooth_lambda``, ``smooth_mu``) of the positions over the adjacency OF THE RESULT;
+                    colours and weights stay, boundary vertices do not move
+    The same bytes on every run.  With nothing asked for the inputs are returned and nothing is launched."""
+    filtering = int(min_component) > 0 or float(min_component_fraction) > 0.0
+    if not filtering and int(smooth) == 0:
+        return vertices, faces
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    n_vertices, n_faces = vertices.shape[0], faces.shape[0]
+    workspace = torch.empty(max(hip.mesh_finish_workspace_bytes(n_vertices, n_faces), 16), dtype=torch.uint8, device=vertices.device)
+    if filtering:
+        _, keep = hip.mesh_components(faces, n_vertices, min_component, min_component_fraction, workspace=workspace)
+        vertices, faces, totals = hip.mesh_compact(vertices, faces, keep, workspace=workspace)
+        n_vertices, n_faces = (int(c) for c in totals.cpu())  # the one copy
+        vertices, faces = vertices[:n_vertices], faces[:n_faces]
+    if int(smooth) > 0 and n_vertices:
+        adjacency = hip.mesh_adjacency(faces, n_vertices, workspace=workspace)
+        vertices = hip.mesh_smooth(vertices, faces, adjacency, int(smooth), smooth_lambda, smooth_mu, workspace=workspace)
+    return vertices, faces
+
+
+def vertex_normals(vertices, faces):
+    """-> [V, 4] float32 rows ``nx ny nz a`` on the device: the area-weighted unit normal of every vertex (0 0 0 where the sum
+    vanishes; on ``mesh``'s output it points towards the observed free space) and a third of its incident area."""
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    adjacency = hip.mesh_adjacency(faces, vertices.shape[0])
+    return hip.mesh_normals(vertices, faces, adjacency)
+
+
+def write_ply(path, points, faces=None, normals=None):
     """points [M, >= 7] (x y z . r g b ..., colours in [0, 1]; a tensor or an array) -> a binary little-endian PLY of float xyz and
     uchar rgb vertices; with ``faces`` [T, 3] (integer vertex rows) also ``element face`` with ``property list uchar int
-    vertex_indices``.  Without faces the file is the point cloud's, byte for byte."""
+    vertex_indices``.  Without faces the file is the point cloud's, byte for byte.  With ``normals`` [M, >= 3] the vertex element is
+    x y z nx ny nz red green blue (float normals); without them the file is what it was before normals existed."""
     pts = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
     pts = pts.reshape(-1, pts.shape[-1]) if pts.size else np.zeros((0, 8), np.float32)
-    vertex = np.zeros(len(pts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)
+        nrm = nrm.reshape(-1, nrm.shape[-1]) if nrm.size else np.zeros((0, 4), np.float32)
+        if len(nrm) != len(pts) or nrm.shape[1] < 3:
+            raise ValueError(f"write_ply: normals {nrm.shape} do not match the {len(pts)} vertices")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vertex = np.zeros(len(pts), dtype=fields + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     for i, name in enumerate(("x", "y", "z")):
         vertex[name] = pts[:, i]
     for i, name in enumerate(("red", "green", "blue")):
         vertex[name] = np.rint(np.clip(np.nan_to_num(pts[:, 4 + i]), 0.0, 1.0) * 255.0).astype(np.uint8)
-    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" \
-             "property uchar red\nproperty uchar green\nproperty uchar blue\n" % len(pts)
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(pts)
+    if normals is not None:
+        for i, name in enumerate(("nx", "ny", "nz")):
+            vertex[name] = nrm[:, i]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
+    header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     body = vertex.tobytes()
     if faces is not None:
         tri = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)

@@ -233,6 +233,12 @@ SIGNATURES = {
     "mnerf_tsdf_integrate": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3 + [_vp] * 3),
     "mnerf_tsdf_mesh_workspace_bytes": (_i64, [_i32] * 3),
     "mnerf_tsdf_mesh": (_int, [_vp] * 2 + [_f32] * 4 + [_i32] * 3 + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
+    "mnerf_mesh_finish_workspace_bytes": (_i64, [_i64] * 2),
+    "mnerf_mesh_adjacency": (_int, [_P(_i32), _i64, _i64, _P(_i32), _P(_i32)] + [_vp] * 3),
+    "mnerf_mesh_components": (_int, [_P(_i32), _i64, _i64, _i64, C.c_double, _P(_i32)] + [_vp] * 3),
+    "mnerf_mesh_compact": (_int, [_vp, _P(_i32), _i64, _i64, _vp, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
+    "mnerf_mesh_smooth": (_int, [_vp, _i64, _P(_i32), _i64, _P(_i32), _P(_i32), _vp, _i32, _f32, _f32] + [_vp] * 3),
+    "mnerf_mesh_normals": (_int, [_vp, _i64, _P(_i32), _i64, _P(_i32), _P(_i32), _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -1745,3 +1751,148 @@ def tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, triangles
         check(lib.mnerf_tsdf_mesh(_ptr(sums), _ptr(weight), *grid, float(min_weight), _ptr(vertices), vertices.numel() // VERTEX_FLOATS,
                                   _ptr_i32(triangles), triangles.numel() // 3, _ptr(counts), _ptr(workspace), st), "mnerf_tsdf_mesh")
     return vertices, triangles, counts
+
+
+# ----------------------------------------------------------------------- mesh finishing (matchnerf_amd/csrc/mesh_finish.hip)
+
+NORMAL_FLOATS = 4  # floats of one row of a normal buffer: nx ny nz a
+VERTEX_BOUNDARY, VERTEX_INTERIOR = 0, 1  # the class bytes of mesh_adjacency
+
+
+def mesh_finish_workspace_bytes(n_vertices, n_triangles):
+    return int(load().mnerf_mesh_finish_workspace_bytes(int(n_vertices), int(n_triangles)))
+
+
+def _mesh_args(what, vertices, triangles, n_vertices=None):
+    """the checks of ``tsdf_mesh`` on an indexed mesh -> (device, V, T); ``vertices`` None: a function that takes the faces alone"""
+    import torch
+    if triangles.dtype != torch.int32 or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() % 3:
+        raise MnerfError(f"{what}: triangles must be a contiguous int32 [T, 3] CUDA tensor, got {triangles.dtype} "
+                         f"{tuple(triangles.shape)} on {triangles.device}")
+    dev = triangles.device
+    if vertices is not None:
+        _f32c(vertices, "vertices")
+        if vertices.device != dev or vertices.numel() % VERTEX_FLOATS:
+            raise MnerfError(f"{what}: vertices {tuple(vertices.shape)} on {vertices.device} is no [V, {VERTEX_FLOATS}] buffer on {dev}")
+        n_vertices = vertices.numel() // VERTEX_FLOATS
+    n_vertices = int(n_vertices)
+    if mesh_finish_workspace_bytes(n_vertices, triangles.numel() // 3) < 0:
+        raise MnerfError(f"{what}: {n_vertices} vertices / {triangles.numel() // 3} triangles are out of range")
+    return dev, n_vertices, triangles.numel() // 3
+
+
+def _mesh_buffer(what, name, t, dtype, numel, dev):
+    """an output or table the caller passes, or a fresh one"""
+    import torch
+    if t is None:
+        return torch.empty(numel, dtype=dtype, device=dev)
+    if t.dtype != dtype or t.numel() != numel or t.device != dev or not t.is_contiguous():
+        raise MnerfError(f"{what}: {name} must be a contiguous {dtype} tensor of {numel} elements on {dev}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _mesh_workspace(what, workspace, n_vertices, n_triangles, dev):
+    import torch
+    need = mesh_finish_workspace_bytes(n_vertices, n_triangles)
+    if workspace is None:
+        return torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
+        raise MnerfError(f"{what}: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
+                         f"{need} needed on {dev}")
+    return workspace
+
+
+def mesh_adjacency(triangles, n_vertices, out=None, workspace=None, stream=None):
+    """The vertex -> corner table of an indexed mesh (mnerf_mesh_adjacency): ``triangles`` [T, 3] int32 CUDA over ``n_vertices``
+    vertices -> (offsets int32 [V + 1], corners int32 [3 T], vertex_class uint8 [V]): row v = corners[offsets[v]:offsets[v + 1]]
+    lists ascending the corners 3 t + k with triangles[t, k] == v; the class is VERTEX_INTERIOR or VERTEX_BOUNDARY.  ``out``: the
+    three tensors to write into.  Enqueue only."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_adjacency", None, triangles, n_vertices)
+    workspace = _mesh_workspace("mesh_adjacency", workspace, nv, nt, dev)
+    out = (None, None, None) if out is None else out
+    offsets = _mesh_buffer("mesh_adjacency", "offsets", out[0], torch.int32, nv + 1, dev)
+    corners = _mesh_buffer("mesh_adjacency", "corners", out[1], torch.int32, 3 * nt, dev)
+    vclass = _mesh_buffer("mesh_adjacency", "vertex_class", out[2], torch.uint8, nv, dev)
+    if nv == 0:  # the library touches no buffer then
+        offsets.zero_()
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_adjacency(_ptr_i32(triangles), nv, nt, _ptr_i32(offsets), _ptr_i32(corners), _ptr(vclass), _ptr(workspace), st),
+              "mnerf_mesh_adjacency")
+    return offsets, corners, vclass
+
+
+def mesh_components(triangles, n_vertices, min_triangles=0, min_fraction=0.0, out=None, workspace=None, stream=None):
+    """Connected components of an indexed mesh (mnerf_mesh_components) -> (labels int32 [V]: the smallest vertex row of the vertex's
+    component, keep uint8 [V]: 1 iff the component has at least ``min_triangles`` triangles and at least ``min_fraction`` of the
+    largest component's).  ``out``: the two tensors to write into.  Enqueue only, no copy."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_components", None, triangles, n_vertices)
+    workspace = _mesh_workspace("mesh_components", workspace, nv, nt, dev)
+    out = (None, None) if out is None else out
+    labels = _mesh_buffer("mesh_components", "labels", out[0], torch.int32, nv, dev)
+    keep = _mesh_buffer("mesh_components", "keep", out[1], torch.uint8, nv, dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_components(_ptr_i32(triangles), nv, nt, int(min_triangles), float(min_fraction), _ptr_i32(labels), _ptr(keep),
+                                        _ptr(workspace), st), "mnerf_mesh_components")
+    return labels, keep
+
+
+def mesh_compact(vertices, triangles, keep, vertices_out=None, triangles_out=None, counts=None, workspace=None, stream=None):
+    """The mesh of the vertices whose ``keep`` byte is set (mnerf_mesh_compact): kept rows bit for bit and in order, a triangle kept
+    iff its first vertex is, indices re-numbered.  ``vertices_out`` [capacity, 8] / ``triangles_out`` [capacity, 3] default to the
+    input's sizes, ``counts`` is a 2-element int64 tensor.  Enqueue only: -> (vertices_out, triangles_out, counts); rows at or beyond
+    a capacity are not written, the counts are the totals either way."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_compact", vertices, triangles)
+    keep = _mesh_buffer("mesh_compact", "keep", keep, torch.uint8, nv, dev)
+    if vertices_out is None:
+        vertices_out = torch.empty(nv, VERTEX_FLOATS, device=dev)
+    if triangles_out is None:
+        triangles_out = torch.empty(nt, 3, dtype=torch.int32, device=dev)
+    _mesh_args("mesh_compact", vertices_out, triangles_out)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev) if counts is None else _mesh_buffer("mesh_compact", "counts", counts,
+                                                                                              torch.int64, 2, dev)
+    workspace = _mesh_workspace("mesh_compact", workspace, nv, nt, dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_compact(_ptr(vertices), _ptr_i32(triangles), nv, nt, _ptr(keep), _ptr(vertices_out),
+                                     vertices_out.numel() // VERTEX_FLOATS, _ptr_i32(triangles_out), triangles_out.numel() // 3,
+                                     _ptr(counts), _ptr(workspace), st), "mnerf_mesh_compact")
+    return vertices_out, triangles_out, counts
+
+
+def mesh_smooth(vertices, triangles, adjacency, iterations, lam=0.5, mu=-0.53, out=None, workspace=None, stream=None):
+    """``iterations`` rounds of Taubin smoothing of the positions (mnerf_mesh_smooth: p + lam L(p), then p + mu L(p), L the uniform
+    umbrella on interior vertices; boundary vertices and the fields w | r g b 0 do not change).  ``adjacency`` = the triple of
+    ``mesh_adjacency`` for this mesh.  ``out`` may be ``vertices`` (in place); default a new tensor.  Enqueue only: -> out."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_smooth", vertices, triangles)
+    offsets = _mesh_buffer("mesh_smooth", "offsets", adjacency[0], torch.int32, nv + 1, dev)
+    corners = _mesh_buffer("mesh_smooth", "corners", adjacency[1], torch.int32, 3 * nt, dev)
+    vclass = _mesh_buffer("mesh_smooth", "vertex_class", adjacency[2], torch.uint8, nv, dev)
+    out = _mesh_buffer("mesh_smooth", "out", out, torch.float32, nv * VERTEX_FLOATS, dev).view(nv, VERTEX_FLOATS)
+    workspace = _mesh_workspace("mesh_smooth", workspace, nv, nt, dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_smooth(_ptr(vertices), nv, _ptr_i32(triangles), nt, _ptr_i32(offsets), _ptr_i32(corners), _ptr(vclass),
+                                    int(iterations), float(lam), float(mu), _ptr(out), _ptr(workspace), st), "mnerf_mesh_smooth")
+    return out
+
+
+def mesh_normals(vertices, triangles, adjacency, out=None, stream=None):
+    """Area-weighted vertex normals (mnerf_mesh_normals) -> [V, 4] float32 rows ``nx ny nz a``: the normalised corner sum of the
+    triangles' cross products (0 0 0 where it vanishes) and a third of the incident area.  ``adjacency`` as for ``mesh_smooth``."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_normals", vertices, triangles)
+    offsets = _mesh_buffer("mesh_normals", "offsets", adjacency[0], torch.int32, nv + 1, dev)
+    corners = _mesh_buffer("mesh_normals", "corners", adjacency[1], torch.int32, 3 * nt, dev)
+    out = _mesh_buffer("mesh_normals", "out", out, torch.float32, nv * NORMAL_FLOATS, dev).view(nv, NORMAL_FLOATS)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_normals(_ptr(vertices), nv, _ptr_i32(triangles), nt, _ptr_i32(offsets), _ptr_i32(corners), _ptr(out), st),
+              "mnerf_mesh_normals")
+    return out

@@ -29,7 +29,9 @@ path, kept where the other poses confirm them), with ``--vis_depth`` also the co
 ``--nerf.fuse_min_views=<confirming views>`` (min(2, K - 1)).  With ``--nerf.export_mesh`` also a coloured triangle mesh of the same
 maps, ``<stem>_mesh.ply`` (TSDF fusion, marching tetrahedra): ``--nerf.mesh_resolution=<voxels along the longest side>`` (256),
 ``--nerf.mesh_voxel=<world units>`` (instead of the resolution), ``--nerf.mesh_trunc=<world units>`` (4 voxels),
-``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)).
+``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)).  The mesh is cleaned up by
+``--nerf.mesh_min_component=<triangles>`` / ``--nerf.mesh_min_component_fraction=<of the largest component>`` (smaller connected
+components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, and ``--nerf.mesh_normals`` adds ``nx ny nz`` per vertex.
 
     python test.py --yaml=demo_own --nerf.export_geometry=sources
     python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192"""
