@@ -17,11 +17,27 @@
 // With G_j = dL/dw_j = <g_rgb, c_j> + g_depth d_j + g_opacity - bg sum(g_rgb):
 //   dL/dc_j  = w_j g_rgb
 //   dL/dsd_j = G_j T_j (1 - a_j) - sum_{k>j} G_k w_k          (w_k depends on sd_j through T_k only)
+// Two passes over the ray's 64-sample blocks:
+//   front to back: T_j from the exclusive prefix sum of sd, the forward kernel's own scan (composite.hip) with a scalar carry;
+//     g_rgb_s is written, and T_j of every block but the last is parked in g_sigma[j] (the lane that parks it reads it back);
+//   back to front: the suffix sum_{k>j} G_k w_k, summed directly: a reverse scan inside the wave (__shfl_down) of the terms
+//     shifted up one lane, plus a scalar carry from the blocks behind.  The suffix is never formed as "total - prefix" (two
+//     float32 sums of the whole ray that differ by rounding where the true suffix is 0: at the last sample, where k_j = 1e10 |ray|
+//     multiplies the residue, and behind an opaque surface), nor as "inclusive - self": a run of exact zeros sums to an exact zero.
 __device__ __forceinline__ float wave_incl_scan_up(float v, int lane) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
     float t = __shfl_up(v, off, 64);
     if (lane >= off) v += t;
+  }
+  return v;
+}
+
+__device__ __forceinline__ float wave_incl_scan_down(float v, int lane) {  // v_lane + v_{lane+1} + .. + v_63
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    float t = __shfl_down(v, off, 64);
+    if (lane + off < 64) v += t;
   }
   return v;
 }
@@ -41,60 +57,51 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(
     const float gd = g_depth ? g_depth[r] : 0.0f;
     const float go = (g_opacity ? g_opacity[r] : 0.0f) - (setbg ? (gr + gg + gb) : 0.0f);
     const int n_blk = (S + 63) / 64;
-    // pass 1 (front to back): total of G_k w_k over the ray, needed for the suffix sums
-    float carry = 0.0f, total = 0.0f;
+    // pass 1 (front to back): T_j; the colour gradients
+    float carry = 0.0f, T = 1.0f;
     for (int blk = 0; blk < n_blk; ++blk) {
       const int j = blk * 64 + lane;
       const bool ok = j < S;
-      float sd = 0.0f, G = 0.0f;
+      float sd = 0.0f;
       if (ok) {
         const float d = depth_s[base + j];
         float k = 1.0f;
         if (!wo_interval) k = ((j + 1 < S) ? (depth_s[base + j + 1] - d) : 1e10f) * rl;
         sd = sigma[base + j] * k;
-        G = gr * rgb_s[(base + j) * 3 + 0] + gg * rgb_s[(base + j) * 3 + 1] + gb * rgb_s[(base + j) * 3 + 2] + gd * d + go;
       }
       float prev = __shfl_up(sd, 1, 64);
       if (lane == 0) prev = 0.0f;
       const float excl = carry + wave_incl_scan_up(prev, lane);
-      const float w = ok ? expf(-excl) * (1.0f - expf(-sd)) : 0.0f;
-      float gw = G * w;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) gw += __shfl_xor(gw, off, 64);
-      total += gw;
-      carry = __shfl(excl + sd, 63, 64);
-    }
-    // pass 2: gradients; suffix_j = total - prefix_inclusive_j
-    carry = 0.0f;
-    float gw_before = 0.0f;
-    for (int blk = 0; blk < n_blk; ++blk) {
-      const int j = blk * 64 + lane;
-      const bool ok = j < S;
-      float sd = 0.0f, G = 0.0f, k = 1.0f, cr = 0.f, cg = 0.f, cb = 0.f;
+      T = expf(-excl);
       if (ok) {
-        const float d = depth_s[base + j];
-        if (!wo_interval) k = ((j + 1 < S) ? (depth_s[base + j + 1] - d) : 1e10f) * rl;
-        sd = sigma[base + j] * k;
-        cr = rgb_s[(base + j) * 3 + 0];
-        cg = rgb_s[(base + j) * 3 + 1];
-        cb = rgb_s[(base + j) * 3 + 2];
-        G = gr * cr + gg * cg + gb * cb + gd * d + go;
-      }
-      float prev = __shfl_up(sd, 1, 64);
-      if (lane == 0) prev = 0.0f;
-      const float excl = carry + wave_incl_scan_up(prev, lane);
-      const float T = expf(-excl), e = expf(-sd);
-      const float w = ok ? T * (1.0f - e) : 0.0f;
-      const float gw = G * w;
-      const float incl = gw_before + wave_incl_scan_up(gw, lane);   // sum_{k<=j} G_k w_k
-      if (ok) {
+        const float w = T * (1.0f - expf(-sd));
         g_rgb_s[(base + j) * 3 + 0] = w * gr;
         g_rgb_s[(base + j) * 3 + 1] = w * gg;
         g_rgb_s[(base + j) * 3 + 2] = w * gb;
-        g_sigma[base + j] = (G * T * e - (total - incl)) * k;
+        if (blk + 1 < n_blk) g_sigma[base + j] = T;  // the last block's T stays in the register
       }
-      gw_before = __shfl(incl, 63, 64);
       carry = __shfl(excl + sd, 63, 64);
+    }
+    // pass 2 (back to front): suffix_j = sum_{k>j} G_k w_k; the density gradients
+    float behind = 0.0f;  // sum of G_k w_k over the blocks behind this one
+    for (int blk = n_blk - 1; blk >= 0; --blk) {
+      const int j = blk * 64 + lane;
+      const bool ok = j < S;
+      float k = 1.0f, local = 0.0f, gw = 0.0f;
+      if (ok) {
+        const float d = depth_s[base + j];
+        if (!wo_interval) k = ((j + 1 < S) ? (depth_s[base + j + 1] - d) : 1e10f) * rl;
+        const float e = expf(-sigma[base + j] * k);
+        if (blk + 1 < n_blk) T = g_sigma[base + j];
+        const float G = gr * rgb_s[(base + j) * 3 + 0] + gg * rgb_s[(base + j) * 3 + 1] + gb * rgb_s[(base + j) * 3 + 2] + gd * d + go;
+        local = G * T * e;
+        gw = G * (T * (1.0f - e));
+      }
+      float next = __shfl_down(gw, 1, 64);
+      if (lane == 63) next = 0.0f;
+      const float suffix = behind + wave_incl_scan_down(next, lane);
+      if (ok) g_sigma[base + j] = (local - suffix) * k;
+      behind = __shfl(suffix + gw, 0, 64);
     }
   }
 }
