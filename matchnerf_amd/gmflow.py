@@ -32,6 +32,8 @@ import torch.nn.functional as F
 from . import hip  # noqa: F401  (the encoder has no path without the HIP library)
 from .autograd import window_attention
 from .camera import pair_list
+from .wstream import (  # noqa: F401  (re-exported: the encoder's numpy packers and layout constants)
+    EB_CHUNK, EB_SEG_FLOATS, K_ROW_ORDER, pack_conv, pack_conv_blocks, pack_conv_stem, pack_encoder_block, pack_key, pack_qkv)
 
 
 def _fused_norm(x):
@@ -59,7 +61,7 @@ def _train_packs(owner, convs, device):
             c._mnerf_train_pack = None
         return
     from . import packing
-    key = (tuple((int(c.weight._version), int(c.weight.data_ptr())) for c in convs), str(device))
+    key = pack_key([c.weight for c in convs], str(device))
     if getattr(owner, "_train_pack_key", None) != key:
         pk = getattr(owner, "_train_packer", None)
         if pk is None or pk.device != torch.device(device) or len(pk.convs) != len(convs) or any(a is not b for a, b in zip(pk.convs, convs)):
@@ -84,64 +86,11 @@ def _conv_out(conv, x):
     return conv(x).contiguous()
 
 
-def pack_conv(weight):
-    """Conv2d weight [c_out, c_in, k, k] -> (wstream float32 words, ew) for ``mnerf_conv2d`` (csrc/conv.hip): the
-    implicit-GEMM matrix W[out, tap * c_in + c] (tap = ky * k + kx) as split-fp16 A-operand fragments, K16-step s =
-    16 consecutive columns, unit (s, 32-row block) = [hi | lo] x 64 lanes x 8 (the decoder's unit layout,
-    cond_nerf._fragments_h)."""
-    import numpy as np
-    from . import cond_nerf as CN
-    w = (weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)).astype(np.float32)
-    c_out, c_in, kh, kw = w.shape
-    assert kh == kw and c_in % 32 == 0 and c_out % 32 == 0, w.shape
-    mat = np.ascontiguousarray(w.transpose(0, 2, 3, 1).reshape(c_out, kh * kw * c_in))
-    ew = CN.f16_weight_exponent(mat)
-    cols = np.arange(mat.shape[1]).reshape(-1, 2, 8)
-    halfs = CN._fragments_h(mat, cols, c_out // 32, ew)            # [steps, blocks, 2, 64, 8] fp16
-    return halfs.reshape(-1).view(np.float32).copy(), int(ew)
-
-
-def pack_conv_blocks(weight, block=128):
-    """Conv2d weight [c_out, c_in, k, k] of ANY width -> (wstream, ew) for ``mnerf_conv2d`` with c_out above 128 (csrc/conv.hip: the
-    output channels run in blocks of ``block`` along a grid dimension): the ``pack_conv`` stream of every block of ``block`` rows,
-    one after the other, all with ONE exponent ew (the kernel scales the result back by one power of two per layer).  c_in is
-    zero-padded to a multiple of 32 (the first layer of LPIPS's VGG-16: 3 -> 32).  c_out <= ``block``: exactly ``pack_conv``."""
-    import numpy as np
-    from . import cond_nerf as CN
-    w = (weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)).astype(np.float32)
-    c_out, c_in, kh, kw = w.shape
-    pad = -c_in % 32
-    if pad:
-        w = np.concatenate([w, np.zeros((c_out, pad, kh, kw), np.float32)], 1)
-        c_in += pad
-    assert kh == kw and c_out % 32 == 0 and (c_out <= block or c_out % block == 0), w.shape
-    mat = np.ascontiguousarray(w.transpose(0, 2, 3, 1).reshape(c_out, kh * kw * c_in))
-    ew = CN.f16_weight_exponent(mat)
-    cols = np.arange(mat.shape[1]).reshape(-1, 2, 8)
-    rows = min(block, c_out)
-    parts = [CN._fragments_h(mat[r:r + rows], cols, rows // 32, ew).reshape(-1) for r in range(0, c_out, rows)]
-    return np.concatenate(parts).view(np.float32).copy(), int(ew)
-
-
-def pack_conv_stem(weight):
-    """The stem's weight [64, 3, 7, 7] -> (wstream, ew) for ``mnerf_conv_stem``: matrix [64, 3 tap + c], 147 columns
-    padded with zeros to ten K16-steps."""
-    import numpy as np
-    from . import cond_nerf as CN
-    w = (weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)).astype(np.float32)
-    assert w.shape == (64, 3, 7, 7), w.shape
-    mat = np.zeros((64, 160), np.float32)
-    mat[:, :147] = w.transpose(0, 2, 3, 1).reshape(64, 147)
-    ew = CN.f16_weight_exponent(mat)
-    halfs = CN._fragments_h(mat, np.arange(160).reshape(10, 2, 8), 2, ew)
-    return halfs.reshape(-1).view(np.float32).copy(), int(ew)
-
-
 def _hip_conv(conv, x, in_absmax, **kw):
     """``conv`` (nn.Conv2d with a shape conv.hip builds) through ``mnerf_conv2d``; the packed weights are cached on the
     module and re-packed when the parameter changed."""
     ps = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
-    key = (tuple(int(p._version) for p in ps), tuple(int(p.data_ptr()) for p in ps), str(x.device))
+    key = pack_key(ps, str(x.device))
     if getattr(conv, "_mnerf_pack", None) is None or conv._mnerf_pack[0] != key:
         ws, ew = pack_conv(conv.weight)
         bias = conv.bias.detach().float().contiguous().to(x.device) if conv.bias is not None else None
@@ -215,7 +164,7 @@ class CNNEncoder(nn.Module):
             scal = hip.absmax_regions(14, x.device)  # max|.| of every convolution input (one fill kernel)
             x = x.contiguous()
             hip.absmax(x, scal[13])
-            key = (int(self.conv1.weight._version), int(self.conv1.weight.data_ptr()), str(x.device))
+            key = pack_key([self.conv1.weight], str(x.device))
             if getattr(self, "_stem_pack", None) is None or self._stem_pack[0] != key:
                 ws, ew = pack_conv_stem(self.conv1.weight)
                 self._stem_pack = (key, torch.from_numpy(ws).to(x.device), ew)
@@ -240,80 +189,6 @@ class CNNEncoder(nn.Module):
             x = F.relu(F.instance_norm(self.conv1(x)))
             x = self.conv2(self.layer3(self.layer2(self.layer1(x))))
         return x if tokens_plus is None else x.permute(0, 2, 3, 1) + tokens_plus.reshape(x.shape[2], x.shape[3], -1)
-
-
-EB_SEG_FLOATS = 32 * 256  # one weight segment of the encoder block kernel: 4 K16-steps x 4 blocks x [hi | lo] x 1 KiB
-EB_CHUNK = 128            # hidden units of the FFN produced and consumed at a time
-
-
-def pack_encoder_block(merge_w, mlp0_w=None, mlp2_w=None):
-    """Weights of one transformer layer's post-attention chain -> (wstream float32 words, (ew_merge, ew_w1, ew_w2)) in the
-    split-fp16 MFMA A-fragment layout consumed by ``mnerf_encoder_block`` (csrc/encoder_block.hip; same unit layout as
-    the decoder's stream, cond_nerf.pack_wstream_h).  Segment order: merge (2 segments: input features 0-63, 64-127 in
-    natural order), then for every 128-unit hidden chunk c: mlp.0 rows [128c, 128c+128) (4 segments: the 128 source
-    features in natural order, then the 128 message features in accumulator order) and mlp.2 columns [128c, 128c+128)
-    (2 segments, accumulator order)."""
-    import numpy as np
-    from . import cond_nerf as CN
-
-    def npf(w):
-        return (w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w)).astype(np.float32)
-
-    natural = np.arange(128).reshape(8, 2, 8)          # K16-step t, half h, j -> feature 16 t + 8 h + j
-    acc_order = CN._reg_cols16(4)                      # accumulator-register order of a 128-row stage
-    merge_w = npf(merge_w)
-    ew_m = CN.f16_weight_exponent(merge_w)
-    parts = [CN._fragments_h(merge_w, natural, 4, ew_m)]                      # [8, 4, 2, 64, 8]
-    ews = [ew_m, 0, 0]
-    if mlp0_w is not None:
-        w1, w2 = npf(mlp0_w), npf(mlp2_w)
-        assert w1.shape == (1024, 256) and w2.shape == (128, 1024)
-        ews[1], ews[2] = CN.f16_weight_exponent(w1), CN.f16_weight_exponent(w2)
-        cols1 = np.concatenate([natural, 128 + acc_order], 0)                # 16 steps over cat[source, message]
-        for c in range(1024 // EB_CHUNK):
-            parts.append(CN._fragments_h(w1[EB_CHUNK * c:EB_CHUNK * (c + 1)], cols1, 4, ews[1]))
-            parts.append(CN._fragments_h(w2[:, EB_CHUNK * c:EB_CHUNK * (c + 1)], acc_order, 4, ews[2]))
-    halfs = np.concatenate([p.reshape(-1) for p in parts])                    # fp16, [steps][4][2][64][8] per stage
-    ws = halfs.view(np.float32).copy()
-    assert ws.size % EB_SEG_FLOATS == 0
-    return ws, tuple(int(e) for e in ews)
-
-
-def _k_row_order():
-    """Row permutation of Wk for ``mnerf_qkv_projection`` / ``mnerf_qkv_window_images``: accumulator row 32 m + n of the
-    transposed chain is register r = (n & 3) + 4 (n >> 3) of lane half (n >> 2) & 1; it is given output channel
-    16 t + 8 half + j with 8 t + j = 16 m + r, so that a lane's registers 8t..8t+7 are the eight channels it supplies to
-    K16-step t of the attention's S^T = K Q^T."""
-    import numpy as np
-    rows = np.zeros(128, np.int64)
-    for m in range(4):
-        for n in range(32):
-            r, half = (n & 3) + 4 * (n >> 3), (n >> 2) & 1
-            q = 16 * m + r
-            rows[32 * m + n] = 16 * (q >> 3) + 8 * half + (q & 7)
-    assert sorted(rows.tolist()) == list(range(128))
-    return rows
-
-
-K_ROW_ORDER = _k_row_order()
-
-
-def pack_qkv(wq, wk, wv):
-    """q/k/v projection weights [128,128] -> (wstream float32 words, (ew_q, ew_k, ew_v)) for ``mnerf_qkv_projection``
-    (csrc/qkv.hip): three matrices of 8 K16-steps x 4 row blocks, input features in natural order, each with its own
-    power-of-two scale."""
-    import numpy as np
-    from . import cond_nerf as CN
-    natural = np.arange(128).reshape(8, 2, 8)
-    parts, ews = [], []
-    for i, w in enumerate((wq, wk, wv)):
-        w = (w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w)).astype(np.float32)
-        assert w.shape == (128, 128), w.shape
-        if i == 1:
-            w = w[K_ROW_ORDER]  # accumulator registers 8t..8t+7 of a lane = the attention's K16-step t (csrc/qkv.hip)
-        ews.append(CN.f16_weight_exponent(w))
-        parts.append(CN._fragments_h(w, natural, 4, ews[-1]).reshape(-1))
-    return np.concatenate(parts).view(np.float32).copy(), tuple(int(e) for e in ews)
 
 
 class TransformerLayer(nn.Module):
@@ -345,7 +220,7 @@ class TransformerLayer(nn.Module):
 
     @staticmethod
     def _pack_key(ps, device):
-        return (tuple(int(p._version) for p in ps), tuple(int(p.data_ptr()) for p in ps), str(device))
+        return pack_key(ps, str(device))
 
     def _block_weights(self):
         return [self.merge.weight] + ([] if self.no_ffn else [self.mlp[0].weight, self.mlp[2].weight])
