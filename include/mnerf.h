@@ -1061,6 +1061,69 @@ int mnerf_mesh_smooth(const float* vertices_in, int64_t n_vertices, const int32_
 int mnerf_mesh_normals(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const int32_t* offsets,
                        const int32_t* corners, float* normals, void* stream);
 
+/* mnerf_mesh_decimate (MESH FINISHING, continued; added under v12 without a layout change; the same file) - decimation by vertex
+ * clustering with quadric-error representatives (Lindstrom): the vertices of every cell of a uniform grid become ONE vertex, placed
+ * where the squared distances to the planes of the cell's triangles are smallest, and the triangles that still join three different
+ * cells are kept once each.  The conventions of the section apply: any [V][8] / [T][3] mesh, the bounds on V and T, V == 0 is
+ * MNERF_OK and touches no buffer, enqueue-only, every check before any HIP call (RANGE, NULL, ALIGN), the determinism rule - no
+ * floating-point atomic; integer atomics only in the counts of the two CSR tables and in their row fills, the first of which is
+ * sorted afterwards and the second of which is only searched for the existence of an entry.  The outputs must not overlap the inputs.
+ *   grid           gx x gy x gz cells of side `cell` (finite, > 0) from the corner `origin` (finite); every g* >= 1 and
+ *                  gx gy gz < 2^31.  Cell (i, j, k) has the linear index (k gy + j) gx + i.  The grid is DENSE, as the TSDF volume is:
+ *                  the workspace holds two int32 per cell, occupied or not
+ *   cell of a vertex   per axis q = (x - origin_x) / cell in fp32, the subtraction and the division each rounded on their own;
+ *                  i = clamp(floor(q), 0, gx - 1) (a q of +-inf included).  A vertex outside the grid belongs to the nearest border
+ *                  cell.  A vertex with a non-finite x, y or z has NO cell: it is dropped, vertex_map[v] = -1
+ *   new vertices   one per occupied cell, in ascending linear cell index;  vertex_map: device int32 [V] or NULL, the new row of v's cell
+ *   members        a cell's vertices in ascending row order (a cell -> vertex CSR built as mnerf_mesh_adjacency builds its rows:
+ *                  integer atomic add, the two-level scan over the cells, the fill through a cursor, the cell's thread sorts its row)
+ *   offsets, corners   as mnerf_mesh_adjacency wrote them for THIS mesh (vertex_class is not read)
+ *   representative all in fp64, every operation rounded on its own (no FMA).  g = origin + (index + 0.5) cell per axis, evaluated
+ *                  in double from the fp32 arguments; every point below is (double) p - g.
+ *                  Vertex quadric: for member v, over its corners ascending, the corner's triangle (p0, p1, p2) in stored winding:
+ *                    u = p1 - p0, t = p2 - p0;  n = u x t (x: u_y t_z - u_z t_y, y: u_z t_x - u_x t_z, z: u_x t_y - u_y t_x);
+ *                    d = -((n_x p0_x + n_y p0_y) + n_z p0_z);  A_v += n n^T (xx xy xz yy yz zz);  b_v += d n.
+ *                  n n^T weighs a plane by its squared area: a degenerate triangle adds exactly 0, there is no square root and
+ *                  no division.  A triangle with an index outside [0, V) or a non-finite vertex is skipped.
+ *                  Cell quadric: A = sum A_v, b = sum b_v over the members ascending.  Means: m = (sum ((double) p_v - g)) / count,
+ *                  and w, r, g, b = (sum (double) value) / count, over the members ascending.
+ *                  lambda = REG (A_xx + A_yy + A_zz), REG = 1.0 / MNERF_DECIMATE_REG_INV = 1e-3 (the nearest double; the constant is
+ *                  kept as its integer inverse because every #define of this header is an integer).  If lambda is not > 0 (no
+ *                  area at all): x = m.  Otherwise x solves
+ *                  (A + lambda I) x = lambda m - b - symmetric positive definite, condition number <= 1 / REG + 1 - by Gaussian
+ *                  elimination without pivoting.  x is then CLAMPED per component to [-cell / 2, +cell / 2] in double (a clamp, not a
+ *                  fallback: the result is continuous in its inputs; a NaN goes to the lower bound).
+ *                  Row: (float) (g + x) | (float) w | (float) r g b | 0.
+ *                  GUARANTEE: every new vertex lies in the closed box g +- cell / 2 of its cell, up to the final rounding to fp32.
+ *   triangles      a triangle is a CANDIDATE iff its three indices are in [0, V), its three vertices have cells and its three new
+ *                  rows are pairwise distinct; a candidate is KEPT iff no candidate with a smaller triangle index has the same SET
+ *                  of three new rows (winding ignored).  triangles_out: the kept triangles in their original order, each with its
+ *                  own stored winding, re-numbered.  (The candidates' adjacency over the new rows, by the kernels of
+ *                  mnerf_mesh_adjacency; one thread per candidate walks the row of its smallest new row for an earlier triangle
+ *                  of the same set; the mesher's count / scan / scatter over the flags.)
+ *   vertices_out   device [vertex_capacity] rows, 16-byte aligned;  triangles_out: device [triangle_capacity][3] int32
+ *   counts         device int64 [2], 8-byte aligned: new vertices, kept triangles.  Rows at or beyond a capacity are not written,
+ *                  the counts are the totals either way and the call is MNERF_OK.  V and T are upper bounds of the two counts.
+ *   workspace      device, 16-byte aligned, mnerf_mesh_decimate_workspace_bytes(V, T, gx, gy, gz) bytes, scratch only.  With
+ *                  N = gx gy gz, Bn = ceil(N / 256), Tn = ceil(Bn / 1024) and Bv, Tv, Bt, Tt alike from V and T:  int64 [2] |
+ *                  int32 [V] the cell of a vertex | [V] the members | [N + 1] the cells' offsets | [N] the fill cursor, then the
+ *                  cells' new rows | [Bn] [Tn] | [3 T] the candidates | [V + 1] [V] [3 T] their offsets, cursor and corners |
+ *                  [Bv] [Tv] | [Bt] [Tt] | uint8 [T] the kept flags:
+ *                  16 + 4 (4 V + 2 N + 2 + 6 T + Bn + Tn + Bv + Tv + Bt + Tt) + T bytes, rounded up to 16.
+ * One thread per vertex, cell or triangle, 256 per workgroup; 12 launches for the vertices (11 without vertex_map) and 12 for the
+ * triangles (1 with T == 0).  A cell's sums run inside ONE thread: a pathological grid - one cell holding a huge mesh - serialises
+ * them (the row is sorted by a heap sort, so that costs n log n, and the sums n).
+ * MNERF_E_RANGE: the bounds of the section, a g* < 1, gx gy gz >= 2^31, a cell not finite and positive, an origin not finite, a negative
+ * capacity.  MNERF_E_NULL: vertices, offsets, counts or workspace missing; triangles or corners missing with T > 0; an output missing
+ * with its capacity > 0.  MNERF_E_ALIGN: vertices, vertices_out or workspace not 16-byte, counts not 8-byte, any other not 4-byte
+ * aligned.  mnerf_mesh_decimate_workspace_bytes: host only; -1 beyond the bounds (of V, T or the grid), 0 for V == 0. */
+#define MNERF_DECIMATE_REG_INV 1000 /* the regularisation weight of mnerf_mesh_decimate is 1.0 / this */
+int64_t mnerf_mesh_decimate_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int32_t gx, int32_t gy, int32_t gz);
+int mnerf_mesh_decimate(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, const int32_t* offsets,
+                        const int32_t* corners, float origin_x, float origin_y, float origin_z, float cell, int32_t gx, int32_t gy,
+                        int32_t gz, float* vertices_out, int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity,
+                        int32_t* vertex_map, int64_t* counts, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -757,8 +757,9 @@ class Coach:
         where given.  With the option nerf.export_mesh also <stem>_mesh.ply next to each cloud: the triangle mesh of the same maps
         (``fusion.mesh``: TSDF fusion + marching tetrahedra; float xyz + uchar rgb vertices and a face list), with nerf.mesh_resolution /
         mesh_voxel / mesh_trunc / mesh_min_weight where given, cleaned up by nerf.mesh_min_component / mesh_min_component_fraction
-        (small connected components dropped) and nerf.mesh_smooth (rounds of Taubin smoothing) where given; with nerf.mesh_normals
-        the vertices also carry float nx ny nz (``fusion.vertex_normals``).  One process (not sharded).
+        (small connected components dropped), nerf.mesh_smooth (rounds of Taubin smoothing) and nerf.mesh_decimate (quadric
+        vertex clustering with cells of that many voxels, applied last) where given; with nerf.mesh_normals the vertices also carry
+        float nx ny nz (``fusion.vertex_normals`` of the mesh that is written).  One process (not sharded).
         Returns {set: [path of every .ply]}."""
         from PIL import Image
 
@@ -777,8 +778,9 @@ class Coach:
                                                                               ("trunc", "mesh_trunc"), ("min_weight", "mesh_min_weight"),
                                                                               ("min_component", "mesh_min_component"),
                                                                               ("min_component_fraction", "mesh_min_component_fraction"),
-                                                                              ("smooth", "mesh_smooth"))
+                                                                              ("smooth", "mesh_smooth"), ("decimate", "mesh_decimate"))
                          if getattr(self.opts.nerf, name, None) is not None}
+            fusion._decimate_cell("nerf.mesh_decimate", mesh_args.get("decimate", 0.0))  # refused before anything is rendered
         mesh_normals = bool(getattr(self.opts.nerf, "mesh_normals", None))
         out_root = os.path.join(self.opts.output_path, "geometry")
         written = {}

@@ -11,10 +11,12 @@
 //   compact_count / finish_scan / finish_total / compact_vertices / compact_triangles   the mesher's stable scan and scatter
 //   smooth_step             one Jacobi step of the umbrella operator, ping-pong through the workspace
 //   normals                 the corner sum of the triangles' cross products
+//   dec_*                   decimation by quadric vertex clustering (section 6 below)
 // THE DETERMINISM RULE: two runs give the same bytes in every output.  No floating-point atomic anywhere: every float sum runs over
 // a CSR row in ascending corner order inside one thread.  Integer atomics only where the final memory contents do not depend on
 // their order: the corner counts and triangle counts (add), the largest component (max), the union-find's hooks (whose final roots
-// are the components' smallest rows whatever the order), and the row fill, which is sorted afterwards.
+// are the components' smallest rows whatever the order), and the row fill, which is sorted afterwards (the decimation's second
+// table is not sorted: its rows are only searched for the existence of an entry).
 #include <math.h>
 
 #include "common.hpp"
@@ -561,5 +563,338 @@ extern "C" int mnerf_mesh_normals(const float* vertices, int64_t n_vertices, con
   hipLaunchKernelGGL(normals_kernel, dim3(blocks_of(n_vertices)), dim3(PC_BLOCK), 0, (hipStream_t)stream, vertices, triangles, offsets,
                      corners, (int)n_vertices, normals);
   return mnerf_check_launch("mnerf_mesh_normals");
+}
+
+// ------------------------------------------------------------------------------------------------ 6. decimation
+// Quadric vertex clustering over a dense uniform grid (include/mnerf.h "mnerf_mesh_decimate"):
+//   dec_cells / finish_* / adj_offsets / dec_fill        the cell of every vertex; the cell -> vertex rows, built as the adjacency's
+//   dec_occupied / finish_scan / finish_total / dec_representatives   the stable scan over the occupied cells; every cell's thread
+//                           sorts its row, sums its quadric in fp64 and writes the new vertex
+//   dec_candidates / adj_* / dec_first / finish_scan / finish_total / dec_triangles   the new index triples, their adjacency, the
+//                           first triangle of every set of three new rows, the stable scan and scatter over those
+constexpr double MNERF_DECIMATE_REG = 1.0 / MNERF_DECIMATE_REG_INV;
+struct DecGrid {
+  float ox, oy, oz, cell;
+  int gx, gy, gz;
+};
+
+__device__ __forceinline__ int dec_axis(float x, float origin, float cell, int g) {
+  const float q = (x - origin) / cell;
+  return (int)fmin(fmax((double)floorf(q), 0.0), (double)(g - 1));  // (clamped in double: q may be +-inf, g - 1 no fp32 number)
+}
+
+// the linear cell index of a position; -1: not finite
+__device__ __forceinline__ int dec_cell_of(const float4 p, const DecGrid& g) {
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return -1;
+  const int i = dec_axis(p.x, g.ox, g.cell, g.gx), j = dec_axis(p.y, g.oy, g.cell, g.gy), k = dec_axis(p.z, g.oz, g.cell, g.gz);
+  return (k * g.gy + j) * g.gx + i;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_cells_kernel(const float* __restrict__ vertices, int n_vertices, DecGrid g,
+                                                             int* __restrict__ cell_of, int* __restrict__ cell_offsets) {
+  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  if (i >= n_vertices) return;
+  const int c = dec_cell_of(reinterpret_cast<const float4*>(vertices)[(size_t)i * 2], g);
+  cell_of[i] = c;
+  if (c >= 0) atomicAdd(&cell_offsets[c], 1);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_fill_kernel(const int* __restrict__ cell_of, int n_vertices, int* __restrict__ cursor,
+                                                            int* __restrict__ members) {
+  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  if (i >= n_vertices) return;
+  const int c = cell_of[i];
+  if (c >= 0) members[atomicAdd(&cursor[c], 1)] = (int)i;  // (a slot of the cell's row: the row is sorted below)
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_occupied_kernel(const int* __restrict__ cell_offsets, int n_cells, int* __restrict__ counts) {
+  const long long c = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  int total;
+  block_prefix(c < n_cells && cell_offsets[c + 1] > cell_offsets[c], total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// ascending, in place, any length: a cell's row can be long and arrives in no order, so not the insertion sort of the short rows
+__device__ __forceinline__ void dec_sort(int* a, int n) {
+  for (int end = 1; end < n; ++end) {  // sift every element up into the max-heap a[0 .. end]
+    int child = end;
+    const int key = a[child];
+    while (child > 0) {
+      const int parent = (child - 1) >> 1;
+      if (a[parent] >= key) break;
+      a[child] = a[parent];
+      child = parent;
+    }
+    a[child] = key;
+  }
+  for (int end = n - 1; end > 0; --end) {  // the largest to the end, the former last element sifted down from the root
+    const int key = a[end];
+    a[end] = a[0];
+    int parent = 0;
+    for (;;) {
+      int child = 2 * parent + 1;
+      if (child >= end) break;
+      if (child + 1 < end && a[child + 1] > a[child]) ++child;
+      if (a[child] <= key) break;
+      a[parent] = a[child];
+      parent = child;
+    }
+    a[parent] = key;
+  }
+}
+
+__device__ __forceinline__ double dec_clamp(double x, double half) { return fmin(fmax(x, -half), half); }  // (a NaN -> -half)
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_representatives_kernel(
+    const float* __restrict__ vertices, const int* __restrict__ triangles, const int* __restrict__ offsets, const int* __restrict__ corners,
+    int n_vertices, int n_triangles, DecGrid g, int n_cells, const int* __restrict__ cell_offsets, int* __restrict__ members,
+    const int* __restrict__ counts, const int* __restrict__ tiles, int* __restrict__ cell_row, float* __restrict__ out, long long capacity) {
+  const long long c = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  const int begin = c < n_cells ? cell_offsets[c] : 0, end = c < n_cells ? cell_offsets[c + 1] : 0;
+  const bool occupied = end > begin;
+  int total;
+  const int before = block_prefix(occupied, total);
+  if (c >= n_cells) return;
+  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  cell_row[c] = occupied ? (int)row : -1;
+  if (!occupied || row >= capacity) return;
+  dec_sort(members + begin, end - begin);
+  const int plane = g.gx * g.gy, ck = (int)(c / plane), cj = (int)((c - (long long)ck * plane) / g.gx), ci = (int)(c - (long long)ck * plane - cj * g.gx);
+  const double h = (double)g.cell;
+  const double gx = (double)g.ox + ((double)ci + 0.5) * h, gy = (double)g.oy + ((double)cj + 0.5) * h, gz = (double)g.oz + ((double)ck + 0.5) * h;
+  const float4* rows = reinterpret_cast<const float4*>(vertices);
+  double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
+  double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0, sr = 0.0, sg = 0.0, sb = 0.0;
+  for (int m = begin; m < end; ++m) {
+    const int v = members[m];
+    const float4 p = rows[(size_t)v * 2], q = rows[(size_t)v * 2 + 1];
+    sx = sx + ((double)p.x - gx), sy = sy + ((double)p.y - gy), sz = sz + ((double)p.z - gz);
+    sw = sw + (double)p.w, sr = sr + (double)q.x, sg = sg + (double)q.y, sb = sb + (double)q.z;
+    double vxx = 0.0, vxy = 0.0, vxz = 0.0, vyy = 0.0, vyz = 0.0, vzz = 0.0, wx = 0.0, wy = 0.0, wz = 0.0;
+    for (int a = offsets[v]; a < offsets[v + 1]; ++a) {
+      const int t = corners[a] / 3;
+      int i0, i1, i2;
+      if (!in_range(t, n_triangles) || !triangle_ok(triangles, t, n_vertices, i0, i1, i2)) continue;
+      const float4 f0 = rows[(size_t)i0 * 2], f1 = rows[(size_t)i1 * 2], f2 = rows[(size_t)i2 * 2];
+      if (!(isfinite(f0.x) && isfinite(f0.y) && isfinite(f0.z) && isfinite(f1.x) && isfinite(f1.y) && isfinite(f1.z) && isfinite(f2.x) &&
+            isfinite(f2.y) && isfinite(f2.z)))
+        continue;
+      const double p0x = (double)f0.x - gx, p0y = (double)f0.y - gy, p0z = (double)f0.z - gz;
+      const double ux = ((double)f1.x - gx) - p0x, uy = ((double)f1.y - gy) - p0y, uz = ((double)f1.z - gz) - p0z;
+      const double tx = ((double)f2.x - gx) - p0x, ty = ((double)f2.y - gy) - p0y, tz = ((double)f2.z - gz) - p0z;
+      const double nx = uy * tz - uz * ty, ny = uz * tx - ux * tz, nz = ux * ty - uy * tx;
+      const double d = -((nx * p0x + ny * p0y) + nz * p0z);
+      vxx = vxx + nx * nx, vxy = vxy + nx * ny, vxz = vxz + nx * nz, vyy = vyy + ny * ny, vyz = vyz + ny * nz, vzz = vzz + nz * nz;
+      wx = wx + d * nx, wy = wy + d * ny, wz = wz + d * nz;
+    }
+    axx = axx + vxx, axy = axy + vxy, axz = axz + vxz, ayy = ayy + vyy, ayz = ayz + vyz, azz = azz + vzz;
+    bx = bx + wx, by = by + wy, bz = bz + wz;
+  }
+  const double n = (double)(end - begin);
+  const double mx = sx / n, my = sy / n, mz = sz / n;
+  double x = mx, y = my, z = mz;
+  const double lambda = MNERF_DECIMATE_REG * ((axx + ayy) + azz);
+  if (lambda > 0.0) {  // (A + lambda I) x = lambda m - b by elimination without pivoting: symmetric positive definite, cond <= 1 / REG + 1
+    const double m00 = axx + lambda, m11 = ayy + lambda, m22 = azz + lambda;
+    const double r0 = lambda * mx - bx, r1 = lambda * my - by, r2 = lambda * mz - bz;
+    const double l10 = axy / m00, l20 = axz / m00;
+    const double e11 = m11 - l10 * axy, e12 = ayz - l10 * axz, e22 = m22 - l20 * axz;
+    const double s1 = r1 - l10 * r0, s2 = r2 - l20 * r0;
+    const double l21 = e12 / e11;
+    z = (s2 - l21 * s1) / (e22 - l21 * e12);
+    y = (s1 - e12 * z) / e11;
+    x = ((r0 - axy * y) - axz * z) / m00;
+  }
+  const double half = 0.5 * h;
+  float4* dst = reinterpret_cast<float4*>(out) + (size_t)row * 2;
+  dst[0] = make_float4((float)(gx + dec_clamp(x, half)), (float)(gy + dec_clamp(y, half)), (float)(gz + dec_clamp(z, half)), (float)(sw / n));
+  dst[1] = make_float4((float)(sr / n), (float)(sg / n), (float)(sb / n), 0.0f);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_map_kernel(const int* __restrict__ cell_of, const int* __restrict__ cell_row, int n_vertices,
+                                                           int* __restrict__ vertex_map) {
+  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  if (i >= n_vertices) return;
+  const int c = cell_of[i];
+  vertex_map[i] = c >= 0 ? cell_row[c] : -1;
+}
+
+// the new rows of every triangle; -1 -1 -1 unless it is a candidate
+__global__ __launch_bounds__(PC_BLOCK) void dec_candidates_kernel(const int* __restrict__ triangles, long long n_triangles, int n_vertices,
+                                                                  const int* __restrict__ cell_of, const int* __restrict__ cell_row,
+                                                                  int* __restrict__ candidates) {
+  const long long t = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  if (t >= n_triangles) return;
+  int a, b, c, ra = -1, rb = -1, rc = -1;
+  if (triangle_ok(triangles, t, n_vertices, a, b, c)) {
+    const int ca = cell_of[a], cb = cell_of[b], cc = cell_of[c];
+    if (ca >= 0 && cb >= 0 && cc >= 0 && ca != cb && cb != cc && ca != cc) ra = cell_row[ca], rb = cell_row[cb], rc = cell_row[cc];
+  }
+  candidates[3 * t] = ra, candidates[3 * t + 1] = rb, candidates[3 * t + 2] = rc;
+}
+
+__device__ __forceinline__ void dec_sort3(int& a, int& b, int& c) {
+  int s;
+  if (a > b) s = a, a = b, b = s;
+  if (b > c) s = b, b = c, c = s;
+  if (a > b) s = a, a = b, b = s;
+}
+
+// keep[t] = t is a candidate and no candidate before it has its three new rows: one thread per triangle walks the row of its smallest
+// new vertex (in whatever order the fill left it: the answer is the existence of an earlier one)
+__global__ __launch_bounds__(PC_BLOCK) void dec_first_kernel(const int* __restrict__ candidates, long long n_triangles,
+                                                             const int* __restrict__ offsets, const int* __restrict__ corners,
+                                                             unsigned char* __restrict__ keep, int* __restrict__ counts) {
+  const long long t = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  bool first = false;
+  if (t < n_triangles) {
+    int a = candidates[3 * t], b = candidates[3 * t + 1], c = candidates[3 * t + 2];
+    if (a >= 0) {
+      dec_sort3(a, b, c);
+      first = true;
+      for (int k = offsets[a]; k < offsets[a + 1] && first; ++k) {
+        const int u = corners[k] / 3;
+        if (u >= t) continue;
+        int d = candidates[3 * u], e = candidates[3 * u + 1], f = candidates[3 * u + 2];
+        dec_sort3(d, e, f);
+        first = !(d == a && e == b && f == c);
+      }
+    }
+    keep[t] = first;
+  }
+  int total;
+  block_prefix(first, total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void dec_triangles_kernel(const int* __restrict__ candidates, long long n_triangles,
+                                                                 const unsigned char* __restrict__ keep, const int* __restrict__ counts,
+                                                                 const int* __restrict__ tiles, int* __restrict__ out, long long capacity) {
+  const long long t = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
+  const bool kept = t < n_triangles && keep[t];
+  int total;
+  const int before = block_prefix(kept, total);
+  if (!kept) return;
+  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  if (row >= capacity) return;
+  out[row * 3 + 0] = candidates[3 * t];
+  out[row * 3 + 1] = candidates[3 * t + 1];
+  out[row * 3 + 2] = candidates[3 * t + 2];
+}
+
+struct DecWorkspace {
+  long long bytes;
+  // int64 [2] | int32 [V] cell of a vertex | [V] members | [N + 1] cell offsets | [N] the fill cursor, then the cells' new rows |
+  // [Bn] [Tn] | [3 T] candidates | [V + 1] [V] [3 T] their adjacency and its cursor | [Bv] [Tv] | [Bt] [Tt] | uint8 [T] keep
+  size_t head, cell_of, members, cell_offsets, cell_row, ncounts, ntiles, candidates, tri_offsets, tri_cursor, tri_corners, vcounts, vtiles,
+      tcounts, ttiles, keep;
+  FinishScan sn, sv, st;
+};
+static DecWorkspace dec_workspace(long long n_vertices, long long n_triangles, long long n_cells) {
+  DecWorkspace w = {};
+  if (n_vertices == 0) return w;
+  const size_t v = (size_t)n_vertices, t = (size_t)n_triangles, n = (size_t)n_cells;
+  w.sn = finish_scan(n_cells), w.sv = finish_scan(n_vertices), w.st = finish_scan(n_triangles);
+  w.head = 0;
+  w.cell_of = 16;
+  w.members = w.cell_of + 4 * v;
+  w.cell_offsets = w.members + 4 * v;
+  w.cell_row = w.cell_offsets + 4 * (n + 1);
+  w.ncounts = w.cell_row + 4 * n;
+  w.ntiles = w.ncounts + 4 * (size_t)w.sn.blocks;
+  w.candidates = w.ntiles + 4 * (size_t)w.sn.tiles;
+  w.tri_offsets = w.candidates + 12 * t;
+  w.tri_cursor = w.tri_offsets + 4 * (v + 1);
+  w.tri_corners = w.tri_cursor + 4 * v;
+  w.vcounts = w.tri_corners + 12 * t;
+  w.vtiles = w.vcounts + 4 * (size_t)w.sv.blocks;
+  w.tcounts = w.vtiles + 4 * (size_t)w.sv.tiles;
+  w.ttiles = w.tcounts + 4 * (size_t)w.st.blocks;
+  w.keep = w.ttiles + 4 * (size_t)w.st.tiles;
+  w.bytes = (long long)((w.keep + t + 15) & ~(size_t)15);
+  return w;
+}
+
+static bool dec_grid_ok(int32_t gx, int32_t gy, int32_t gz) {
+  return gx >= 1 && gy >= 1 && gz >= 1 && (long long)gx * gy < (1ll << 31) && (long long)gx * gy * gz < (1ll << 31);
+}
+
+extern "C" int64_t mnerf_mesh_decimate_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int32_t gx, int32_t gy, int32_t gz) {
+  if (!finish_sizes_ok(n_vertices, n_triangles) || !dec_grid_ok(gx, gy, gz)) return -1;
+  return dec_workspace(n_vertices, n_triangles, (long long)gx * gy * gz).bytes;
+}
+
+extern "C" int mnerf_mesh_decimate(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles,
+                                   const int32_t* offsets, const int32_t* corners, float origin_x, float origin_y, float origin_z, float cell,
+                                   int32_t gx, int32_t gy, int32_t gz, float* vertices_out, int64_t vertex_capacity, int32_t* triangles_out,
+                                   int64_t triangle_capacity, int32_t* vertex_map, int64_t* counts, void* workspace, void* stream) {
+  MNERF_REQUIRE(finish_sizes_ok(n_vertices, n_triangles), MNERF_E_RANGE, "mnerf_mesh_decimate: %lld vertices / %lld triangles",
+                (long long)n_vertices, (long long)n_triangles);
+  MNERF_REQUIRE(dec_grid_ok(gx, gy, gz), MNERF_E_RANGE, "mnerf_mesh_decimate: a grid of %d x %d x %d cells (every axis >= 1, the product < 2^31)",
+                gx, gy, gz);
+  MNERF_REQUIRE(std::isfinite(cell) && cell > 0.0f, MNERF_E_RANGE, "mnerf_mesh_decimate: cell=%g must be finite and > 0", (double)cell);
+  MNERF_REQUIRE(std::isfinite(origin_x) && std::isfinite(origin_y) && std::isfinite(origin_z), MNERF_E_RANGE,
+                "mnerf_mesh_decimate: origin (%g, %g, %g) is not finite", (double)origin_x, (double)origin_y, (double)origin_z);
+  MNERF_REQUIRE(vertex_capacity >= 0 && triangle_capacity >= 0, MNERF_E_RANGE, "mnerf_mesh_decimate: capacities %lld / %lld",
+                (long long)vertex_capacity, (long long)triangle_capacity);
+  if (n_vertices == 0) return MNERF_OK;
+  MNERF_REQUIRE(vertices && offsets && counts && workspace, MNERF_E_NULL, "mnerf_mesh_decimate: NULL vertices / offsets / counts / workspace");
+  MNERF_REQUIRE(n_triangles == 0 || (triangles && corners), MNERF_E_NULL, "mnerf_mesh_decimate: NULL triangles / corners");
+  MNERF_REQUIRE(vertex_capacity == 0 || vertices_out, MNERF_E_NULL, "mnerf_mesh_decimate: vertices_out is NULL");
+  MNERF_REQUIRE(triangle_capacity == 0 || triangles_out, MNERF_E_NULL, "mnerf_mesh_decimate: triangles_out is NULL");
+  MNERF_REQUIRE(mnerf_aligned16(vertices) && mnerf_aligned16(vertices_out) && mnerf_aligned16(workspace), MNERF_E_ALIGN,
+                "mnerf_mesh_decimate: vertices / vertices_out / workspace not 16B aligned");
+  MNERF_REQUIRE(aligned_to(triangles, 4) && aligned_to(offsets, 4) && aligned_to(corners, 4) && aligned_to(triangles_out, 4) &&
+                    aligned_to(vertex_map, 4) && aligned_to(counts, 8),
+                MNERF_E_ALIGN, "mnerf_mesh_decimate: triangles / offsets / corners / triangles_out / vertex_map / counts not aligned to 4 / 8 bytes");
+  const long long n_cells_ll = (long long)gx * gy * gz;
+  const DecWorkspace w = dec_workspace(n_vertices, n_triangles, n_cells_ll);
+  char* base = static_cast<char*>(workspace);
+  long long* total = reinterpret_cast<long long*>(base + w.head);
+  auto ints = [&](size_t at) { return reinterpret_cast<int*>(base + at); };
+  int *cell_of = ints(w.cell_of), *members = ints(w.members), *cell_offsets = ints(w.cell_offsets), *cell_row = ints(w.cell_row);
+  int *ncounts = ints(w.ncounts), *ntiles = ints(w.ntiles), *candidates = ints(w.candidates), *tri_offsets = ints(w.tri_offsets);
+  int *tri_cursor = ints(w.tri_cursor), *tri_corners = ints(w.tri_corners), *vcounts = ints(w.vcounts), *vtiles = ints(w.vtiles);
+  int *tcounts = ints(w.tcounts), *ttiles = ints(w.ttiles);
+  unsigned char* keep = reinterpret_cast<unsigned char*>(base + w.keep);
+  long long* count = reinterpret_cast<long long*>(counts);
+  const DecGrid g = {origin_x, origin_y, origin_z, cell, gx, gy, gz};
+  const int nv = (int)n_vertices, nc = (int)n_cells_ll;
+  const long long nt = (long long)n_triangles, n_corners = 3 * nt;
+  const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices)), nblocks(blocks_of(n_cells_ll)), tblocks(blocks_of(nt)), cblocks(blocks_of(n_corners));
+  hipStream_t st = (hipStream_t)stream;
+  // the cell -> vertex rows
+  hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_cells_ll + 1)), threads, 0, st, cell_offsets, nc);
+  hipLaunchKernelGGL(dec_cells_kernel, vblocks, threads, 0, st, vertices, nv, g, cell_of, cell_offsets);
+  hipLaunchKernelGGL(finish_blocksum_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts);
+  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sn.tiles), threads, 0, st, ncounts, (int)w.sn.blocks, ntiles);
+  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ntiles, (int)w.sn.tiles, total);
+  hipLaunchKernelGGL(adj_offsets_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts, ntiles, cell_row);
+  hipLaunchKernelGGL(dec_fill_kernel, vblocks, threads, 0, st, cell_of, nv, cell_row, members);
+  // the new vertices
+  hipLaunchKernelGGL(dec_occupied_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts);
+  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sn.tiles), threads, 0, st, ncounts, (int)w.sn.blocks, ntiles);
+  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ntiles, (int)w.sn.tiles, count);
+  hipLaunchKernelGGL(dec_representatives_kernel, nblocks, threads, 0, st, vertices, triangles, offsets, corners, nv, (int)nt, g, nc,
+                     cell_offsets, members, ncounts, ntiles, cell_row, vertices_out, (long long)vertex_capacity);
+  if (vertex_map) hipLaunchKernelGGL(dec_map_kernel, vblocks, threads, 0, st, cell_of, cell_row, nv, vertex_map);
+  // the new triangles: the adjacency of the candidates over the new rows (at most V of them), the first of every set, the scatter
+  if (nt) {
+    hipLaunchKernelGGL(dec_candidates_kernel, tblocks, threads, 0, st, triangles, nt, nv, cell_of, cell_row, candidates);
+    hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_vertices + 1)), threads, 0, st, tri_offsets, nv);
+    hipLaunchKernelGGL(adj_count_kernel, cblocks, threads, 0, st, candidates, n_corners, nv, tri_offsets);
+    hipLaunchKernelGGL(finish_blocksum_kernel, vblocks, threads, 0, st, tri_offsets, nv, vcounts);
+    hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sv.tiles), threads, 0, st, vcounts, (int)w.sv.blocks, vtiles);
+    hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, vtiles, (int)w.sv.tiles, total + 1);
+    hipLaunchKernelGGL(adj_offsets_kernel, vblocks, threads, 0, st, tri_offsets, nv, vcounts, vtiles, tri_cursor);
+    hipLaunchKernelGGL(adj_fill_kernel, cblocks, threads, 0, st, candidates, n_corners, nv, tri_cursor, tri_corners);
+    hipLaunchKernelGGL(dec_first_kernel, tblocks, threads, 0, st, candidates, nt, tri_offsets, tri_corners, keep, tcounts);
+    hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.st.tiles), threads, 0, st, tcounts, (int)w.st.blocks, ttiles);
+  }
+  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ttiles, (int)w.st.tiles, count + 1);
+  if (nt)
+    hipLaunchKernelGGL(dec_triangles_kernel, tblocks, threads, 0, st, candidates, nt, keep, tcounts, ttiles, triangles_out,
+                       (long long)triangle_capacity);
+  return mnerf_check_launch("mnerf_mesh_decimate");
 }
 #pragma clang fp contract(fast)

@@ -13,7 +13,8 @@ indexed, coloured triangle mesh whose vertex and face order is defined - two run
 
 ``finish`` and ``vertex_normals`` clean such a mesh - or any indexed mesh in the same layout - up on the device (include/mnerf.h "MESH
 FINISHING", matchnerf_amd/csrc/mesh_finish.hip): small connected components dropped, Taubin smoothing of the positions,
-area-weighted vertex normals; ``write_ply`` takes the normals.
+area-weighted vertex normals; ``write_ply`` takes the normals.  ``decimate`` reduces it by quadric vertex clustering over a uniform
+grid (``hip.mesh_decimate``): one vertex per occupied cell, the same bytes on every run.
 """
 import numpy as np
 import torch
@@ -113,7 +114,7 @@ def _auto_bounds(views, fused, counts, rgbs, hw, legacy, min_consistent):
 
 def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
          consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None, min_component=0,
-         min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+         min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, decimate=0.0):
     """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
     fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
     (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
@@ -127,9 +128,12 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
     mesh launch and the two counts after it.  The vertex and face buffers are sized from a first guess (a few rows per voxel of the
     grid's three faces); when the counts exceed it the mesher is RUN AGAIN ONCE with exact sizes - no further copy.
       min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu    ``finish`` applied to the result (one more copy
-                    when a component threshold is set)"""
+                    when a component threshold is set)
+      decimate      > 0: the finished mesh is decimated (``decimate`` below) with cells of ``decimate`` VOXELS on a grid aligned with the
+                    volume - the same origin, ceil(n / decimate) cells per axis - so no box is copied; one more copy, of the counts"""
     h, w = int(hw[0]), int(hw[1])
     n, k_views = h * w, len(views)
+    decimate = _decimate_cell("mesh", decimate)
     if k_views < 1 or (consistency and k_views < 2):
         raise ValueError(f"mesh: {k_views} view(s); cross-view consistency needs at least 2")
     if min_consistent is None:
@@ -203,18 +207,34 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
         faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
         hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, counts=totals, workspace=workspace)
     return finish(vertices[:n_vertices], faces[:n_faces], min_component=min_component, min_component_fraction=min_component_fraction,
-                  smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
+                  smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, decimate_cell=decimate * voxel, decimate_origin=origin,
+                  decimate_dims=tuple(int(np.ceil(d / decimate)) for d in dims) if decimate > 0 else None)
 
 
-def finish(vertices, faces, *, min_component=0, min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+def _decimate_cell(what, cell):
+    """the cell size of a decimation, checked before anything is launched; 0 = none"""
+    cell = float(cell)
+    if not (np.isfinite(cell) and cell >= 0.0):
+        raise ValueError(f"{what}: a decimation cell of {cell}; it must be finite and >= 0 (0: no decimation)")
+    return cell
+
+
+def finish(vertices, faces, *, min_component=0, min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53,
+           decimate_cell=0.0, decimate_origin=None, decimate_dims=None):
     """Clean an indexed mesh up on the device (include/mnerf.h "MESH FINISHING") -> (vertices [V', 8], faces [T', 3]):
       min_component, min_component_fraction   drop every connected component with fewer than ``min_component`` triangles or fewer
                     than ``min_component_fraction`` of the largest component's (the floaters next to the surface); the kept rows
                     and faces keep their order.  The two counts of the result cost ONE device->host copy
       smooth        rounds of Taubin smoothing (``smooth_lambda``, ``smooth_mu``) of the positions over the adjacency OF THE RESULT;
                     colours and weights stay, boundary vertices do not move
+      decimate_cell, decimate_origin, decimate_dims   > 0: ``decimate`` of the result, applied LAST (components, smoothing, decimation)
     The same bytes on every run.  With nothing asked for the inputs are returned and nothing is launched."""
+    decimate_cell = _decimate_cell("finish", decimate_cell)
     filtering = int(min_component) > 0 or float(min_component_fraction) > 0.0
+    if decimate_cell > 0.0:
+        vertices, faces = finish(vertices, faces, min_component=min_component, min_component_fraction=min_component_fraction, smooth=smooth,
+                                 smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
+        return decimate(vertices, faces, decimate_cell, decimate_origin, decimate_dims)
     if not filtering and int(smooth) == 0:
         return vertices, faces
     vertices, faces = vertices.contiguous(), faces.contiguous()
@@ -229,6 +249,45 @@ def finish(vertices, faces, *, min_component=0, min_component_fraction=0.0, smoo
         adjacency = hip.mesh_adjacency(faces, n_vertices, workspace=workspace)
         vertices = hip.mesh_smooth(vertices, faces, adjacency, int(smooth), smooth_lambda, smooth_mu, workspace=workspace)
     return vertices, faces
+
+
+def decimate(vertices, faces, cell, origin=None, dims=None):
+    """Decimate an indexed mesh by quadric vertex clustering (``hip.mesh_decimate``) -> (vertices [V', 8], faces [T', 3]) on the device:
+    the vertices of every cell of side ``cell`` become one vertex - where the squared distances to the planes of the cell's triangles
+    are smallest, kept inside the cell; weight and colour are the cell's means - and the triangles that still join three cells are kept
+    once each, in their order.  The geometric error is bounded by the cell's diagonal; the result need not be manifold (two sheets
+    closer than a cell merge).
+      origin, dims  the grid: its corner (x, y, z) and (gx, gy, gz) cells; vertices outside belong to the nearest border cell.  Both
+                    None: the grid of the vertices' finite bounding box, which costs one device->host copy (the box)
+    The two counts of the result cost one more copy; the output buffers have the input's sizes (upper bounds), so nothing is run
+    twice.  The same bytes on every run."""
+    cell = _decimate_cell("decimate", cell)
+    if cell == 0.0:
+        raise ValueError("decimate: a cell of 0")
+    if (origin is None) != (dims is None):
+        raise ValueError("decimate: origin and dims go together")
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    n_vertices = vertices.shape[0]
+    if n_vertices == 0:
+        return vertices, faces
+    if origin is None:
+        xyz = vertices[:, :3]
+        finite = torch.isfinite(xyz).all(1, keepdim=True)
+        inf = torch.full((), float("inf"), device=vertices.device)
+        box = torch.stack([torch.where(finite, xyz, inf).amin(0), torch.where(finite, xyz, -inf).amax(0)]).double().cpu().numpy()  # the copy
+        if not np.isfinite(box).all():
+            raise ValueError("decimate: no vertex is finite, so there is no box to lay a grid over; pass origin and dims")
+        origin = tuple(float(x) for x in box[0])
+        dims = tuple(int(np.floor((box[1, a] - box[0, a]) / cell)) + 1 for a in range(3))
+    origin, dims = tuple(float(x) for x in origin), tuple(int(d) for d in dims)
+    if len(origin) != 3 or len(dims) != 3 or not np.isfinite(origin).all() or min(dims) < 1:
+        raise ValueError(f"decimate: origin {origin!r} / dims {dims!r} are no grid")
+    if hip.mesh_decimate_workspace_bytes(n_vertices, faces.shape[0], dims) < 0:
+        raise ValueError(f"decimate: a grid of {dims} cells is too large; raise cell")
+    adjacency = hip.mesh_adjacency(faces, n_vertices)
+    vertices, faces, totals = hip.mesh_decimate(vertices, faces, adjacency, origin, cell, dims)
+    n_vertices, n_faces = (int(c) for c in totals.cpu())  # the one copy
+    return vertices[:n_vertices], faces[:n_faces]
 
 
 def vertex_normals(vertices, faces):

@@ -233,6 +233,11 @@ SIGNATURES = {
     "mnerf_tsdf_integrate": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3 + [_vp] * 3),
     "mnerf_tsdf_mesh_workspace_bytes": (_i64, [_i32] * 3),
     "mnerf_tsdf_mesh": (_int, [_vp] * 2 + [_f32] * 4 + [_i32] * 3 + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
+    # (the two rows of the decimation: the header declares them at the end of MESH FINISHING; here they stand in front of the
+    # section's first six, which tests/test_mesh_finish_cpu.py expects to be the table's last rows)
+    "mnerf_mesh_decimate_workspace_bytes": (_i64, [_i64] * 2 + [_i32] * 3),
+    "mnerf_mesh_decimate": (_int, [_vp, _P(_i32), _i64, _i64, _P(_i32), _P(_i32)] + [_f32] * 4 + [_i32] * 3
+                            + [_vp, _i64, _P(_i32), _i64, _P(_i32)] + [_vp] * 3),
     "mnerf_mesh_finish_workspace_bytes": (_i64, [_i64] * 2),
     "mnerf_mesh_adjacency": (_int, [_P(_i32), _i64, _i64, _P(_i32), _P(_i32)] + [_vp] * 3),
     "mnerf_mesh_components": (_int, [_P(_i32), _i64, _i64, _i64, C.c_double, _P(_i32)] + [_vp] * 3),
@@ -1896,3 +1901,52 @@ def mesh_normals(vertices, triangles, adjacency, out=None, stream=None):
         check(lib.mnerf_mesh_normals(_ptr(vertices), nv, _ptr_i32(triangles), nt, _ptr_i32(offsets), _ptr_i32(corners), _ptr(out), st),
               "mnerf_mesh_normals")
     return out
+
+
+DECIMATE_REG = 1.0 / 1000  # 1 / MNERF_DECIMATE_REG_INV: the regularisation weight of mesh_decimate
+
+
+def mesh_decimate_workspace_bytes(n_vertices, n_triangles, dims):
+    return int(load().mnerf_mesh_decimate_workspace_bytes(int(n_vertices), int(n_triangles), int(dims[0]), int(dims[1]), int(dims[2])))
+
+
+def mesh_decimate(vertices, triangles, adjacency, origin, cell, dims, vertices_out=None, triangles_out=None, vertex_map=None, counts=None,
+                  workspace=None, stream=None):
+    """Decimation by quadric vertex clustering (mnerf_mesh_decimate): the vertices of every cell of the grid ``origin`` (x, y, z),
+    ``cell``, ``dims`` = (gx, gy, gz) become one vertex - the regularised minimiser of the cell's plane quadric, clamped to the cell -
+    in ascending cell order, and the triangles that still join three cells are kept once each, in order.  ``adjacency`` = the tables
+    of ``mesh_adjacency`` for this mesh.  ``vertices_out`` [capacity, 8] / ``triangles_out`` [capacity, 3] default to the input's
+    sizes (upper bounds of the counts), ``vertex_map`` is an int32 [V] tensor or None (not wanted), ``counts`` a 2-element int64
+    tensor.  Enqueue only: -> (vertices_out, triangles_out, counts); rows at or beyond a capacity are not written, the counts are the
+    totals either way."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_decimate", vertices, triangles)
+    offsets = _mesh_buffer("mesh_decimate", "offsets", adjacency[0], torch.int32, nv + 1, dev)
+    corners = _mesh_buffer("mesh_decimate", "corners", adjacency[1], torch.int32, 3 * nt, dev)
+    grid = _grid(origin, cell, dims)
+    need = mesh_decimate_workspace_bytes(nv, nt, grid[4:])
+    if need < 0 or not (np.isfinite(grid[:4]).all() and grid[3] > 0):
+        raise MnerfError(f"mesh_decimate: the grid {tuple(grid[4:])} of cell {grid[3]} from {tuple(grid[:3])} is out of range")
+    if vertices_out is None:
+        vertices_out = torch.empty(nv, VERTEX_FLOATS, device=dev)
+    if triangles_out is None:
+        triangles_out = torch.empty(nt, 3, dtype=torch.int32, device=dev)
+    _mesh_args("mesh_decimate", vertices_out, triangles_out)
+    if vertices_out.device != dev:
+        raise MnerfError(f"mesh_decimate: vertices_out on {vertices_out.device}, the mesh on {dev}")
+    if vertex_map is not None:
+        vertex_map = _mesh_buffer("mesh_decimate", "vertex_map", vertex_map, torch.int32, nv, dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev) if counts is None else _mesh_buffer("mesh_decimate", "counts", counts,
+                                                                                              torch.int64, 2, dev)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
+        raise MnerfError(f"mesh_decimate: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
+                         f"{need} needed on {dev}")
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_decimate(_ptr(vertices), _ptr_i32(triangles), nv, nt, _ptr_i32(offsets), _ptr_i32(corners), *grid,
+                                      _ptr(vertices_out), vertices_out.numel() // VERTEX_FLOATS, _ptr_i32(triangles_out),
+                                      triangles_out.numel() // 3, _ptr_i32(vertex_map), _ptr(counts), _ptr(workspace), st),
+              "mnerf_mesh_decimate")
+    return vertices_out, triangles_out, counts

@@ -551,18 +551,19 @@ class MatchNeRF(torch.nn.Module):
         return clouds
 
     MESH_ARGS = ("bounds", "resolution", "voxel", "trunc", "min_weight", "consistency", "min_component", "min_component_fraction", "smooth",
-                 "smooth_lambda", "smooth_mu")
+                 "smooth_lambda", "smooth_mu", "decimate")
 
     def export_mesh(self, batch, views="sources", render_path_mode="interpolate", normals=False, **mesh_args):
         """The scene of ``batch`` as coloured triangle meshes -> a list over the batch of (vertices [V, 8] float32 rows
         ``x y z w | r g b 0``, faces [T, 3] int32) on the device (``fusion.mesh``: the depth maps of ``export_points`` fused into a
         truncated-signed-distance volume, its zero surface extracted by marching tetrahedra).  ``views`` and the one encoder pass as
         in ``export_points``; ``mesh_args``: bounds, resolution, voxel, trunc, min_weight, consistency, the clean-up of
-        ``fusion.finish`` (min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu) and the thresholds of
-        ``export_points``.  ``normals=True``: triples (vertices, faces, normals [V, 4] float32 rows ``nx ny nz a``,
+        ``fusion.finish`` (min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu), ``decimate`` (the cell of
+        ``fusion.decimate`` in voxels, applied last; 0: none) and the thresholds of ``export_points``.  ``normals=True``: triples (vertices, faces, normals [V, 4] float32 rows ``nx ny nz a``,
         ``fusion.vertex_normals`` of the finished mesh).  The same refusals, before the first launch."""
         from . import fusion
         unknown = set(mesh_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"} - set(self.MESH_ARGS)
+        fusion._decimate_cell("export_mesh", mesh_args.get("decimate", 0.0))
         maps, cams_of = self._fusion_maps("export_mesh", batch, views, render_path_mode, unknown)
         legacy = bool(self.opts.nerf.legacy_coord)
         meshes = [fusion.mesh(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, **mesh_args)

@@ -31,7 +31,8 @@ maps, ``<stem>_mesh.ply`` (TSDF fusion, marching tetrahedra): ``--nerf.mesh_reso
 ``--nerf.mesh_voxel=<world units>`` (instead of the resolution), ``--nerf.mesh_trunc=<world units>`` (4 voxels),
 ``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)).  The mesh is cleaned up by
 ``--nerf.mesh_min_component=<triangles>`` / ``--nerf.mesh_min_component_fraction=<of the largest component>`` (smaller connected
-components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, and ``--nerf.mesh_normals`` adds ``nx ny nz`` per vertex.
+components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, then reduced by ``--nerf.mesh_decimate=<cell in voxels>``
+(quadric vertex clustering: one vertex per occupied cell), and ``--nerf.mesh_normals`` adds ``nx ny nz`` per vertex.
 
     python test.py --yaml=demo_own --nerf.export_geometry=sources
     python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192"""
