@@ -3,7 +3,7 @@
 //
 // All three are memory-bound kernels of one thread per pixel, consecutive threads on consecutive pixels:
 //   depth_consistency_kernel   per pixel of the reference view and per partner: two projections, four taps, two more projections
-//   point_count / point_scan / point_total / point_scatter   wave ballots + a two-level scan of the workgroups' counts: the rows
+//   point_count / the scan (scan.hip) / point_scatter   wave ballots + a two-level scan of the workgroups' counts: the rows
 //                              come out in pixel order without an atomic cursor, so that two runs give the same bits
 //   depth_colormap_kernel      one load, three byte stores
 // The cameras travel by value in the kernel arguments (as mnerf_scene's views do): 16 x 44 floats.
@@ -14,7 +14,7 @@
 // every operation rounds on its own; the FMAs are the explicit ones of the helpers (common.hpp)
 #pragma clang fp contract(off)
 
-#include "fusion_common.hpp"  // FusionCam, the projection chain, fusion_value, the workgroup scans (shared with mesh.hip)
+#include "fusion_common.hpp"  // FusionCam, the projection chain, fusion_value, the scan and the workspace carve
 
 __global__ __launch_bounds__(256) void depth_consistency_kernel(FusionCams cams, int n_views, int ref, int height, int width,
                                                                 int legacy_coord, const float* __restrict__ depth,
@@ -97,8 +97,7 @@ extern "C" int mnerf_depth_consistency(const mnerf_view* views, int32_t n_views,
 }
 
 // ------------------------------------------------------------------------------------------------ point cloud
-// Workspace: int32 counts[n_blocks] (after point_scan_kernel: the exclusive prefix inside the block's tile) | int32 tiles[n_tiles]
-// (the tiles' totals, after point_total_kernel their exclusive prefix).  Every prefix is below 2^31 (height x width is).
+// Workspace: the scratch of one scan over the pixels.  Every prefix is below 2^31 (height x width is).
 
 __device__ __forceinline__ bool point_selected(const float* __restrict__ depth, const int* __restrict__ n_consistent,
                                                int min_consistent, long long i, long long n) {
@@ -116,41 +115,6 @@ __global__ __launch_bounds__(PC_BLOCK) void point_count_kernel(const float* __re
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(PC_BLOCK) void point_scan_kernel(int* __restrict__ counts, int n_blocks, int* __restrict__ tiles) {
-  const long long first = (long long)blockIdx.x * PC_TILE + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = first + k < n_blocks ? counts[first + k] : 0;
-  int total;
-  int p = tile_scan(v, total);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (first + k < n_blocks) counts[first + k] = p;
-    p += v[k];
-  }
-  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive scan of the tile totals (rounds of PC_TILE with a carried sum) and the grand total
-__global__ __launch_bounds__(PC_BLOCK) void point_total_kernel(int* __restrict__ tiles, int n_tiles, long long* __restrict__ count) {
-  int carry = 0;
-  for (int begin = 0; begin < n_tiles; begin += PC_TILE) {
-    const int first = begin + threadIdx.x * 4;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = first + k < n_tiles ? tiles[first + k] : 0;
-    int total;
-    int p = carry + tile_scan(v, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (first + k < n_tiles) tiles[first + k] = p;
-      p += v[k];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *count = (long long)carry;
-}
-
 __global__ __launch_bounds__(PC_BLOCK) void point_scatter_kernel(FusionCam cam, int width, int legacy_coord,
                                                                  const float* __restrict__ depth, const float* __restrict__ rgb,
                                                                  const int* __restrict__ n_consistent, int min_consistent, long long n,
@@ -161,7 +125,7 @@ __global__ __launch_bounds__(PC_BLOCK) void point_scatter_kernel(FusionCam cam, 
   int total;
   const int before = block_prefix(flag, total);
   if (!flag) return;
-  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  const long long row = scan_row(counts, tiles, before);
   if (row >= capacity) return;
   const int py = (int)(i / width), px = (int)(i - (long long)py * width);
   const float off = legacy_coord ? 0.0f : 0.5f;
@@ -175,9 +139,9 @@ __global__ __launch_bounds__(PC_BLOCK) void point_scatter_kernel(FusionCam cam, 
 
 extern "C" int64_t mnerf_point_cloud_workspace_bytes(int64_t n_pixels) {
   if (n_pixels < 0) return -1;
-  const int64_t n_blocks = n_pixels / PC_BLOCK + (n_pixels % PC_BLOCK != 0);
-  const int64_t n_tiles = n_blocks / PC_TILE + (n_blocks % PC_TILE != 0);
-  return ((n_blocks + n_tiles) * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;
+  Carve sizes(nullptr);
+  sizes.scan(n_pixels);
+  return sizes.bytes();
 }
 
 extern "C" int mnerf_point_cloud(const mnerf_view* view, int32_t height, int32_t width, int32_t legacy_coord, const float* depth,
@@ -197,16 +161,13 @@ extern "C" int mnerf_point_cloud(const mnerf_view* view, int32_t height, int32_t
                 "mnerf_point_cloud: workspace / count not aligned to 4 / 8 bytes");
   FusionCam cam;
   MNERF_REQUIRE(fusion_cam(*view, &cam), MNERF_E_RANGE, "mnerf_point_cloud: the view has a singular intr or extr");
-  const int n_blocks = (int)((n + PC_BLOCK - 1) / PC_BLOCK);
-  const int n_tiles = (n_blocks + PC_TILE - 1) / PC_TILE;
-  int* counts = static_cast<int*>(workspace);
-  int* tiles = counts + n_blocks;
+  const ScanScratch s = Carve(workspace).scan(n);
+  const dim3 blocks((unsigned)s.blocks), threads(PC_BLOCK);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(point_count_kernel, dim3((unsigned)n_blocks), dim3(PC_BLOCK), 0, st, depth, n_consistent, min_consistent, n, counts);
-  hipLaunchKernelGGL(point_scan_kernel, dim3((unsigned)n_tiles), dim3(PC_BLOCK), 0, st, counts, n_blocks, tiles);
-  hipLaunchKernelGGL(point_total_kernel, dim3(1), dim3(PC_BLOCK), 0, st, tiles, n_tiles, reinterpret_cast<long long*>(count));
-  hipLaunchKernelGGL(point_scatter_kernel, dim3((unsigned)n_blocks), dim3(PC_BLOCK), 0, st, cam, width, legacy_coord ? 1 : 0, depth, rgb,
-                     n_consistent, min_consistent, n, counts, tiles, points, (long long)capacity);
+  hipLaunchKernelGGL(point_count_kernel, blocks, threads, 0, st, depth, n_consistent, min_consistent, n, s.counts);
+  scan_enqueue(s, reinterpret_cast<long long*>(count), st);
+  hipLaunchKernelGGL(point_scatter_kernel, blocks, threads, 0, st, cam, width, legacy_coord ? 1 : 0, depth, rgb, n_consistent,
+                     min_consistent, n, s.counts, s.tiles, points, (long long)capacity);
   return mnerf_check_launch("mnerf_point_cloud");
 }
 

@@ -1,7 +1,8 @@
-// What the geometry-export kernels share (fusion.hip: consistency, point cloud; mesh.hip: TSDF volume, mesher): the camera with its
-// host-inverted matrices, the fp32 projection chain, the value of a depth texel, and the integer workgroup scans of the stable
-// compactions.  Include after common.hpp, under `#pragma clang fp contract(off)`: every operation rounds on its own and the FMAs
-// are the explicit ones of the helpers.
+// What the geometry-export kernels share (fusion.hip: consistency, point cloud; mesh.hip: TSDF volume, mesher; mesh_finish.hip:
+// finishing, decimation): the camera with its host-inverted matrices, the fp32 projection chain, the value of a depth texel, the
+// integer workgroup scans of the stable compactions with the two-level scan over them (scan.hip), and the carving of a workspace.
+// Include after common.hpp, under `#pragma clang fp contract(off)`: every operation rounds on its own and the FMAs are the explicit
+// ones of the helpers.
 #pragma once
 #include <math.h>
 
@@ -132,3 +133,54 @@ __device__ __forceinline__ int tile_scan(const int v[4], int& total) {
   }
   return base + incl - mine;
 }
+
+// ------------------------------------------------------------------------------------------------ the two-level scan (scan.hip)
+// A count kernel leaves one int32 per workgroup of PC_BLOCK elements in `counts`.  scan_enqueue turns every count into the exclusive
+// prefix inside its tile of PC_TILE workgroups, `tiles` into the tiles' exclusive prefixes, and writes the grand total - two
+// launches, or the second alone over an empty range (the total, 0, is written all the same; nothing with an empty grid is launched).
+// A scatter kernel of the same grid then places its workgroup's elements from scan_row.  Every prefix is below 2^31 (the entry
+// points bound their sizes so), hence the int32 tables.
+struct ScanScratch {  // int32 [blocks] | int32 [n_tiles], one after the other in a workspace
+  int *counts, *tiles;
+  long long blocks, n_tiles;
+};
+static inline long long scan_blocks(long long n) { return n / PC_BLOCK + (n % PC_BLOCK != 0); }  // (no n + 255: any int64 n >= 0)
+static inline long long scan_tiles(long long n) { return (scan_blocks(n) + PC_TILE - 1) / PC_TILE; }
+
+void scan_enqueue(const ScanScratch& s, long long* total, hipStream_t st);
+// the same over values[n], one per thread, that no count kernel has summed: the workgroups' sums first (three launches)
+void scan_values_enqueue(const int* values, int n, const ScanScratch& s, long long* total, hipStream_t st);
+// The offsets of a CSR table from its rows' lengths: offsets[0 .. n) hold the counts and become their exclusive prefixes,
+// offsets[n] = the total (also in *total), cursor[0 .. n) = a copy for a fill that advances it; n >= 1.  scan_values_enqueue plus
+// one launch.
+void csr_offsets_enqueue(int* offsets, int n, const ScanScratch& s, long long* total, int* cursor, hipStream_t st);
+
+// the output row of a workgroup's element that has `before` selected elements of the same workgroup in front of it
+__device__ __forceinline__ long long scan_row(const int* __restrict__ counts, const int* __restrict__ tiles, int before) {
+  return (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+}
+
+// ------------------------------------------------------------------------------------------------ host: carving a workspace
+// A layout is a list of requests: each returns its array at the running offset rounded up to the alignment.  With a null base only
+// the offsets and the total mean anything - that is how the *_workspace_bytes functions size what the entry points carve.
+struct Carve {
+  char* base;
+  size_t at = 0;
+  explicit Carve(void* workspace) : base(static_cast<char*>(workspace)) {}
+  size_t take(size_t bytes, size_t alignment) {
+    const size_t offset = (at + alignment - 1) & ~(alignment - 1);
+    at = offset + bytes;
+    return offset;
+  }
+  template <typename T>
+  T* array(size_t count, size_t alignment = alignof(T)) {
+    return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + take(count * sizeof(T), alignment));
+  }
+  ScanScratch scan(long long n) {  // the scratch of one scan over n elements, a single request
+    ScanScratch s;
+    s.blocks = scan_blocks(n), s.n_tiles = scan_tiles(n);
+    s.counts = array<int>((size_t)s.blocks), s.tiles = array<int>((size_t)s.n_tiles);
+    return s;
+  }
+  long long bytes() const { return (long long)((at + 15) & ~(size_t)15); }  // the total: a multiple of 16
+};

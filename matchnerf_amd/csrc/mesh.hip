@@ -4,9 +4,9 @@
 // Memory-bound kernels of one thread per voxel / lattice point, x fastest, 256 threads per workgroup:
 //   tsdf_integrate_kernel   per voxel and view: one projection, one texel, a read-modify-write of five floats
 //   mesh_flags_kernel       per lattice point: valid | inside | "the cell I am the origin of is valid", one byte
-//   mesh_vcount / mesh_scan / mesh_total / mesh_vscatter   the 7-bit mask of live owned edges, the two-level scan of the
+//   mesh_vcount / the scan (scan.hip) / mesh_vscatter   the 7-bit mask of live owned edges, the two-level scan of the
 //                           workgroups' counts, each point's vertex base, the vertex rows
-//   mesh_tcount / mesh_scan / mesh_total / mesh_tscatter   the same over cells for the triangles
+//   mesh_tcount / the scan / mesh_tscatter   the same over cells for the triangles
 // No atomics anywhere: vertices and triangles come out in a defined order and two runs give the same bits.
 #include <math.h>
 
@@ -229,41 +229,6 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_vcount_kernel(const unsigned ch
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
-// the point cloud's two scans (fusion.hip) with the grand total into one slot of counts
-__global__ __launch_bounds__(PC_BLOCK) void mesh_scan_kernel(int* __restrict__ counts, int n_blocks, int* __restrict__ tiles) {
-  const long long first = (long long)blockIdx.x * PC_TILE + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = first + k < n_blocks ? counts[first + k] : 0;
-  int total;
-  int p = tile_scan(v, total);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (first + k < n_blocks) counts[first + k] = p;
-    p += v[k];
-  }
-  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(PC_BLOCK) void mesh_total_kernel(int* __restrict__ tiles, int n_tiles, long long* __restrict__ count) {
-  int carry = 0;
-  for (int begin = 0; begin < n_tiles; begin += PC_TILE) {
-    const int first = begin + threadIdx.x * 4;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = first + k < n_tiles ? tiles[first + k] : 0;
-    int total;
-    int p = carry + tile_scan(v, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (first + k < n_tiles) tiles[first + k] = p;
-      p += v[k];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *count = (long long)carry;
-}
-
 __global__ __launch_bounds__(PC_BLOCK) void mesh_vscatter_kernel(const float* __restrict__ sums, const float* __restrict__ weight,
                                                                  TsdfGrid g, const unsigned char* __restrict__ masks,
                                                                  const int* __restrict__ counts, const int* __restrict__ tiles,
@@ -276,7 +241,7 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_vscatter_kernel(const float* __
   int total;
   const int before = tile_scan(v, total);
   if (i >= n) return;
-  long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  long long row = scan_row(counts, tiles, before);
   vbase[i] = (int)row;
   if (!mask) return;
   const int ix = (int)(i % g.nx), iy = (int)((i / g.nx) % g.ny), iz = (int)(i / ((long long)g.nx * g.ny));
@@ -319,17 +284,29 @@ __device__ __forceinline__ int tet_code(int cell, int t) {
          (cell >> tet_corner(t, 3) & 1) << 3;
 }
 
+// the table rows of the six tets of the cell at i (0: the tet emits nothing); returns the triangles the cell emits, their counts' sum
+__device__ __forceinline__ int cell_triangles(const unsigned char* __restrict__ flags, long long i, long long n, int nx, int ny,
+                                              int rows[6]) {
+  const int cell = cell_code(flags, i, n, nx, ny);
+  int mine = 0;
+#pragma unroll
+  for (int t = 0; t < 6; ++t) rows[t] = 0;
+  if (cell > 0 && cell < 255) {  // (a branch, not six selects: most cells are empty or full, and whole waves skip the table)
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      rows[t] = (int)TET_TABLE.row[tet_code(cell, t)];
+      mine += rows[t] & 3;
+    }
+  }
+  return mine;
+}
+
 __global__ __launch_bounds__(PC_BLOCK) void mesh_tcount_kernel(const unsigned char* __restrict__ flags, int nx, int ny, int nz,
                                                                int* __restrict__ counts) {
   const long long n = (long long)nx * ny * nz;
   const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
-  const int cell = cell_code(flags, i, n, nx, ny);
-  int mine = 0;
-  if (cell > 0 && cell < 255) {
-#pragma unroll
-    for (int t = 0; t < 6; ++t) mine += (int)(TET_TABLE.row[tet_code(cell, t)] & 3u);
-  }
-  const int v[4] = {mine, 0, 0, 0};
+  int rows[6];
+  const int v[4] = {cell_triangles(flags, i, n, nx, ny, rows), 0, 0, 0};
   int total;
   tile_scan(v, total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
@@ -342,18 +319,13 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_tscatter_kernel(const unsigned 
                                                                  long long capacity) {
   const long long n = (long long)nx * ny * nz;
   const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
-  const int cell = cell_code(flags, i, n, nx, ny);
-  int rows[6], mine = 0;
-#pragma unroll
-  for (int t = 0; t < 6; ++t) {
-    rows[t] = cell > 0 && cell < 255 ? (int)TET_TABLE.row[tet_code(cell, t)] : 0;
-    mine += rows[t] & 3;
-  }
+  int rows[6];
+  const int mine = cell_triangles(flags, i, n, nx, ny, rows);
   const int v[4] = {mine, 0, 0, 0};
   int total;
   const int before = tile_scan(v, total);
   if (!mine) return;
-  long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  long long row = scan_row(counts, tiles, before);
 #pragma unroll
   for (int t = 0; t < 6; ++t) {
     const int n_tri = rows[t] & 3;
@@ -386,22 +358,20 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_tscatter_kernel(const unsigned 
 constexpr long long MESH_MAX_POINTS = ((1ll << 31) - 1) / 12;
 
 struct MeshWorkspace {
-  long long n, n_blocks, n_tiles, bytes;
-  size_t vbase, vcounts, vtiles, tcounts, ttiles, flags, masks;  // byte offsets
+  long long bytes;
+  int* vbase;                   // int32 [n]: the first vertex row of every lattice point
+  ScanScratch vscan, tscan;     // the scans over the points' vertices and the cells' triangles
+  unsigned char *flags, *masks;  // uint8 [n] each
 };
-static MeshWorkspace mesh_workspace(long long n) {
-  MeshWorkspace w = {};
-  w.n = n;
-  w.n_blocks = (n + PC_BLOCK - 1) / PC_BLOCK;
-  w.n_tiles = (w.n_blocks + PC_TILE - 1) / PC_TILE;
-  w.vbase = 0;
-  w.vcounts = w.vbase + 4 * (size_t)n;
-  w.vtiles = w.vcounts + 4 * (size_t)w.n_blocks;
-  w.tcounts = w.vtiles + 4 * (size_t)w.n_tiles;
-  w.ttiles = w.tcounts + 4 * (size_t)w.n_blocks;
-  w.flags = w.ttiles + 4 * (size_t)w.n_tiles;
-  w.masks = w.flags + (size_t)n;
-  w.bytes = (long long)((w.masks + (size_t)n + 15) & ~(size_t)15);
+static MeshWorkspace mesh_workspace(void* workspace, long long n) {
+  Carve c(workspace);
+  MeshWorkspace w;
+  w.vbase = c.array<int>((size_t)n);
+  w.vscan = c.scan(n);
+  w.tscan = c.scan(n);
+  w.flags = c.array<unsigned char>((size_t)n);
+  w.masks = c.array<unsigned char>((size_t)n);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -409,7 +379,7 @@ extern "C" int64_t mnerf_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32
   if (nx < 0 || ny < 0 || nz < 0) return -1;
   const double n = (double)nx * (double)ny * (double)nz;
   if (n > (double)MESH_MAX_POINTS) return -1;
-  return mesh_workspace((long long)nx * ny * nz).bytes;
+  return mesh_workspace(nullptr, (long long)nx * ny * nz).bytes;
 }
 
 extern "C" int mnerf_tsdf_mesh(const float* sums, const float* weight, float origin_x, float origin_y, float origin_z, float voxel,
@@ -433,30 +403,20 @@ extern "C" int mnerf_tsdf_mesh(const float* sums, const float* weight, float ori
   MNERF_REQUIRE((((uintptr_t)weight) & 3u) == 0 && (((uintptr_t)triangles) & 3u) == 0 && (((uintptr_t)workspace) & 3u) == 0 &&
                     (((uintptr_t)counts) & 7u) == 0,
                 MNERF_E_ALIGN, "mnerf_tsdf_mesh: weight / triangles / workspace / counts not aligned to 4 / 4 / 4 / 8 bytes");
-  const MeshWorkspace w = mesh_workspace(n);
-  char* base = static_cast<char*>(workspace);
-  int* vbase = reinterpret_cast<int*>(base + w.vbase);
-  int* vcounts = reinterpret_cast<int*>(base + w.vcounts);
-  int* vtiles = reinterpret_cast<int*>(base + w.vtiles);
-  int* tcounts = reinterpret_cast<int*>(base + w.tcounts);
-  int* ttiles = reinterpret_cast<int*>(base + w.ttiles);
-  unsigned char* flags = reinterpret_cast<unsigned char*>(base + w.flags);
-  unsigned char* masks = reinterpret_cast<unsigned char*>(base + w.masks);
+  const MeshWorkspace w = mesh_workspace(workspace, n);
   long long* count = reinterpret_cast<long long*>(counts);
   const TsdfGrid g = {origin_x, origin_y, origin_z, voxel, nx, ny, nz};
-  const dim3 blocks((unsigned)w.n_blocks), tiles((unsigned)w.n_tiles), one(1), threads(PC_BLOCK);
+  const dim3 blocks((unsigned)w.vscan.blocks), threads(PC_BLOCK);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mesh_flags_kernel, blocks, threads, 0, st, sums, weight, min_weight, nx, ny, nz, flags);
-  hipLaunchKernelGGL(mesh_vcount_kernel, blocks, threads, 0, st, flags, nx, ny, nz, masks, vcounts);
-  hipLaunchKernelGGL(mesh_scan_kernel, tiles, threads, 0, st, vcounts, (int)w.n_blocks, vtiles);
-  hipLaunchKernelGGL(mesh_total_kernel, one, threads, 0, st, vtiles, (int)w.n_tiles, count);
-  hipLaunchKernelGGL(mesh_vscatter_kernel, blocks, threads, 0, st, sums, weight, g, masks, vcounts, vtiles, vbase, vertices,
-                     (long long)vertex_capacity);
-  hipLaunchKernelGGL(mesh_tcount_kernel, blocks, threads, 0, st, flags, nx, ny, nz, tcounts);
-  hipLaunchKernelGGL(mesh_scan_kernel, tiles, threads, 0, st, tcounts, (int)w.n_blocks, ttiles);
-  hipLaunchKernelGGL(mesh_total_kernel, one, threads, 0, st, ttiles, (int)w.n_tiles, count + 1);
-  hipLaunchKernelGGL(mesh_tscatter_kernel, blocks, threads, 0, st, flags, masks, vbase, nx, ny, nz, tcounts, ttiles, triangles,
-                     (long long)triangle_capacity);
+  hipLaunchKernelGGL(mesh_flags_kernel, blocks, threads, 0, st, sums, weight, min_weight, nx, ny, nz, w.flags);
+  hipLaunchKernelGGL(mesh_vcount_kernel, blocks, threads, 0, st, w.flags, nx, ny, nz, w.masks, w.vscan.counts);
+  scan_enqueue(w.vscan, count, st);
+  hipLaunchKernelGGL(mesh_vscatter_kernel, blocks, threads, 0, st, sums, weight, g, w.masks, w.vscan.counts, w.vscan.tiles, w.vbase,
+                     vertices, (long long)vertex_capacity);
+  hipLaunchKernelGGL(mesh_tcount_kernel, blocks, threads, 0, st, w.flags, nx, ny, nz, w.tscan.counts);
+  scan_enqueue(w.tscan, count + 1, st);
+  hipLaunchKernelGGL(mesh_tscatter_kernel, blocks, threads, 0, st, w.flags, w.masks, w.vbase, nx, ny, nz, w.tscan.counts, w.tscan.tiles,
+                     triangles, (long long)triangle_capacity);
   return mnerf_check_launch("mnerf_tsdf_mesh");
 }
 #pragma clang fp contract(fast)

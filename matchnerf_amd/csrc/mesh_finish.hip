@@ -3,12 +3,12 @@
 // ones, Taubin smoothing of the positions, area-weighted vertex normals.
 //
 // Memory-bound streaming and gather kernels of one thread per vertex or per triangle, 256 threads per workgroup:
-//   adj_count / finish_blocksum / finish_scan / finish_total / adj_offsets / adj_fill / adj_sort_class
-//                           corners per vertex, the two-level scan of mesh.hip over them, the rows filled through a cursor, every
-//                           row sorted by its own thread and classified
+//   adj_zero / adj_count / the CSR offsets (scan.hip) / adj_fill / adj_sort_class
+//                           corners per vertex, the two-level scan over them, the rows filled through a cursor, every row sorted
+//                           by its own thread and classified
 //   cc_init / cc_union / cc_flatten / cc_count / cc_largest / cc_keep
 //                           a lock-free union-find over the triangles' edges, triangles per component, the keep bytes
-//   compact_count / finish_scan / finish_total / compact_vertices / compact_triangles   the mesher's stable scan and scatter
+//   compact_vcount / compact_tcount / the scan / compact_vertices / compact_triangles   the mesher's stable scan and scatter
 //   smooth_step             one Jacobi step of the umbrella operator, ping-pong through the workspace
 //   normals                 the corner sum of the triangles' cross products
 //   dec_*                   decimation by quadric vertex clustering (section 6 below)
@@ -33,61 +33,6 @@ constexpr unsigned char VC_BOUNDARY = 0, VC_INTERIOR = 1;
 
 __device__ __forceinline__ bool in_range(int v, int n) { return (unsigned int)v < (unsigned int)n; }
 
-// ------------------------------------------------------------------------------------------------ the two-level scan
-// values[n], one per thread -> the workgroups' totals
-__global__ __launch_bounds__(PC_BLOCK) void finish_blocksum_kernel(const int* __restrict__ values, int n, int* __restrict__ counts) {
-  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
-  const int v[4] = {i < n ? values[i] : 0, 0, 0, 0};
-  int total;
-  tile_scan(v, total);
-  if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-// the mesher's two scans (mesh.hip): the workgroups' counts in tiles of 1024, then the tiles' totals and the grand total
-__global__ __launch_bounds__(PC_BLOCK) void finish_scan_kernel(int* __restrict__ counts, int n_blocks, int* __restrict__ tiles) {
-  const long long first = (long long)blockIdx.x * PC_TILE + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = first + k < n_blocks ? counts[first + k] : 0;
-  int total;
-  int p = tile_scan(v, total);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (first + k < n_blocks) counts[first + k] = p;
-    p += v[k];
-  }
-  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(PC_BLOCK) void finish_total_kernel(int* __restrict__ tiles, int n_tiles, long long* __restrict__ count) {
-  int carry = 0;
-  for (int begin = 0; begin < n_tiles; begin += PC_TILE) {
-    const int first = begin + threadIdx.x * 4;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = first + k < n_tiles ? tiles[first + k] : 0;
-    int total;
-    int p = carry + tile_scan(v, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (first + k < n_tiles) tiles[first + k] = p;
-      p += v[k];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *count = (long long)carry;
-}
-
-struct FinishScan {  // the scratch of one scan over n elements: int32 [blocks] | int32 [tiles]
-  long long blocks, tiles;
-};
-static FinishScan finish_scan(long long n) {
-  FinishScan s;
-  s.blocks = (n + PC_BLOCK - 1) / PC_BLOCK;
-  s.tiles = (s.blocks + PC_TILE - 1) / PC_TILE;
-  return s;
-}
-
 // ------------------------------------------------------------------------------------------------ 1. adjacency
 __global__ __launch_bounds__(PC_BLOCK) void adj_zero_kernel(int* __restrict__ offsets, int n_vertices) {
   const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
@@ -100,21 +45,6 @@ __global__ __launch_bounds__(PC_BLOCK) void adj_count_kernel(const int* __restri
   if (c >= n_corners) return;
   const int v = triangles[c];
   if (in_range(v, n_vertices)) atomicAdd(&offsets[v], 1);
-}
-
-// offsets[v]: the count -> the exclusive prefix; cursor[v] = the same; offsets[V] = the total
-__global__ __launch_bounds__(PC_BLOCK) void adj_offsets_kernel(int* __restrict__ offsets, int n_vertices, const int* __restrict__ counts,
-                                                               const int* __restrict__ tiles, int* __restrict__ cursor) {
-  const long long i = (long long)blockIdx.x * PC_BLOCK + threadIdx.x;
-  const int mine = i < n_vertices ? offsets[i] : 0;
-  const int v[4] = {mine, 0, 0, 0};
-  int total;
-  const int before = tile_scan(v, total);
-  if (i >= n_vertices) return;
-  const int first = tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
-  offsets[i] = first;
-  cursor[i] = first;
-  if (i == n_vertices - 1) offsets[n_vertices] = first + mine;
 }
 
 __global__ __launch_bounds__(PC_BLOCK) void adj_fill_kernel(const int* __restrict__ triangles, long long n_corners, int n_vertices,
@@ -170,26 +100,22 @@ __global__ __launch_bounds__(PC_BLOCK) void adj_sort_class_kernel(const int* __r
 
 struct FinishWorkspace {
   long long bytes;
-  size_t head;                                  // int64 [2]: totals of the scans / the largest component
-  size_t per_vertex, vcounts, vtiles, tcounts, ttiles;  // int32 [V] | [Bv] | [Tv] | [Bt] | [Tt]   (adjacency, components, compact)
-  size_t ping;                                  // fp32 [V][8], 16-byte aligned (smooth) - shares the bytes of the above
-  FinishScan sv, st;
+  long long* head;   // int64 [2]: totals of the scans / the largest component
+  int* per_vertex;   // int32 [V]   (adjacency, components, compact)
+  ScanScratch sv, st;  // the scans over the vertices and over the triangles
+  float* ping;       // fp32 [V][8], 16-byte aligned (smooth) - shares the bytes of the integer tables after the head
 };
-static FinishWorkspace finish_workspace(long long n_vertices, long long n_triangles) {
+static FinishWorkspace finish_workspace(void* workspace, long long n_vertices, long long n_triangles) {
   FinishWorkspace w = {};
   if (n_vertices == 0) return w;
-  w.sv = finish_scan(n_vertices);
-  w.st = finish_scan(n_triangles);
-  w.head = 0;
-  w.per_vertex = 16;
-  w.vcounts = w.per_vertex + 4 * (size_t)n_vertices;
-  w.vtiles = w.vcounts + 4 * (size_t)w.sv.blocks;
-  w.tcounts = w.vtiles + 4 * (size_t)w.sv.tiles;
-  w.ttiles = w.tcounts + 4 * (size_t)w.st.blocks;
-  const size_t integers = w.ttiles + 4 * (size_t)w.st.tiles;
-  w.ping = 16;
-  const size_t floats = w.ping + 32 * (size_t)n_vertices;
-  w.bytes = (long long)(((integers > floats ? integers : floats) + 15) & ~(size_t)15);
+  Carve integers(workspace), floats(workspace);
+  w.head = integers.array<long long>(2);
+  w.per_vertex = integers.array<int>((size_t)n_vertices);
+  w.sv = integers.scan(n_vertices);
+  w.st = integers.scan(n_triangles);
+  floats.array<long long>(2);
+  w.ping = floats.array<float>(8 * (size_t)n_vertices, 16);
+  w.bytes = integers.bytes() > floats.bytes() ? integers.bytes() : floats.bytes();
   return w;
 }
 
@@ -199,7 +125,7 @@ static bool finish_sizes_ok(int64_t n_vertices, int64_t n_triangles) {
 
 extern "C" int64_t mnerf_mesh_finish_workspace_bytes(int64_t n_vertices, int64_t n_triangles) {
   if (!finish_sizes_ok(n_vertices, n_triangles)) return -1;
-  return finish_workspace(n_vertices, n_triangles).bytes;
+  return finish_workspace(nullptr, n_vertices, n_triangles).bytes;
 }
 
 static inline bool aligned_to(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
@@ -215,22 +141,15 @@ extern "C" int mnerf_mesh_adjacency(const int32_t* triangles, int64_t n_vertices
   MNERF_REQUIRE(aligned_to(triangles, 4) && aligned_to(offsets, 4) && aligned_to(corners, 4), MNERF_E_ALIGN,
                 "mnerf_mesh_adjacency: triangles / offsets / corners not 4B aligned");
   MNERF_REQUIRE(mnerf_aligned16(workspace), MNERF_E_ALIGN, "mnerf_mesh_adjacency: workspace not 16B aligned");
-  const FinishWorkspace w = finish_workspace(n_vertices, n_triangles);
-  char* base = static_cast<char*>(workspace);
-  long long* total = reinterpret_cast<long long*>(base + w.head);
-  int* cursor = reinterpret_cast<int*>(base + w.per_vertex);
-  int* vcounts = reinterpret_cast<int*>(base + w.vcounts);
-  int* vtiles = reinterpret_cast<int*>(base + w.vtiles);
+  const FinishWorkspace w = finish_workspace(workspace, n_vertices, n_triangles);
+  int* cursor = w.per_vertex;
   const int nv = (int)n_vertices;
   const long long n_corners = 3 * (long long)n_triangles;
   const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices)), cblocks(blocks_of(n_corners));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_vertices + 1)), threads, 0, st, offsets, nv);
   if (n_corners) hipLaunchKernelGGL(adj_count_kernel, cblocks, threads, 0, st, triangles, n_corners, nv, offsets);
-  hipLaunchKernelGGL(finish_blocksum_kernel, vblocks, threads, 0, st, offsets, nv, vcounts);
-  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sv.tiles), threads, 0, st, vcounts, (int)w.sv.blocks, vtiles);
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, vtiles, (int)w.sv.tiles, total);
-  hipLaunchKernelGGL(adj_offsets_kernel, vblocks, threads, 0, st, offsets, nv, vcounts, vtiles, cursor);
+  csr_offsets_enqueue(offsets, nv, w.sv, w.head, cursor, st);
   if (n_corners) hipLaunchKernelGGL(adj_fill_kernel, cblocks, threads, 0, st, triangles, n_corners, nv, cursor, corners);
   hipLaunchKernelGGL(adj_sort_class_kernel, vblocks, threads, 0, st, triangles, offsets, nv, corners, vertex_class);
   return mnerf_check_launch("mnerf_mesh_adjacency");
@@ -338,10 +257,9 @@ extern "C" int mnerf_mesh_components(const int32_t* triangles, int64_t n_vertice
   MNERF_REQUIRE(n_triangles == 0 || triangles, MNERF_E_NULL, "mnerf_mesh_components: triangles is NULL");
   MNERF_REQUIRE(aligned_to(triangles, 4) && aligned_to(labels, 4), MNERF_E_ALIGN, "mnerf_mesh_components: triangles / labels not 4B aligned");
   MNERF_REQUIRE(mnerf_aligned16(workspace), MNERF_E_ALIGN, "mnerf_mesh_components: workspace not 16B aligned");
-  const FinishWorkspace w = finish_workspace(n_vertices, n_triangles);
-  char* base = static_cast<char*>(workspace);
-  int* largest = reinterpret_cast<int*>(base + w.head);
-  int* tri_count = reinterpret_cast<int*>(base + w.per_vertex);
+  const FinishWorkspace w = finish_workspace(workspace, n_vertices, n_triangles);
+  int* largest = reinterpret_cast<int*>(w.head);
+  int* tri_count = w.per_vertex;
   const int nv = (int)n_vertices;
   const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices)), tblocks(blocks_of(n_triangles));
   hipStream_t st = (hipStream_t)stream;
@@ -385,7 +303,7 @@ __global__ __launch_bounds__(PC_BLOCK) void compact_vertices_kernel(const float*
   int total;
   const int before = block_prefix(kept, total);
   if (i >= n_vertices) return;
-  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  const long long row = scan_row(counts, tiles, before);
   new_row[i] = kept ? (int)row : -1;
   if (!kept || row >= capacity) return;
   const float4* src = reinterpret_cast<const float4*>(vertices) + (size_t)i * 2;
@@ -404,7 +322,7 @@ __global__ __launch_bounds__(PC_BLOCK) void compact_triangles_kernel(const int* 
   const bool kept = triangle_kept(triangles, t, n_triangles, n_vertices, keep, a, b, c);
   const int before = block_prefix(kept, total);
   if (!kept) return;
-  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  const long long row = scan_row(counts, tiles, before);
   if (row >= capacity) return;
   out[row * 3 + 0] = new_row[a];
   out[row * 3 + 1] = new_row[b];
@@ -427,31 +345,22 @@ extern "C" int mnerf_mesh_compact(const float* vertices, const int32_t* triangle
                 "mnerf_mesh_compact: vertices / vertices_out / workspace not 16B aligned");
   MNERF_REQUIRE(aligned_to(triangles, 4) && aligned_to(triangles_out, 4) && aligned_to(counts, 8), MNERF_E_ALIGN,
                 "mnerf_mesh_compact: triangles / triangles_out / counts not aligned to 4 / 4 / 8 bytes");
-  const FinishWorkspace w = finish_workspace(n_vertices, n_triangles);
-  char* base = static_cast<char*>(workspace);
-  int* new_row = reinterpret_cast<int*>(base + w.per_vertex);
-  int* vcounts = reinterpret_cast<int*>(base + w.vcounts);
-  int* vtiles = reinterpret_cast<int*>(base + w.vtiles);
-  int* tcounts = reinterpret_cast<int*>(base + w.tcounts);
-  int* ttiles = reinterpret_cast<int*>(base + w.ttiles);
+  const FinishWorkspace w = finish_workspace(workspace, n_vertices, n_triangles);
+  int* new_row = w.per_vertex;
   long long* count = reinterpret_cast<long long*>(counts);
   const int nv = (int)n_vertices;
   const long long nt = (long long)n_triangles;
   const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices)), tblocks(blocks_of(n_triangles));
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(compact_vcount_kernel, vblocks, threads, 0, st, keep, nv, vcounts);
-  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sv.tiles), threads, 0, st, vcounts, (int)w.sv.blocks, vtiles);
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, vtiles, (int)w.sv.tiles, count);
-  hipLaunchKernelGGL(compact_vertices_kernel, vblocks, threads, 0, st, vertices, keep, nv, vcounts, vtiles, new_row, vertices_out,
+  hipLaunchKernelGGL(compact_vcount_kernel, vblocks, threads, 0, st, keep, nv, w.sv.counts);
+  scan_enqueue(w.sv, count, st);
+  hipLaunchKernelGGL(compact_vertices_kernel, vblocks, threads, 0, st, vertices, keep, nv, w.sv.counts, w.sv.tiles, new_row, vertices_out,
                      (long long)vertex_capacity);
-  if (nt) {
-    hipLaunchKernelGGL(compact_tcount_kernel, tblocks, threads, 0, st, triangles, nt, nv, keep, tcounts);
-    hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.st.tiles), threads, 0, st, tcounts, (int)w.st.blocks, ttiles);
-  }
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ttiles, (int)w.st.tiles, count + 1);
+  if (nt) hipLaunchKernelGGL(compact_tcount_kernel, tblocks, threads, 0, st, triangles, nt, nv, keep, w.st.counts);
+  scan_enqueue(w.st, count + 1, st);  // (no triangle: the total, 0, alone)
   if (nt)
-    hipLaunchKernelGGL(compact_triangles_kernel, tblocks, threads, 0, st, triangles, nt, nv, keep, new_row, tcounts, ttiles, triangles_out,
-                       (long long)triangle_capacity);
+    hipLaunchKernelGGL(compact_triangles_kernel, tblocks, threads, 0, st, triangles, nt, nv, keep, new_row, w.st.counts, w.st.tiles,
+                       triangles_out, (long long)triangle_capacity);
   return mnerf_check_launch("mnerf_mesh_compact");
 }
 
@@ -502,8 +411,7 @@ extern "C" int mnerf_mesh_smooth(const float* vertices_in, int64_t n_vertices, c
                 "mnerf_mesh_smooth: vertices_in / vertices_out / workspace not 16B aligned");
   MNERF_REQUIRE(aligned_to(triangles, 4) && aligned_to(offsets, 4) && aligned_to(corners, 4), MNERF_E_ALIGN,
                 "mnerf_mesh_smooth: triangles / offsets / corners not 4B aligned");
-  const FinishWorkspace w = finish_workspace(n_vertices, n_triangles);
-  float* ping = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.ping);
+  float* ping = finish_workspace(workspace, n_vertices, n_triangles).ping;
   const int nv = (int)n_vertices;
   const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices));
   hipStream_t st = (hipStream_t)stream;
@@ -567,11 +475,11 @@ extern "C" int mnerf_mesh_normals(const float* vertices, int64_t n_vertices, con
 
 // ------------------------------------------------------------------------------------------------ 6. decimation
 // Quadric vertex clustering over a dense uniform grid (include/mnerf.h "mnerf_mesh_decimate"):
-//   dec_cells / finish_* / adj_offsets / dec_fill        the cell of every vertex; the cell -> vertex rows, built as the adjacency's
-//   dec_occupied / finish_scan / finish_total / dec_representatives   the stable scan over the occupied cells; every cell's thread
-//                           sorts its row, sums its quadric in fp64 and writes the new vertex
-//   dec_candidates / adj_* / dec_first / finish_scan / finish_total / dec_triangles   the new index triples, their adjacency, the
-//                           first triangle of every set of three new rows, the stable scan and scatter over those
+//   dec_cells / the CSR offsets / dec_fill        the cell of every vertex; the cell -> vertex rows, built as the adjacency's
+//   dec_occupied / the scan / dec_representatives   the stable scan over the occupied cells; every cell's thread sorts its row,
+//                           sums its quadric in fp64 and writes the new vertex
+//   dec_candidates / adj_* / dec_first / the scan / dec_triangles   the new index triples, their adjacency, the first triangle
+//                           of every set of three new rows, the stable scan and scatter over those
 constexpr double MNERF_DECIMATE_REG = 1.0 / MNERF_DECIMATE_REG_INV;
 struct DecGrid {
   float ox, oy, oz, cell;
@@ -655,7 +563,7 @@ __global__ __launch_bounds__(PC_BLOCK) void dec_representatives_kernel(
   int total;
   const int before = block_prefix(occupied, total);
   if (c >= n_cells) return;
-  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  const long long row = scan_row(counts, tiles, before);
   cell_row[c] = occupied ? (int)row : -1;
   if (!occupied || row >= capacity) return;
   dec_sort(members + begin, end - begin);
@@ -775,7 +683,7 @@ __global__ __launch_bounds__(PC_BLOCK) void dec_triangles_kernel(const int* __re
   int total;
   const int before = block_prefix(kept, total);
   if (!kept) return;
-  const long long row = (long long)tiles[blockIdx.x / PC_TILE] + counts[blockIdx.x] + before;
+  const long long row = scan_row(counts, tiles, before);
   if (row >= capacity) return;
   out[row * 3 + 0] = candidates[3 * t];
   out[row * 3 + 1] = candidates[3 * t + 1];
@@ -784,34 +692,29 @@ __global__ __launch_bounds__(PC_BLOCK) void dec_triangles_kernel(const int* __re
 
 struct DecWorkspace {
   long long bytes;
-  // int64 [2] | int32 [V] cell of a vertex | [V] members | [N + 1] cell offsets | [N] the fill cursor, then the cells' new rows |
-  // [Bn] [Tn] | [3 T] candidates | [V + 1] [V] [3 T] their adjacency and its cursor | [Bv] [Tv] | [Bt] [Tt] | uint8 [T] keep
-  size_t head, cell_of, members, cell_offsets, cell_row, ncounts, ntiles, candidates, tri_offsets, tri_cursor, tri_corners, vcounts, vtiles,
-      tcounts, ttiles, keep;
-  FinishScan sn, sv, st;
+  long long* head;                           // int64 [2]: the totals of the two CSR tables
+  int *cell_of, *members;                    // int32 [V] the cell of a vertex | [V] the cells' rows
+  int *cell_offsets, *cell_row;              // [N + 1] | [N] the fill cursor, then the cells' new rows
+  ScanScratch sn;                            // the scans over the cells
+  int* candidates;                           // [3 T]
+  int *tri_offsets, *tri_cursor, *tri_corners;  // [V + 1] [V] [3 T] the candidates' adjacency and its cursor
+  ScanScratch sv, st;                        // the scans over the vertices and over the triangles
+  unsigned char* keep;                       // uint8 [T]
 };
-static DecWorkspace dec_workspace(long long n_vertices, long long n_triangles, long long n_cells) {
+static DecWorkspace dec_workspace(void* workspace, long long n_vertices, long long n_triangles, long long n_cells) {
   DecWorkspace w = {};
   if (n_vertices == 0) return w;
   const size_t v = (size_t)n_vertices, t = (size_t)n_triangles, n = (size_t)n_cells;
-  w.sn = finish_scan(n_cells), w.sv = finish_scan(n_vertices), w.st = finish_scan(n_triangles);
-  w.head = 0;
-  w.cell_of = 16;
-  w.members = w.cell_of + 4 * v;
-  w.cell_offsets = w.members + 4 * v;
-  w.cell_row = w.cell_offsets + 4 * (n + 1);
-  w.ncounts = w.cell_row + 4 * n;
-  w.ntiles = w.ncounts + 4 * (size_t)w.sn.blocks;
-  w.candidates = w.ntiles + 4 * (size_t)w.sn.tiles;
-  w.tri_offsets = w.candidates + 12 * t;
-  w.tri_cursor = w.tri_offsets + 4 * (v + 1);
-  w.tri_corners = w.tri_cursor + 4 * v;
-  w.vcounts = w.tri_corners + 12 * t;
-  w.vtiles = w.vcounts + 4 * (size_t)w.sv.blocks;
-  w.tcounts = w.vtiles + 4 * (size_t)w.sv.tiles;
-  w.ttiles = w.tcounts + 4 * (size_t)w.st.blocks;
-  w.keep = w.ttiles + 4 * (size_t)w.st.tiles;
-  w.bytes = (long long)((w.keep + t + 15) & ~(size_t)15);
+  Carve c(workspace);
+  w.head = c.array<long long>(2);
+  w.cell_of = c.array<int>(v), w.members = c.array<int>(v);
+  w.cell_offsets = c.array<int>(n + 1), w.cell_row = c.array<int>(n);
+  w.sn = c.scan(n_cells);
+  w.candidates = c.array<int>(3 * t);
+  w.tri_offsets = c.array<int>(v + 1), w.tri_cursor = c.array<int>(v), w.tri_corners = c.array<int>(3 * t);
+  w.sv = c.scan(n_vertices), w.st = c.scan(n_triangles);
+  w.keep = c.array<unsigned char>(t);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -821,7 +724,7 @@ static bool dec_grid_ok(int32_t gx, int32_t gy, int32_t gz) {
 
 extern "C" int64_t mnerf_mesh_decimate_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int32_t gx, int32_t gy, int32_t gz) {
   if (!finish_sizes_ok(n_vertices, n_triangles) || !dec_grid_ok(gx, gy, gz)) return -1;
-  return dec_workspace(n_vertices, n_triangles, (long long)gx * gy * gz).bytes;
+  return dec_workspace(nullptr, n_vertices, n_triangles, (long long)gx * gy * gz).bytes;
 }
 
 extern "C" int mnerf_mesh_decimate(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles,
@@ -848,15 +751,7 @@ extern "C" int mnerf_mesh_decimate(const float* vertices, const int32_t* triangl
                     aligned_to(vertex_map, 4) && aligned_to(counts, 8),
                 MNERF_E_ALIGN, "mnerf_mesh_decimate: triangles / offsets / corners / triangles_out / vertex_map / counts not aligned to 4 / 8 bytes");
   const long long n_cells_ll = (long long)gx * gy * gz;
-  const DecWorkspace w = dec_workspace(n_vertices, n_triangles, n_cells_ll);
-  char* base = static_cast<char*>(workspace);
-  long long* total = reinterpret_cast<long long*>(base + w.head);
-  auto ints = [&](size_t at) { return reinterpret_cast<int*>(base + at); };
-  int *cell_of = ints(w.cell_of), *members = ints(w.members), *cell_offsets = ints(w.cell_offsets), *cell_row = ints(w.cell_row);
-  int *ncounts = ints(w.ncounts), *ntiles = ints(w.ntiles), *candidates = ints(w.candidates), *tri_offsets = ints(w.tri_offsets);
-  int *tri_cursor = ints(w.tri_cursor), *tri_corners = ints(w.tri_corners), *vcounts = ints(w.vcounts), *vtiles = ints(w.vtiles);
-  int *tcounts = ints(w.tcounts), *ttiles = ints(w.ttiles);
-  unsigned char* keep = reinterpret_cast<unsigned char*>(base + w.keep);
+  const DecWorkspace w = dec_workspace(workspace, n_vertices, n_triangles, n_cells_ll);
   long long* count = reinterpret_cast<long long*>(counts);
   const DecGrid g = {origin_x, origin_y, origin_z, cell, gx, gy, gz};
   const int nv = (int)n_vertices, nc = (int)n_cells_ll;
@@ -864,36 +759,28 @@ extern "C" int mnerf_mesh_decimate(const float* vertices, const int32_t* triangl
   const dim3 threads(PC_BLOCK), vblocks(blocks_of(n_vertices)), nblocks(blocks_of(n_cells_ll)), tblocks(blocks_of(nt)), cblocks(blocks_of(n_corners));
   hipStream_t st = (hipStream_t)stream;
   // the cell -> vertex rows
-  hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_cells_ll + 1)), threads, 0, st, cell_offsets, nc);
-  hipLaunchKernelGGL(dec_cells_kernel, vblocks, threads, 0, st, vertices, nv, g, cell_of, cell_offsets);
-  hipLaunchKernelGGL(finish_blocksum_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts);
-  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sn.tiles), threads, 0, st, ncounts, (int)w.sn.blocks, ntiles);
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ntiles, (int)w.sn.tiles, total);
-  hipLaunchKernelGGL(adj_offsets_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts, ntiles, cell_row);
-  hipLaunchKernelGGL(dec_fill_kernel, vblocks, threads, 0, st, cell_of, nv, cell_row, members);
+  hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_cells_ll + 1)), threads, 0, st, w.cell_offsets, nc);
+  hipLaunchKernelGGL(dec_cells_kernel, vblocks, threads, 0, st, vertices, nv, g, w.cell_of, w.cell_offsets);
+  csr_offsets_enqueue(w.cell_offsets, nc, w.sn, w.head, w.cell_row, st);
+  hipLaunchKernelGGL(dec_fill_kernel, vblocks, threads, 0, st, w.cell_of, nv, w.cell_row, w.members);
   // the new vertices
-  hipLaunchKernelGGL(dec_occupied_kernel, nblocks, threads, 0, st, cell_offsets, nc, ncounts);
-  hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sn.tiles), threads, 0, st, ncounts, (int)w.sn.blocks, ntiles);
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ntiles, (int)w.sn.tiles, count);
+  hipLaunchKernelGGL(dec_occupied_kernel, nblocks, threads, 0, st, w.cell_offsets, nc, w.sn.counts);
+  scan_enqueue(w.sn, count, st);
   hipLaunchKernelGGL(dec_representatives_kernel, nblocks, threads, 0, st, vertices, triangles, offsets, corners, nv, (int)nt, g, nc,
-                     cell_offsets, members, ncounts, ntiles, cell_row, vertices_out, (long long)vertex_capacity);
-  if (vertex_map) hipLaunchKernelGGL(dec_map_kernel, vblocks, threads, 0, st, cell_of, cell_row, nv, vertex_map);
+                     w.cell_offsets, w.members, w.sn.counts, w.sn.tiles, w.cell_row, vertices_out, (long long)vertex_capacity);
+  if (vertex_map) hipLaunchKernelGGL(dec_map_kernel, vblocks, threads, 0, st, w.cell_of, w.cell_row, nv, vertex_map);
   // the new triangles: the adjacency of the candidates over the new rows (at most V of them), the first of every set, the scatter
   if (nt) {
-    hipLaunchKernelGGL(dec_candidates_kernel, tblocks, threads, 0, st, triangles, nt, nv, cell_of, cell_row, candidates);
-    hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_vertices + 1)), threads, 0, st, tri_offsets, nv);
-    hipLaunchKernelGGL(adj_count_kernel, cblocks, threads, 0, st, candidates, n_corners, nv, tri_offsets);
-    hipLaunchKernelGGL(finish_blocksum_kernel, vblocks, threads, 0, st, tri_offsets, nv, vcounts);
-    hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.sv.tiles), threads, 0, st, vcounts, (int)w.sv.blocks, vtiles);
-    hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, vtiles, (int)w.sv.tiles, total + 1);
-    hipLaunchKernelGGL(adj_offsets_kernel, vblocks, threads, 0, st, tri_offsets, nv, vcounts, vtiles, tri_cursor);
-    hipLaunchKernelGGL(adj_fill_kernel, cblocks, threads, 0, st, candidates, n_corners, nv, tri_cursor, tri_corners);
-    hipLaunchKernelGGL(dec_first_kernel, tblocks, threads, 0, st, candidates, nt, tri_offsets, tri_corners, keep, tcounts);
-    hipLaunchKernelGGL(finish_scan_kernel, dim3((unsigned)w.st.tiles), threads, 0, st, tcounts, (int)w.st.blocks, ttiles);
+    hipLaunchKernelGGL(dec_candidates_kernel, tblocks, threads, 0, st, triangles, nt, nv, w.cell_of, w.cell_row, w.candidates);
+    hipLaunchKernelGGL(adj_zero_kernel, dim3(blocks_of(n_vertices + 1)), threads, 0, st, w.tri_offsets, nv);
+    hipLaunchKernelGGL(adj_count_kernel, cblocks, threads, 0, st, w.candidates, n_corners, nv, w.tri_offsets);
+    csr_offsets_enqueue(w.tri_offsets, nv, w.sv, w.head + 1, w.tri_cursor, st);
+    hipLaunchKernelGGL(adj_fill_kernel, cblocks, threads, 0, st, w.candidates, n_corners, nv, w.tri_cursor, w.tri_corners);
+    hipLaunchKernelGGL(dec_first_kernel, tblocks, threads, 0, st, w.candidates, nt, w.tri_offsets, w.tri_corners, w.keep, w.st.counts);
   }
-  hipLaunchKernelGGL(finish_total_kernel, dim3(1), threads, 0, st, ttiles, (int)w.st.tiles, count + 1);
+  scan_enqueue(w.st, count + 1, st);  // (no triangle: the total, 0, alone)
   if (nt)
-    hipLaunchKernelGGL(dec_triangles_kernel, tblocks, threads, 0, st, candidates, nt, keep, tcounts, ttiles, triangles_out,
+    hipLaunchKernelGGL(dec_triangles_kernel, tblocks, threads, 0, st, w.candidates, nt, w.keep, w.st.counts, w.st.tiles, triangles_out,
                        (long long)triangle_capacity);
   return mnerf_check_launch("mnerf_mesh_decimate");
 }

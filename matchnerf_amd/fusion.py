@@ -67,7 +67,7 @@ def fuse(views, depths, opacities, rgbs, hw, legacy, px_tol=1.0, rel_tol=0.01, m
     dev = depths.device
     points = torch.empty(k_views * n, hip.POINT_FLOATS, device=dev)
     counts = torch.zeros(k_views, dtype=torch.int64, device=dev)
-    workspace = torch.empty(max(hip.point_cloud_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+    workspace = hip.export_workspace("point_cloud", None, hip.point_cloud_workspace_bytes(n), dev)
     out = (torch.empty(h, w, device=dev), torch.empty(h, w, dtype=torch.int32, device=dev))
     all_views = hip.view_array(views) if k_views <= hip.MNERF_MAX_VIEWS else None
     centres = None if all_views is not None else camera_centres(views)
@@ -97,7 +97,7 @@ def _auto_bounds(views, fused, counts, rgbs, hw, legacy, min_consistent):
     dev = fused.device
     points = torch.empty(k_views * n, hip.POINT_FLOATS, device=dev)
     rows = torch.zeros(k_views, dtype=torch.int64, device=dev)
-    workspace = torch.empty(max(hip.point_cloud_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+    workspace = hip.export_workspace("point_cloud", None, hip.point_cloud_workspace_bytes(n), dev)
     for k in range(k_views):
         hip.point_cloud(views[k], (h, w), fused[k], rgbs[k], counts[k], min_consistent, legacy=legacy, points=points[k * n:(k + 1) * n],
                         count=rows[k:k + 1], workspace=workspace)
@@ -196,7 +196,7 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
                            opacity=None if map_opacity is None else map_opacity[group],
                            n_consistent=None if counts is None else counts[group], min_consistent=min_consistent, legacy=legacy,
                            min_opacity=min_opacity)
-    workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    workspace = hip.export_workspace("tsdf_mesh", None, need, dev)
     guess = min(7 * nx * ny * nz, max(1024, MESH_GUESS_ROWS * (nx * ny + ny * nz + nz * nx)))
     vertices = torch.empty(guess, hip.VERTEX_FLOATS, device=dev)
     faces = torch.empty(2 * guess, 3, dtype=torch.int32, device=dev)
@@ -239,7 +239,7 @@ def finish(vertices, faces, *, min_component=0, min_component_fraction=0.0, smoo
         return vertices, faces
     vertices, faces = vertices.contiguous(), faces.contiguous()
     n_vertices, n_faces = vertices.shape[0], faces.shape[0]
-    workspace = torch.empty(max(hip.mesh_finish_workspace_bytes(n_vertices, n_faces), 16), dtype=torch.uint8, device=vertices.device)
+    workspace = hip.export_workspace("mesh_finish", None, hip.mesh_finish_workspace_bytes(n_vertices, n_faces), vertices.device)
     if filtering:
         _, keep = hip.mesh_components(faces, n_vertices, min_component, min_component_fraction, workspace=workspace)
         vertices, faces, totals = hip.mesh_compact(vertices, faces, keep, workspace=workspace)

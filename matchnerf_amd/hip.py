@@ -1613,6 +1613,17 @@ def depth_consistency(views, ref, depth, opacity=None, legacy=True, px_tol=1.0, 
     return fused, cnt
 
 
+def export_workspace(what, workspace, need, dev):
+    """the workspace of an export call: the caller's if it lies on ``dev`` and holds ``need`` bytes, a fresh one for None"""
+    import torch
+    if workspace is None:
+        return torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
+        raise MnerfError(f"{what}: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
+                         f"{need} needed on {dev}")
+    return workspace
+
+
 def point_cloud_workspace_bytes(n_pixels):
     return int(load().mnerf_point_cloud_workspace_bytes(int(n_pixels)))
 
@@ -1638,16 +1649,8 @@ def point_cloud(view, hw, depth, rgb, n_consistent, min_consistent, legacy=True,
         points = torch.empty(n, POINT_FLOATS, device=dev)
     if _f32c(points, "points").device != dev or points.numel() % POINT_FLOATS:
         raise MnerfError(f"point_cloud: points {tuple(points.shape)} on {points.device} is no [capacity, {POINT_FLOATS}] buffer on {dev}")
-    if count is None:
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
-    if count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
-        raise MnerfError("point_cloud: count must be a 1-element int64 tensor on the depth's device")
-    need = point_cloud_workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
-        raise MnerfError(f"point_cloud: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
-                         f"{need} needed on {dev}")
+    count = torch.zeros(1, dtype=torch.int64, device=dev) if count is None else _mesh_buffer("point_cloud", "count", count, torch.int64, 1, dev)
+    workspace = export_workspace("point_cloud", workspace, point_cloud_workspace_bytes(n), dev)
     with _on(dev, stream) as st:
         check(lib.mnerf_point_cloud(C.byref(view), h, w, int(bool(legacy)), _ptr(depth), _ptr(rgb), _ptr_i32(n_consistent),
                                     int(min_consistent), _ptr(points), points.numel() // POINT_FLOATS, _ptr(count), _ptr(workspace), st),
@@ -1740,18 +1743,11 @@ def tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, triangles
         raise MnerfError(f"tsdf_mesh: vertices {tuple(vertices.shape)} on {vertices.device} is no [capacity, {VERTEX_FLOATS}] buffer on {dev}")
     if triangles.dtype != torch.int32 or not triangles.is_contiguous() or triangles.device != dev or triangles.numel() % 3:
         raise MnerfError(f"tsdf_mesh: triangles must be a contiguous int32 [capacity, 3] tensor on {dev}")
-    if counts is None:
-        counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    if counts.dtype != torch.int64 or counts.numel() != 2 or counts.device != dev or not counts.is_contiguous():
-        raise MnerfError("tsdf_mesh: counts must be a contiguous 2-element int64 tensor on the volume's device")
+    counts = torch.zeros(2, dtype=torch.int64, device=dev) if counts is None else _mesh_buffer("tsdf_mesh", "counts", counts, torch.int64, 2, dev)
     need = tsdf_mesh_workspace_bytes(grid[4:])
     if need < 0:
         raise MnerfError(f"tsdf_mesh: the grid {tuple(grid[4:])} is too large to mesh")
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
-        raise MnerfError(f"tsdf_mesh: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
-                         f"{need} needed on {dev}")
+    workspace = export_workspace("tsdf_mesh", workspace, need, dev)
     with _on(dev, stream) as st:
         check(lib.mnerf_tsdf_mesh(_ptr(sums), _ptr(weight), *grid, float(min_weight), _ptr(vertices), vertices.numel() // VERTEX_FLOATS,
                                   _ptr_i32(triangles), triangles.numel() // 3, _ptr(counts), _ptr(workspace), st), "mnerf_tsdf_mesh")
@@ -1798,14 +1794,7 @@ def _mesh_buffer(what, name, t, dtype, numel, dev):
 
 
 def _mesh_workspace(what, workspace, n_vertices, n_triangles, dev):
-    import torch
-    need = mesh_finish_workspace_bytes(n_vertices, n_triangles)
-    if workspace is None:
-        return torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
-        raise MnerfError(f"{what}: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
-                         f"{need} needed on {dev}")
-    return workspace
+    return export_workspace(what, workspace, mesh_finish_workspace_bytes(n_vertices, n_triangles), dev)
 
 
 def mesh_adjacency(triangles, n_vertices, out=None, workspace=None, stream=None):
@@ -1939,11 +1928,7 @@ def mesh_decimate(vertices, triangles, adjacency, origin, cell, dims, vertices_o
         vertex_map = _mesh_buffer("mesh_decimate", "vertex_map", vertex_map, torch.int32, nv, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev) if counts is None else _mesh_buffer("mesh_decimate", "counts", counts,
                                                                                               torch.int64, 2, dev)
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
-        raise MnerfError(f"mesh_decimate: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, "
-                         f"{need} needed on {dev}")
+    workspace = export_workspace("mesh_decimate", workspace, need, dev)
     with _on(dev, stream) as st:
         check(lib.mnerf_mesh_decimate(_ptr(vertices), _ptr_i32(triangles), nv, nt, _ptr_i32(offsets), _ptr_i32(corners), *grid,
                                       _ptr(vertices_out), vertices_out.numel() // VERTEX_FLOATS, _ptr_i32(triangles_out),

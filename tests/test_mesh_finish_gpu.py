@@ -308,6 +308,10 @@ def test_empty_meshes(hip):
     assert np.array_equal(_bits(_smooth(hip, vertices, none_f, adj, 2)), _bits(H.degenerate()[0]))
     kept_v, kept_f, counts = _compact(hip, vertices, none_f, _cuda(np.array([1, 0, 1, 1, 0, 0, 1], np.uint8)))
     assert counts == [4, 0] and np.array_equal(_bits(kept_v[:4]), _bits(H.degenerate()[0][[0, 2, 3, 6]]))
+    # ... and the triangle total is WRITTEN as 0 (the scan over no element still enqueues its total), not left as it was
+    stale = torch.full((2,), -1, dtype=torch.int64, device="cuda")
+    hip.mesh_compact(vertices, none_f, _cuda(np.array([1, 0, 1, 1, 0, 0, 1], np.uint8)), counts=stale)
+    assert stale.tolist() == [4, 0]
 
 
 def test_two_runs_give_the_same_bytes(hip):
