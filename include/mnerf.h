@@ -1124,6 +1124,89 @@ int mnerf_mesh_decimate(const float* vertices, const int32_t* triangles, int64_t
                         int32_t gz, float* vertices_out, int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity,
                         int32_t* vertex_map, int64_t* counts, void* workspace, void* stream);
 
+/* MESH TEXTURE (added under v12 without a layout change; matchnerf_amd/csrc/mesh_texture.hip): a texture atlas for an indexed mesh,
+ * baked from the views the mesh was fused from.  The mesh's own colour is one nearest texel per voxel, interpolated and - after a
+ * decimation - averaged over a cell; the atlas carries the frames' detail onto the surface.  The conventions are those of GEOMETRY
+ * EXPORT and MESH EXPORT: pinhole camera-z depth, mnerf_view HOST arrays read during the call (by value in the kernel arguments),
+ * proj(), the VALID test of a texel and the bilinear taps as stated there, pixel centres by legacy_coord, fp32 with every operation
+ * rounded on its own and one FMA where the text says fma(), enqueue-only on `stream`, nothing allocated or copied, every argument
+ * check before any HIP call (MNERF_E_RANGE, then _NULL, then _ALIGN), no kernel reads or writes outside a buffer for any index
+ * value, no atomic of any kind: the only sums run over the views inside one thread, in ascending order, and two runs give the same
+ * bytes.  The mesh is any [V][8] / [T][3] mesh of MESH FINISHING with 0 <= V < 2^31, 0 <= 3 T < 2^31; T == 0 is MNERF_OK and touches
+ * no buffer.
+ *
+ * THE ATLAS is a function of (T, block) only, so its size costs no device->host copy.  Every triangle gets a right-triangle patch;
+ * two triangles share one square block of B x B texels, B = `block`, 4 <= B <= 64.
+ *   nb = ceil(T / 2) blocks;  nbx = the smallest integer with nbx^2 >= nb;  nby = ceil(nb / nbx) (0 for T == 0);  the atlas is
+ *   W = nbx B wide and H = nby B high; W or H above 16384 is MNERF_E_RANGE.  Row 0 is the TOP row; texel (x, y) has the linear index
+ *   y W + x and its centre at (x + 0.5, y + 0.5).  Block p sits at (p mod nbx, p / nbx); triangle 2 p is its LOWER triangle and
+ *   2 p + 1 its UPPER.
+ *   corners        in texel units from the block's top-left corner, for the vertices 0, 1, 2 in stored winding:
+ *                    lower   (0.5, 0.5), (B - 2.5, 0.5), (0.5, B - 2.5)
+ *                    upper   (B - 0.5, B - 0.5), (2.5, B - 0.5), (B - 0.5, 2.5) - the point reflection of the lower
+ *   ownership      the local texel (i, j) of a block belongs to the lower triangle iff i + j <= B - 1 and to the upper one
+ *                  otherwise; the upper triangle then uses i' = B - 1 - i, j' = B - 1 - j in place of i, j.  A texel has NO OWNER
+ *                  when its triangle's index is >= T (a block >= nb; the upper half of the last block when T is odd).
+ *   surface        a = i / (B - 3), b = j / (B - 3) (the integers converted, one division each); if s = a + b > 1 then a = a / s,
+ *                  b = b / s - the two texel rows past the hypotenuse are clamped onto it.  A quantity q of the vertices is
+ *                  blended as fma(b, q2 - q0, fma(a, q1 - q0, q0)); the surface point P is that blend of x, y, z.
+ *   GUARANTEE      the corners fall on texel centres, every texel of a block has exactly one owner, and a bilinear fetch anywhere
+ *                  inside a triangle's UV triangle gives non-zero weight only to texels that triangle owns: the lower triangle's
+ *                  fetches touch texels with i + j <= B - 2 only (the row i + j = B - 1 is a spare for a renderer's rounding), the
+ *                  upper triangle's their reflections, i + j >= B.  No gutter pass and no dilation are needed.  (Blocks are not mip-safe across their borders.)
+ *   VALID triangle its three indices lie in [0, V), its three positions are finite, and n = (p1 - p0) x (p2 - p0), in the fma form
+ *                  of mnerf_mesh_normals, has |n| = sqrt(fma(n_z, n_z, fma(n_y, n_y, n_x n_x))) > 0.
+ *
+ * mnerf_mesh_texture_atlas - host only: size[0] = W, size[1] = H (a HOST array).  MNERF_E_RANGE: T < 0 or 3 T >= 2^31, block outside
+ * 4..64, a side above 16384.  MNERF_E_NULL: size missing.
+ *
+ * mnerf_mesh_texture_uv - one thread per triangle: uv device [T][3][2] fp32, (x / W, y / H) of the corners with the origin at the
+ * top-left.  The numerators (block origin + corner) are half-integers, exact in fp32; one division each.  MNERF_E_RANGE as above;
+ * MNERF_E_NULL: uv missing; MNERF_E_ALIGN: uv not 4-byte aligned.
+ *
+ * mnerf_mesh_texture_accumulate - one thread per texel, one launch; adds n_views (1..MNERF_MAX_VIEWS) views to an accumulation
+ * buffer that the caller owns and has zeroed before the first call.  More views are several calls on one buffer, as with the volume.
+ *   accum          device [H][W][4] fp32, 16-byte aligned: r g b | w
+ *   depth, opacity, n_consistent, min_consistent, rgb, min_opacity    as in mnerf_tsdf_integrate (with n_consistent pass the FUSED
+ *                  depth and opacity = NULL)
+ * A texel without an owner, or whose triangle is not VALID, is not touched.  Otherwise, with P its surface point and n, |n| its
+ * triangle's, for view k in ascending order:
+ *   c = the camera centre, the translation column of the host-inverted extr;  e = c - P;  |e| as |n|;
+ *   cos = fma(n_z, e_z, fma(n_y, e_y, n_x e_x)) / (|n| |e|); skipped unless cos > 0 (the view looks at the back);
+ *   (u, v, zc) = proj(k, P); skipped unless zc > 0 and (u, v) lies in the rectangle of view k's pixel centres;
+ *   the four taps of mnerf_depth_consistency at (u, v) must all be VALID - and, with n_consistent, have n_consistent >=
+ *   min_consistent - else skipped; d = their bilinear value in the a + t b form;
+ *   skipped unless |d - zc| <= vis_rel_tol zc: P is the surface this view sees, not something behind it;
+ *   colour = the bilinear value of rgb at the same taps and weights, per channel, in the same form;
+ *   weight = 1 multiplied `power` times by cos (an integer 0..8; no powf);
+ *   best == 0:  rgb = fma(weight, colour, rgb) per channel, w = w + weight
+ *   best != 0:  iff weight > w the texel becomes colour | weight (ties go to the earlier view)
+ * MNERF_E_RANGE: the bounds of the mesh and the atlas, n_views outside 1..MNERF_MAX_VIEWS, height or width below 1 or height x width
+ * >= 2^31, a min_opacity that is not finite (read only with opacity), vis_rel_tol not finite and positive, power outside 0..8, a
+ * singular intr or extr.  MNERF_E_NULL: vertices (with V > 0), triangles, views, depth, rgb or accum missing.  MNERF_E_ALIGN: vertices
+ * or accum not 16-byte, any other pointer not 4-byte aligned.
+ *
+ * mnerf_mesh_texture_resolve - one thread per texel: atlas device [H][W][4] fp32 r g b a, 16-byte aligned; it may be `accum` itself.
+ *   an owned texel of a VALID triangle with w > 0:  rgb = sums / w, one division per channel (best == 0) or the stored colour
+ *                  (best != 0);  a = 1
+ *   the same with w not > 0:  rgb = the blend (see "surface") of the three VERTEX colours, a = 0 - where no view sees the surface
+ *                  the atlas shows exactly what the untextured mesh shows
+ *   every other texel (no owner, a triangle that is not VALID):  0 0 0 0
+ * The atlas is therefore total.  MNERF_E_RANGE: the bounds of the mesh and the atlas.  MNERF_E_NULL: vertices (with V > 0), triangles,
+ * accum or atlas missing.  MNERF_E_ALIGN: vertices, accum or atlas not 16-byte, triangles not 4-byte aligned.
+ *
+ * Texel density is per triangle, not per area: uniform on the mesher's and the decimator's output, wasteful on a mesh of very
+ * unequal triangles.  There is no seam levelling between views. */
+int mnerf_mesh_texture_atlas(int64_t n_triangles, int32_t block, int32_t* size);
+int mnerf_mesh_texture_uv(int64_t n_triangles, int32_t block, float* uv, void* stream);
+int mnerf_mesh_texture_accumulate(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, int32_t block,
+                                  const mnerf_view* views, int32_t n_views, int32_t height, int32_t width, int32_t legacy_coord,
+                                  const float* depth, const float* opacity, const int32_t* n_consistent, int32_t min_consistent,
+                                  const float* rgb, float min_opacity, float vis_rel_tol, int32_t power, int32_t best, float* accum,
+                                  void* stream);
+int mnerf_mesh_texture_resolve(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, int32_t block,
+                               int32_t best, const float* accum, float* atlas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -759,8 +759,12 @@ class Coach:
         mesh_voxel / mesh_trunc / mesh_min_weight where given, cleaned up by nerf.mesh_min_component / mesh_min_component_fraction
         (small connected components dropped), nerf.mesh_smooth (rounds of Taubin smoothing) and nerf.mesh_decimate (quadric
         vertex clustering with cells of that many voxels, applied last) where given; with nerf.mesh_normals the vertices also carry
-        float nx ny nz (``fusion.vertex_normals`` of the mesh that is written).  One process (not sharded).
-        Returns {set: [path of every .ply]}."""
+        float nx ny nz (``fusion.vertex_normals`` of the mesh that is written).  With nerf.mesh_texture=B also <stem>_mesh.obj, .mtl and
+        .png next to <stem>_mesh.ply: the same mesh with a texture atlas of B x B blocks baked from the views (``fusion.texture``;
+        nerf.mesh_texture_best / mesh_texture_power / mesh_texture_rel_tol where given; nerf.mesh_texture_from = 'render' (default)
+        | 'images': the source photographs instead of their re-renderings, with 'sources' views only); <stem>_mesh.ply is the same
+        bytes with or without it.  One process (not sharded).
+        Returns {set: [path of every .ply, and of every .obj after its mesh's .ply]}."""
         from PIL import Image
 
         from . import fusion
@@ -781,6 +785,12 @@ class Coach:
                                                                               ("smooth", "mesh_smooth"), ("decimate", "mesh_decimate"))
                          if getattr(self.opts.nerf, name, None) is not None}
             fusion._decimate_cell("nerf.mesh_decimate", mesh_args.get("decimate", 0.0))  # refused before anything is rendered
+            mesh_args.update({arg: getattr(self.opts.nerf, name) for arg, name in (("texture", "mesh_texture"), ("texture_best", "mesh_texture_best"),
+                                                                                   ("texture_power", "mesh_texture_power"),
+                                                                                   ("texture_vis_rel_tol", "mesh_texture_rel_tol"))
+                              if getattr(self.opts.nerf, name, None) is not None})
+            texture_from = getattr(self.opts.nerf, "mesh_texture_from", None) or "render"
+            self.model.check_texture("nerf.mesh_texture", mesh_args.get("texture", 0), mesh_args.get("texture_power", 2), texture_from, views)
         mesh_normals = bool(getattr(self.opts.nerf, "mesh_normals", None))
         out_root = os.path.join(self.opts.output_path, "geometry")
         written = {}
@@ -801,12 +811,20 @@ class Coach:
                     written.setdefault(name, []).append(path)
                     self.say(f"[coach] {name}: {n} points -> {path}")
                     if mesh_args is not None:  # the surface of the same maps, fused into a TSDF volume
-                        vertices, faces = fusion.mesh(maps.views[bi], maps.depth[bi], maps.opacity[bi], maps.rgb[bi], maps.hw,
-                                                      bool(self.opts.nerf.legacy_coord), **mesh_args, **fuse_args)
+                        photos = self.model.source_colours(var)[bi] if mesh_args.get("texture", 0) and texture_from == "images" else None
+                        vertices, faces, *textured = fusion.mesh(maps.views[bi], maps.depth[bi], maps.opacity[bi], maps.rgb[bi], maps.hw,
+                                                                 bool(self.opts.nerf.legacy_coord), texture_rgbs=photos, **mesh_args,
+                                                                 **fuse_args)
                         path = os.path.join(out_dir, f"{stem}_mesh.ply")
-                        fusion.write_ply(path, vertices, faces, fusion.vertex_normals(vertices, faces) if mesh_normals else None)
+                        vertex_normals = fusion.vertex_normals(vertices, faces) if mesh_normals else None
+                        fusion.write_ply(path, vertices, faces, vertex_normals)
                         written[name].append(path)
                         self.say(f"[coach] {name}: {vertices.shape[0]} vertices, {faces.shape[0]} triangles -> {path}")
+                        if textured:
+                            path = os.path.join(out_dir, f"{stem}_mesh.obj")
+                            fusion.write_obj(path, vertices, faces, *textured, vertex_normals)
+                            written[name].append(path)
+                            self.say(f"[coach] {name}: a {textured[1].shape[1]} x {textured[1].shape[0]} atlas -> {path}")
                     for k in range(panels.shape[1] if panels is not None else 0):
                         Image.fromarray(panels[bi, k]).save(os.path.join(out_dir, f"{stem}_depth{k}.png"))
             self.model.nerf_setbg_opaque = False

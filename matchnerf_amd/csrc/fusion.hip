@@ -36,7 +36,6 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(FusionCams cams,
   }
   float wx, wy, wz;
   fusion_lift(R, x, y, z, wx, wy, wz);
-  const float u_hi = (float)(width - 1) + off, v_hi = (float)(height - 1) + off;
   int count = 0;
   float sum = z;
   for (int j = 0; j < n_views; ++j) {  // (wave-uniform: the cameras are read through scalar loads)
@@ -44,22 +43,10 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(FusionCams cams,
     const FusionCam& J = cams.cam[j];
     float u, v, zj;
     fusion_project(J, wx, wy, wz, u, v, zj);
-    if (!(zj > 0.0f) || !(u >= off && u <= u_hi && v >= off && v <= v_hi)) continue;
-    const float fx = u - off, fy = v - off;
-    int x0 = min((int)floorf(fx), width - 2), y0 = min((int)floorf(fy), height - 2);
-    x0 = max(x0, 0), y0 = max(y0, 0);
-    const int x1 = min(x0 + 1, width - 1), y1 = min(y0 + 1, height - 1);
-    const float ax = fx - (float)x0, ay = fy - (float)y0;
-    const size_t base = (size_t)j * n;
-    float z00, z10, z01, z11;
-    bool ok = fusion_value(depth, opacity, base + (size_t)y0 * width + x0, min_opacity, J.v.near_, J.v.far_, z00);
-    ok &= fusion_value(depth, opacity, base + (size_t)y0 * width + x1, min_opacity, J.v.near_, J.v.far_, z10);
-    ok &= fusion_value(depth, opacity, base + (size_t)y1 * width + x0, min_opacity, J.v.near_, J.v.far_, z01);
-    ok &= fusion_value(depth, opacity, base + (size_t)y1 * width + x1, min_opacity, J.v.near_, J.v.far_, z11);
-    if (!ok) continue;
-    const float top = __builtin_fmaf(ax, z10 - z00, z00);
-    const float bot = __builtin_fmaf(ax, z11 - z01, z01);
-    const float dj = __builtin_fmaf(ay, bot - top, top);
+    if (!(zj > 0.0f) || !fusion_in_frame(u, v, off, height, width)) continue;
+    const FusionTaps t = fusion_taps(u, v, off, height, width);
+    float dj;
+    if (!fusion_bilinear_value(depth, opacity, nullptr, 0, (size_t)j * n, width, t, min_opacity, J.v.near_, J.v.far_, dj)) continue;
     float bx, by, bz, xr, yr, dr;
     fusion_lift(J, u, v, dj, bx, by, bz);
     fusion_project(R, bx, by, bz, xr, yr, dr);

@@ -1,6 +1,6 @@
 // What the geometry-export kernels share (fusion.hip: consistency, point cloud; mesh.hip: TSDF volume, mesher; mesh_finish.hip:
-// finishing, decimation): the camera with its host-inverted matrices, the fp32 projection chain, the value of a depth texel, the
-// integer workgroup scans of the stable compactions with the two-level scan over them (scan.hip), and the carving of a workspace.
+// finishing, decimation; mesh_texture.hip: the atlas): the camera with its host-inverted matrices, the fp32 projection chain, the
+// value of a depth texel, the bilinear taps, the integer workgroup scans of the stable compactions with the two-level scan over them (scan.hip), and the carving of a workspace.
 // Include after common.hpp, under `#pragma clang fp contract(off)`: every operation rounds on its own and the FMAs are the explicit
 // ones of the helpers.
 #pragma once
@@ -51,6 +51,49 @@ __device__ __forceinline__ bool fusion_value(const float* __restrict__ depth, co
     z = z / o;
   }
   return isfinite(z) && z >= near_ && z <= far_;
+}
+
+// the bilinear taps of a map at pixel coordinates (u, v) inside the rectangle of its pixel centres (include/mnerf.h
+// "mnerf_depth_consistency"): the texels (x0|x1, y0|y1) and the weights ax, ay of x1 and y1
+struct FusionTaps {
+  int x0, y0, x1, y1;
+  float ax, ay;
+};
+__device__ __forceinline__ bool fusion_in_frame(float u, float v, float off, int height, int width) {
+  return u >= off && u <= (float)(width - 1) + off && v >= off && v <= (float)(height - 1) + off;
+}
+__device__ __forceinline__ FusionTaps fusion_taps(float u, float v, float off, int height, int width) {
+  FusionTaps t;
+  const float fx = u - off, fy = v - off;
+  t.x0 = max(min((int)floorf(fx), width - 2), 0), t.y0 = max(min((int)floorf(fy), height - 2), 0);
+  t.x1 = min(t.x0 + 1, width - 1), t.y1 = min(t.y0 + 1, height - 1);
+  t.ax = fx - (float)t.x0, t.ay = fy - (float)t.y0;
+  return t;
+}
+// top + ay (bot - top) with top = v00 + ax (v10 - v00), bot = v01 + ax (v11 - v01), each a + t b one FMA
+__device__ __forceinline__ float fusion_bilinear(const FusionTaps& t, float v00, float v10, float v01, float v11) {
+  const float top = __builtin_fmaf(t.ax, v10 - v00, v00);
+  const float bot = __builtin_fmaf(t.ax, v11 - v01, v01);
+  return __builtin_fmaf(t.ay, bot - top, top);
+}
+// the bilinear value of a view's map (`base` = its first pixel) at the taps; false unless all four texels are VALID, whatever their
+// weights, and - with n_consistent - confirmed by min_consistent views
+__device__ __forceinline__ bool fusion_bilinear_value(const float* __restrict__ depth, const float* __restrict__ opacity,
+                                                      const int* __restrict__ n_consistent, int min_consistent, size_t base,
+                                                      int width, const FusionTaps& t, float min_opacity, float near_, float far_,
+                                                      float& z) {
+  const size_t i00 = base + (size_t)t.y0 * width + t.x0, i10 = base + (size_t)t.y0 * width + t.x1;
+  const size_t i01 = base + (size_t)t.y1 * width + t.x0, i11 = base + (size_t)t.y1 * width + t.x1;
+  float z00, z10, z01, z11;
+  bool ok = fusion_value(depth, opacity, i00, min_opacity, near_, far_, z00);
+  ok &= fusion_value(depth, opacity, i10, min_opacity, near_, far_, z10);
+  ok &= fusion_value(depth, opacity, i01, min_opacity, near_, far_, z01);
+  ok &= fusion_value(depth, opacity, i11, min_opacity, near_, far_, z11);
+  if (n_consistent)
+    ok &= n_consistent[i00] >= min_consistent && n_consistent[i10] >= min_consistent && n_consistent[i01] >= min_consistent &&
+          n_consistent[i11] >= min_consistent;
+  z = fusion_bilinear(t, z00, z10, z01, z11);
+  return ok;
 }
 
 // ------------------------------------------------------------------------------------------------ host: inverse cameras

@@ -15,6 +15,10 @@ indexed, coloured triangle mesh whose vertex and face order is defined - two run
 FINISHING", matchnerf_amd/csrc/mesh_finish.hip): small connected components dropped, Taubin smoothing of the positions,
 area-weighted vertex normals; ``write_ply`` takes the normals.  ``decimate`` reduces it by quadric vertex clustering over a uniform
 grid (``hip.mesh_decimate``): one vertex per occupied cell, the same bytes on every run.
+
+``texture`` bakes the views' colours onto such a mesh (include/mnerf.h "MESH TEXTURE", matchnerf_amd/csrc/mesh_texture.hip): a
+per-triangle atlas whose layout is a function of the triangle count, filled from every view that sees a texel's surface point;
+``write_obj`` writes the result with its material and image.
 """
 import numpy as np
 import torch
@@ -112,9 +116,91 @@ def _auto_bounds(views, fused, counts, rgbs, hw, legacy, min_consistent):
     return box
 
 
+def _texture_block(what, block, power):
+    """the block size and the weight exponent of a texture, checked before anything is launched; block 0 = no texture"""
+    if int(block) != block or not (int(block) == 0 or hip.TEXTURE_MIN_BLOCK <= int(block) <= hip.TEXTURE_MAX_BLOCK):
+        raise ValueError(f"{what}: a texture block of {block!r}; it must be an integer in {hip.TEXTURE_MIN_BLOCK}.."
+                         f"{hip.TEXTURE_MAX_BLOCK} (0: no texture)")
+    if int(power) != power or not 0 <= int(power) <= hip.TEXTURE_MAX_POWER:
+        raise ValueError(f"{what}: a texture power of {power!r}; it must be an integer in 0..{hip.TEXTURE_MAX_POWER}")
+    return int(block), int(power)
+
+
+def _consistent_maps(views, depths, opacities, legacy, px_tol, rel_tol, min_opacity):
+    """``hip.depth_consistency`` with every view as the reference once -> (fused [K, h, w] float32, counts [K, h, w] int32): what the
+    integrator and the texture read instead of the raw maps.  Beyond 16 views a reference is checked against its 15 nearest partners."""
+    k_views, h, w = depths.shape
+    dev = depths.device
+    fused = torch.empty(k_views, h, w, device=dev)
+    counts = torch.empty(k_views, h, w, dtype=torch.int32, device=dev)
+    all_views = hip.view_array(views) if k_views <= hip.MNERF_MAX_VIEWS else None
+    centres = None if all_views is not None else camera_centres(views)
+    for k in range(k_views):
+        if all_views is not None:
+            arr, ref, d, o = all_views, k, depths, opacities
+        else:
+            group = sorted(partners_of(centres, k) + [k])
+            index = torch.as_tensor(group, device=dev)
+            arr, ref = hip.view_array([views[j] for j in group]), group.index(k)
+            d = depths.index_select(0, index)
+            o = None if opacities is None else opacities.index_select(0, index)
+        hip.depth_consistency(arr, ref, d, o, legacy=legacy, px_tol=px_tol, rel_tol=rel_tol, min_opacity=min_opacity,
+                              out=(fused[k], counts[k]))
+    return fused, counts
+
+
+def _bake(vertices, faces, views, maps, map_opacity, counts, min_consistent, rgbs, legacy, min_opacity, block, vis_rel_tol, power, best):
+    """the launches of a texture: uv, one accumulate per group of 16 views on one zeroed buffer, resolve in place -> (uv, atlas)"""
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    n_faces, dev = faces.shape[0], faces.device
+    width, height = hip.mesh_texture_atlas(n_faces, block)
+    uv = hip.mesh_texture_uv(n_faces, block, device=dev)
+    atlas = torch.zeros(height, width, hip.ATLAS_FLOATS, device=dev)
+    for first in range(0, len(views), hip.MNERF_MAX_VIEWS):
+        group = slice(first, min(first + hip.MNERF_MAX_VIEWS, len(views)))
+        hip.mesh_texture_accumulate(vertices, faces, block, views[group], maps[group], rgbs[group], atlas,
+                                    opacity=None if map_opacity is None else map_opacity[group],
+                                    n_consistent=None if counts is None else counts[group], min_consistent=min_consistent, legacy=legacy,
+                                    min_opacity=min_opacity, vis_rel_tol=vis_rel_tol, power=power, best=best)
+    return uv, hip.mesh_texture_resolve(vertices, faces, block, atlas, best=best, out=atlas)
+
+
+def texture(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, block=8, consistency=True, px_tol=1.0, rel_tol=0.01,
+            min_opacity=0.5, min_consistent=None, vis_rel_tol=0.02, power=2, best=False):
+    """Bake a texture atlas for an indexed mesh from K views of its scene (include/mnerf.h "MESH TEXTURE") -> (uv [T, 3, 2] float32: the
+    texture coordinates of every triangle's corners, origin top-left; atlas [H, W, 4] float32 ``r g b a``) on the device.  Every
+    triangle owns a right-triangle patch of a ``block`` x ``block`` square it shares with one other triangle, so the atlas's size is a
+    function of T and ``block`` alone and costs no copy.  A texel takes the frames' colours at its surface point from every view that
+    faces it and SEES it - whose depth map agrees with the point's camera-z within ``vis_rel_tol`` - weighted by cos^``power`` of the
+    angle between the view and the normal (``best``: the single view of the largest weight); where no view sees the surface it falls
+    back to the triangle's vertex colours, with a = 0.  The maps are selected as in ``mesh`` (``consistency``, ``px_tol``, ``rel_tol``,
+    ``min_opacity``, ``min_consistent``); views beyond 16 are accumulated in groups of 16, in order.  No device->host copy; the same
+    bytes on every run."""
+    h, w = int(hw[0]), int(hw[1])
+    n, k_views = h * w, len(views)
+    block, power = _texture_block("texture", block, power)
+    if block == 0:
+        raise ValueError("texture: a block of 0")
+    if k_views < 1 or (consistency and k_views < 2):
+        raise ValueError(f"texture: {k_views} view(s); cross-view consistency needs at least 2")
+    if min_consistent is None:
+        min_consistent = min(2, k_views - 1)
+    depths = depths.reshape(k_views, h, w)
+    opacities = None if opacities is None else opacities.reshape(k_views, h, w)
+    rgbs = rgbs.reshape(k_views, n, 3)
+    if consistency:
+        maps, counts = _consistent_maps(views, depths, opacities, legacy, px_tol, rel_tol, min_opacity)
+        map_opacity = None
+    else:
+        maps, map_opacity, counts, min_consistent = depths, opacities, None, 0
+    return _bake(vertices, faces, views, maps, map_opacity, counts, min_consistent, rgbs, legacy, min_opacity, block, vis_rel_tol, power,
+                 best)
+
+
 def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
          consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None, min_component=0,
-         min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, decimate=0.0):
+         min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, decimate=0.0, texture=0, texture_vis_rel_tol=0.02,
+         texture_power=2, texture_best=False, texture_rgbs=None):
     """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
     fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
     (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
@@ -130,10 +216,15 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
       min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu    ``finish`` applied to the result (one more copy
                     when a component threshold is set)
       decimate      > 0: the finished mesh is decimated (``decimate`` below) with cells of ``decimate`` VOXELS on a grid aligned with the
-                    volume - the same origin, ceil(n / decimate) cells per axis - so no box is copied; one more copy, of the counts"""
+                    volume - the same origin, ceil(n / decimate) cells per axis - so no box is copied; one more copy, of the counts
+      texture       B > 0: -> (vertices, faces, uv, atlas), the FINISHED mesh textured (``texture`` below) with blocks of B texels from
+                    the maps this call selected - the fused depths and counts are computed once - and ``texture_vis_rel_tol``,
+                    ``texture_power``, ``texture_best``; ``texture_rgbs`` [K, h*w, 3]: colours to bake instead of ``rgbs`` (the vertex
+                    colours stay those of ``rgbs``).  No further copy.  0: nothing is launched and the pair is returned"""
     h, w = int(hw[0]), int(hw[1])
     n, k_views = h * w, len(views)
     decimate = _decimate_cell("mesh", decimate)
+    texture, texture_power = _texture_block("mesh", texture, texture_power)
     if k_views < 1 or (consistency and k_views < 2):
         raise ValueError(f"mesh: {k_views} view(s); cross-view consistency needs at least 2")
     if min_consistent is None:
@@ -145,21 +236,7 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
     rgbs = rgbs.reshape(k_views, n, 3)
     dev = depths.device
     if consistency:
-        fused = torch.empty(k_views, h, w, device=dev)
-        counts = torch.empty(k_views, h, w, dtype=torch.int32, device=dev)
-        all_views = hip.view_array(views) if k_views <= hip.MNERF_MAX_VIEWS else None
-        centres = None if all_views is not None else camera_centres(views)
-        for k in range(k_views):
-            if all_views is not None:
-                arr, ref, d, o = all_views, k, depths, opacities
-            else:
-                group = sorted(partners_of(centres, k) + [k])
-                index = torch.as_tensor(group, device=dev)
-                arr, ref = hip.view_array([views[j] for j in group]), group.index(k)
-                d = depths.index_select(0, index)
-                o = None if opacities is None else opacities.index_select(0, index)
-            hip.depth_consistency(arr, ref, d, o, legacy=legacy, px_tol=px_tol, rel_tol=rel_tol, min_opacity=min_opacity,
-                                  out=(fused[k], counts[k]))
+        fused, counts = _consistent_maps(views, depths, opacities, legacy, px_tol, rel_tol, min_opacity)
         maps, map_opacity = fused, None
     else:
         maps, map_opacity, counts, min_consistent = depths, opacities, None, 0
@@ -206,9 +283,14 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
         vertices = torch.empty(n_vertices, hip.VERTEX_FLOATS, device=dev)
         faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
         hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, counts=totals, workspace=workspace)
-    return finish(vertices[:n_vertices], faces[:n_faces], min_component=min_component, min_component_fraction=min_component_fraction,
-                  smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, decimate_cell=decimate * voxel, decimate_origin=origin,
-                  decimate_dims=tuple(int(np.ceil(d / decimate)) for d in dims) if decimate > 0 else None)
+    result = finish(vertices[:n_vertices], faces[:n_faces], min_component=min_component, min_component_fraction=min_component_fraction,
+                    smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, decimate_cell=decimate * voxel, decimate_origin=origin,
+                    decimate_dims=tuple(int(np.ceil(d / decimate)) for d in dims) if decimate > 0 else None)
+    if texture == 0:
+        return result
+    colours = rgbs if texture_rgbs is None else texture_rgbs.reshape(k_views, n, 3)
+    return result + _bake(*result, views, maps, map_opacity, counts, min_consistent, colours, legacy, min_opacity, texture,
+                          texture_vis_rel_tol, texture_power, texture_best)
 
 
 def _decimate_cell(what, cell):
@@ -336,4 +418,49 @@ def write_ply(path, points, faces=None, normals=None):
     with open(path, "wb") as f:
         f.write((header + "end_header\n").encode("ascii"))
         f.write(body)
+    return len(pts)
+
+
+def write_obj(path, vertices, faces, uv, atlas, normals=None):
+    """A textured mesh as Wavefront OBJ: ``path`` (.obj), the same stem + ``.mtl`` and the same stem + ``.png``.
+      vertices [V, >= 3], faces [T, 3], uv [T, 3, 2] and atlas [H, W, >= 3] as ``texture`` returns them (tensors or arrays)
+    The OBJ has ``v`` lines, one ``vt`` per corner with v flipped (OBJ's origin is bottom-left, the atlas's top-left), ``vn`` lines
+    with ``normals`` [V, >= 3], and ``f i/t`` or ``f i/t/n`` (1-based).  The PNG is RGB 8-bit, ``rint(clip * 255)`` as ``write_ply``
+    rounds (PIL writes it).  -> the number of vertices."""
+    import os
+    from PIL import Image
+    host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    pts, tri, tex, img = host(vertices), host(faces).reshape(-1, 3), host(uv).reshape(-1, 3, 2), host(atlas)
+    pts = pts.reshape(-1, pts.shape[-1]) if pts.size else np.zeros((0, 8), np.float32)
+    if len(tex) != len(tri):
+        raise ValueError(f"write_obj: uv {tex.shape} does not match the {len(tri)} faces")
+    if tri.size and (tri.min() < 0 or tri.max() >= len(pts)):
+        raise ValueError(f"write_obj: face indices outside the {len(pts)} vertices")
+    if img.ndim != 3 or img.shape[2] < 3:
+        raise ValueError(f"write_obj: atlas {img.shape} is no [H, W, >= 3] image")
+    nrm = None
+    if normals is not None:
+        nrm = host(normals)
+        nrm = nrm.reshape(-1, nrm.shape[-1]) if nrm.size else np.zeros((0, 4), np.float32)
+        if len(nrm) != len(pts) or nrm.shape[1] < 3:
+            raise ValueError(f"write_obj: normals {nrm.shape} do not match the {len(pts)} vertices")
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    pixels = np.rint(np.clip(np.nan_to_num(img[..., :3].astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+    if pixels.size:
+        Image.fromarray(np.ascontiguousarray(pixels)).save(stem + ".png")
+    else:  # PIL writes no empty image: the atlas of a mesh without faces is one black texel
+        Image.fromarray(np.zeros((1, 1, 3), np.uint8)).save(stem + ".png")
+    with open(stem + ".mtl", "w") as f:
+        f.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {name}.png\n")
+    lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+    lines += ["v %.9g %.9g %.9g" % tuple(float(x) for x in p[:3]) for p in pts]
+    lines += ["vt %.9g %.9g" % (float(c[0]), 1.0 - float(c[1])) for c in tex.reshape(-1, 2)]
+    if nrm is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(float(x) for x in q[:3]) for q in nrm]
+    for t, (a, b, c) in enumerate(tri.tolist()):
+        corner = lambda k, i: f"{i + 1}/{3 * t + k + 1}" + (f"/{i + 1}" if nrm is not None else "")
+        lines.append(f"f {corner(0, a)} {corner(1, b)} {corner(2, c)}")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
     return len(pts)

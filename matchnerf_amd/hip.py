@@ -233,8 +233,13 @@ SIGNATURES = {
     "mnerf_tsdf_integrate": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3 + [_vp] * 3),
     "mnerf_tsdf_mesh_workspace_bytes": (_i64, [_i32] * 3),
     "mnerf_tsdf_mesh": (_int, [_vp] * 2 + [_f32] * 4 + [_i32] * 3 + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
-    # (the two rows of the decimation: the header declares them at the end of MESH FINISHING; here they stand in front of the
-    # section's first six, which tests/test_mesh_finish_cpu.py expects to be the table's last rows)
+    # (the rows of MESH TEXTURE and the two of the decimation: the header declares them after MESH FINISHING's first six; here they
+    # stand in front of those, which tests/test_mesh_finish_cpu.py expects to be the table's last rows)
+    "mnerf_mesh_texture_atlas": (_int, [_i64, _i32, _P(_i32)]),  # size: a host array
+    "mnerf_mesh_texture_uv": (_int, [_i64, _i32, _vp, _vp]),
+    "mnerf_mesh_texture_accumulate": (_int, [_vp, _P(_i32), _i64, _i64, _i32, _P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp]
+                                      + [_f32] * 2 + [_i32] * 2 + [_vp] * 2),
+    "mnerf_mesh_texture_resolve": (_int, [_vp, _P(_i32), _i64, _i64, _i32, _i32] + [_vp] * 3),
     "mnerf_mesh_decimate_workspace_bytes": (_i64, [_i64] * 2 + [_i32] * 3),
     "mnerf_mesh_decimate": (_int, [_vp, _P(_i32), _i64, _i64, _P(_i32), _P(_i32)] + [_f32] * 4 + [_i32] * 3
                             + [_vp, _i64, _P(_i32), _i64, _P(_i32)] + [_vp] * 3),
@@ -1935,3 +1940,94 @@ def mesh_decimate(vertices, triangles, adjacency, origin, cell, dims, vertices_o
                                       triangles_out.numel() // 3, _ptr_i32(vertex_map), _ptr(counts), _ptr(workspace), st),
               "mnerf_mesh_decimate")
     return vertices_out, triangles_out, counts
+
+
+# ----------------------------------------------------------------------- mesh texture (matchnerf_amd/csrc/mesh_texture.hip)
+
+ATLAS_FLOATS = 4  # floats of one texel of an accumulation buffer (r g b | w) or an atlas (r g b a)
+TEXTURE_MIN_BLOCK, TEXTURE_MAX_BLOCK, TEXTURE_MAX_POWER = 4, 64, 8
+
+
+def mesh_texture_atlas(n_triangles, block):
+    """The size (W, H) of the atlas of ``n_triangles`` triangles in blocks of ``block`` texels (mnerf_mesh_texture_atlas: a function
+    of the two numbers only; include/mnerf.h states the layout).  Host only, needs no GPU; MnerfError beyond the header's bounds."""
+    size = (C.c_int32 * 2)()
+    check(load().mnerf_mesh_texture_atlas(int(n_triangles), int(block), size), "mnerf_mesh_texture_atlas")
+    return int(size[0]), int(size[1])
+
+
+def _texture_args(what, vertices, triangles, block, buffers):
+    """the checks of ``_mesh_args`` plus the atlas: every tensor of ``buffers`` (name -> tensor) is a float32 [H, W, 4] buffer on the
+    mesh's device -> (device, V, T, (W, H))"""
+    import torch
+    dev, nv, nt = _mesh_args(what, vertices, triangles)
+    width, height = mesh_texture_atlas(nt, block)
+    for name, t in buffers.items():
+        _mesh_buffer(what, name, t, torch.float32, height * width * ATLAS_FLOATS, dev)
+    return dev, nv, nt, (width, height)
+
+
+def mesh_texture_uv(n_triangles, block, device=None, out=None, stream=None):
+    """The texture coordinates of every triangle's corners (mnerf_mesh_texture_uv) -> [T, 3, 2] float32, (x / W, y / H) with the origin
+    at the top-left of the atlas.  ``out``: the tensor to write into (``device`` is then its device).  Enqueue only."""
+    import torch
+    lib = load()
+    n_triangles = int(n_triangles)
+    mesh_texture_atlas(n_triangles, block)  # the bounds
+    dev = out.device if out is not None else torch.device(_current_device() if device is None else device)
+    if dev.type != "cuda":
+        raise MnerfError(f"mesh_texture_uv: uv lies on {dev}; it is written on the GPU")
+    out = _mesh_buffer("mesh_texture_uv", "uv", out, torch.float32, 6 * n_triangles, dev).view(n_triangles, 3, 2)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_texture_uv(n_triangles, int(block), _ptr(out), st), "mnerf_mesh_texture_uv")
+    return out
+
+
+def mesh_texture_accumulate(vertices, triangles, block, views, depth, rgb, accum, opacity=None, n_consistent=None, min_consistent=0,
+                            legacy=True, min_opacity=0.5, vis_rel_tol=0.02, power=2, best=False, stream=None):
+    """Add up to MNERF_MAX_VIEWS views to the accumulation buffer of a mesh's atlas (mnerf_mesh_texture_accumulate; the visibility
+    test and the weights are stated in include/mnerf.h).  ``vertices`` [V, 8] / ``triangles`` [T, 3] as for ``mesh_normals``;
+    ``views``, ``depth`` [K, h, w], ``opacity``, ``n_consistent``, ``rgb`` [K, h*w, 3] as for ``tsdf_integrate``; ``accum`` [H, W, 4]
+    float32 of ``mesh_texture_atlas(T, block)``, the caller's, zeroed before the first call; calls accumulate.  ``power`` 0..8: the
+    weight of a view is cos^power of its angle to the normal; ``best``: keep the view of the largest weight instead of the weighted
+    sum.  Enqueue only: -> accum."""
+    import torch
+    lib = load()
+    dev, nv, nt, _ = _texture_args("mesh_texture_accumulate", vertices, triangles, block, dict(accum=accum))
+    _f32c(depth, "depth"), _f32c(rgb, "rgb")
+    if depth.dim() != 3 or depth.shape[0] != len(views) or depth.device != dev:
+        raise MnerfError(f"mesh_texture_accumulate: depth {tuple(depth.shape)} on {depth.device} is not [{len(views)}, h, w] on {dev}")
+    k, h, w = (int(x) for x in depth.shape)
+    if rgb.numel() != 3 * depth.numel() or rgb.device != dev:
+        raise MnerfError(f"mesh_texture_accumulate: rgb {tuple(rgb.shape)} on {rgb.device} is not [{k}, {h * w}, 3] on {dev}")
+    if opacity is not None and (_f32c(opacity, "opacity").shape != depth.shape or opacity.device != dev):
+        raise MnerfError(f"mesh_texture_accumulate: opacity {tuple(opacity.shape)} on {opacity.device} does not match depth "
+                         f"{tuple(depth.shape)}")
+    if n_consistent is not None and (n_consistent.dtype != torch.int32 or n_consistent.numel() != depth.numel()
+                                     or not n_consistent.is_contiguous() or n_consistent.device != dev):
+        raise MnerfError(f"mesh_texture_accumulate: n_consistent must be a contiguous int32 tensor of {depth.numel()} elements on {dev}")
+    if int(power) != power or not 0 <= int(power) <= TEXTURE_MAX_POWER:
+        raise MnerfError(f"mesh_texture_accumulate: power={power!r} is no integer in 0..{TEXTURE_MAX_POWER}")
+    arr = views if isinstance(views, C.Array) else view_array(views)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_texture_accumulate(_ptr(vertices), _ptr_i32(triangles), nv, nt, int(block), arr, k, h, w, int(bool(legacy)),
+                                                _ptr(depth), _ptr(opacity), _ptr_i32(n_consistent), int(min_consistent), _ptr(rgb),
+                                                float(min_opacity), float(vis_rel_tol), int(power), int(bool(best)), _ptr(accum), st),
+              "mnerf_mesh_texture_accumulate")
+    return accum
+
+
+def mesh_texture_resolve(vertices, triangles, block, accum, best=False, out=None, stream=None):
+    """The atlas of an accumulation buffer (mnerf_mesh_texture_resolve) -> [H, W, 4] float32 ``r g b a``: the weighted mean (``best``:
+    the stored colour) with a = 1 where a view saw the surface, the blend of the triangle's vertex colours with a = 0 where none did,
+    zeros where no triangle owns the texel.  ``out`` may be ``accum`` (in place); default a new tensor.  Enqueue only."""
+    import torch
+    lib = load()
+    buffers = dict(accum=accum) if out is None else dict(accum=accum, atlas=out)
+    dev, nv, nt, (width, height) = _texture_args("mesh_texture_resolve", vertices, triangles, block, buffers)
+    if out is None:
+        out = torch.zeros(height, width, ATLAS_FLOATS, device=dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_texture_resolve(_ptr(vertices), _ptr_i32(triangles), nv, nt, int(block), int(bool(best)), _ptr(accum),
+                                             _ptr(out), st), "mnerf_mesh_texture_resolve")
+    return out.view(height, width, ATLAS_FLOATS)

@@ -553,23 +553,48 @@ class MatchNeRF(torch.nn.Module):
     MESH_ARGS = ("bounds", "resolution", "voxel", "trunc", "min_weight", "consistency", "min_component", "min_component_fraction", "smooth",
                  "smooth_lambda", "smooth_mu", "decimate")
 
-    def export_mesh(self, batch, views="sources", render_path_mode="interpolate", normals=False, **mesh_args):
+    @staticmethod
+    def check_texture(who, block, power, source, views):
+        """the refusals of a texture request, before anything is rendered -> (block, power)"""
+        from . import fusion
+        block, power = fusion._texture_block(who, block, power)
+        if source not in ("render", "images"):
+            raise ValueError(f"{who}: texture_from={source!r}: 'render' or 'images'")
+        if block and source == "images" and not (isinstance(views, str) and views == "sources"):
+            raise ValueError(f"{who}: texture_from='images' bakes the source photographs, so it needs views='sources', not {views!r}")
+        return block, power
+
+    def source_colours(self, batch):
+        """the source photographs as the colours of the 'sources' fusion views -> [B, K, h*w, 3] float32"""
+        images = batch.images[:, :self.n_src_views]
+        b, k = images.shape[:2]
+        return images.permute(0, 1, 3, 4, 2).reshape(b, k, -1, 3).float().contiguous()
+
+    def export_mesh(self, batch, views="sources", render_path_mode="interpolate", normals=False, texture=0, texture_best=False,
+                    texture_power=2, texture_vis_rel_tol=0.02, texture_from="render", **mesh_args):
         """The scene of ``batch`` as coloured triangle meshes -> a list over the batch of (vertices [V, 8] float32 rows
         ``x y z w | r g b 0``, faces [T, 3] int32) on the device (``fusion.mesh``: the depth maps of ``export_points`` fused into a
         truncated-signed-distance volume, its zero surface extracted by marching tetrahedra).  ``views`` and the one encoder pass as
         in ``export_points``; ``mesh_args``: bounds, resolution, voxel, trunc, min_weight, consistency, the clean-up of
         ``fusion.finish`` (min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu), ``decimate`` (the cell of
         ``fusion.decimate`` in voxels, applied last; 0: none) and the thresholds of ``export_points``.  ``normals=True``: triples (vertices, faces, normals [V, 4] float32 rows ``nx ny nz a``,
-        ``fusion.vertex_normals`` of the finished mesh).  The same refusals, before the first launch."""
+        ``fusion.vertex_normals`` of the finished mesh).  ``texture=B`` (4..64): the tuples grow by (uv [T, 3, 2], atlas [H, W, 4]) at
+        the end - the finished mesh textured with blocks of B texels (``fusion.texture``; ``texture_best``, ``texture_power``,
+        ``texture_vis_rel_tol``).  ``texture_from``: "render" bakes the frames rendered at the fusion poses, "images" - with
+        ``views="sources"`` only - the source photographs ``batch.images`` instead of their re-renderings; the visibility test uses
+        the rendered depth either way.  The same refusals, and those of a bad block, power or source, before the first launch."""
         from . import fusion
         unknown = set(mesh_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"} - set(self.MESH_ARGS)
         fusion._decimate_cell("export_mesh", mesh_args.get("decimate", 0.0))
+        texture, texture_power = self.check_texture("export_mesh", texture, texture_power, texture_from, views)
         maps, cams_of = self._fusion_maps("export_mesh", batch, views, render_path_mode, unknown)
         legacy = bool(self.opts.nerf.legacy_coord)
-        meshes = [fusion.mesh(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, **mesh_args)
-                  for b, cams in enumerate(cams_of)]
+        photos = self.source_colours(batch) if texture and texture_from == "images" else None
+        meshes = [fusion.mesh(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, texture=texture, texture_best=texture_best,
+                              texture_power=texture_power, texture_vis_rel_tol=texture_vis_rel_tol,
+                              texture_rgbs=None if photos is None else photos[b], **mesh_args) for b, cams in enumerate(cams_of)]
         if normals:
-            return [(vertices, faces, fusion.vertex_normals(vertices, faces)) for vertices, faces in meshes]
+            return [(vertices, faces, fusion.vertex_normals(vertices, faces), *textured) for vertices, faces, *textured in meshes]
         return meshes
 
     def _fusion_maps(self, who, batch, views, render_path_mode, unknown):

@@ -33,9 +33,16 @@ maps, ``<stem>_mesh.ply`` (TSDF fusion, marching tetrahedra): ``--nerf.mesh_reso
 ``--nerf.mesh_min_component=<triangles>`` / ``--nerf.mesh_min_component_fraction=<of the largest component>`` (smaller connected
 components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, then reduced by ``--nerf.mesh_decimate=<cell in voxels>``
 (quadric vertex clustering: one vertex per occupied cell), and ``--nerf.mesh_normals`` adds ``nx ny nz`` per vertex.
+``--nerf.mesh_texture=<block in texels, 4..64>`` also writes the finished mesh with a texture atlas baked from the views,
+``<stem>_mesh.obj`` / ``.mtl`` / ``.png`` next to ``<stem>_mesh.ply``: ``--nerf.mesh_texture_power=<0..8>`` (2: a view weighs
+cos^power of its angle to the surface normal), ``--nerf.mesh_texture_best`` (the single best view per texel instead of the
+weighted mean), ``--nerf.mesh_texture_rel_tol=<relative depth>`` (0.02: how closely a view's depth map must agree with a surface
+point to count as seeing it), ``--nerf.mesh_texture_from=render|images`` (``images``: the source photographs instead of their
+re-renderings; with ``--nerf.export_geometry=sources`` only).
 
     python test.py --yaml=demo_own --nerf.export_geometry=sources
-    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192"""
+    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192
+    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_decimate=4 --nerf.mesh_texture=8"""
 import os
 import sys
 
