@@ -1,5 +1,11 @@
-// K6 — GMFlow single-head (shifted-)window attention, flash style, on the matrix pipe (gfx950):
-// exact-f32 MFMA kernel and, by default, a split-bf16 variant (second half of this file).
+// K6 — GMFlow single-head (shifted-)window attention, flash style, on the matrix pipe (gfx950).
+//   window_attention_pre_kernel             the default (MNERF_WA_MATH=f16pre): split-fp16 products on K / V operand images
+//                                           prepared once per call (wa_presplit_kernel here, or the q|k|v kernel of qkv.hip)
+//   window_attention_kernel<NQW, MATH>      one flash loop for the three arithmetics that read fp32 K / V tiles: exact-f32
+//                                           MFMA (the parity baseline), split-bf16 (six products), split-fp16 (three products).
+//                                           A WaMath<MATH> policy supplies the four places where they differ: how the query
+//                                           is held, the score product, the PV product with its accumulator correction, and
+//                                           the final scale.
 //
 // Replaces (paths relative to /root/reference/models/gmflow):
 //   transformer.py:8-16    single_head_full_attention   (num_splits == 1)
@@ -29,39 +35,6 @@
 #include "wa_common.hpp"
 #include "launch_plan.hpp"
 
-// ---- LDS-DMA helpers (see decoder_common.hpp: an asm global_load_lds is invisible to hipcc's
-// wait-count bookkeeping, so the prefetch of tile t+1 is not drained in front of tile t's reads)
-__device__ __forceinline__ void wa_glds16(const float* gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-
-// four consecutive 1-KiB pieces per M0 write: the instruction offset moves the global AND the LDS address of an LDS-DMA load
-// (split_f16.hpp: glds16_sv4; tools/exp/ubench/dma_issue.hip: 40-43 instead of 74-78 cycles of issue per request)
-__device__ __forceinline__ void wa_glds16x4(const float* gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "global_load_lds_dwordx4 %1, off offset:1024\n\t"
-      "global_load_lds_dwordx4 %1, off offset:2048\n\t"
-      "global_load_lds_dwordx4 %1, off offset:3072\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-
 // One K/V tile = 32 keys x 128 channels of each matrix = 2 x 16 KiB, copied as 32 pieces of
 // 1 KiB (one wave instruction = 2 token rows).  V keeps its natural row-major image.  K is
 // swizzled on the SOURCE side: the 16-byte column group c4 of LDS row `key` holds channels
@@ -81,38 +54,74 @@ __device__ __forceinline__ void wa_stage_tile(const float* __restrict__ k, const
     int reg_unused;
     const int tok = win_token(G, wy, wx, li, reg_unused);
     const size_t row = seq_base + (size_t)tok * WA_C;
-    wa_glds16(k + row + ((c4 ^ (key & 31)) << 2), __builtin_amdgcn_readfirstlane(kb + (unsigned)piece * 1024u));
-    wa_glds16(v + row + (c4 << 2), __builtin_amdgcn_readfirstlane(vb + (unsigned)piece * 1024u));
+    glds16(k + row + ((c4 ^ (key & 31)) << 2), __builtin_amdgcn_readfirstlane(kb + (unsigned)piece * 1024u));
+    glds16(v + row + (c4 << 2), __builtin_amdgcn_readfirstlane(vb + (unsigned)piece * 1024u));
   }
 }
 
-template <int NQW>
-__global__ __launch_bounds__(NQW * 64, 2) void window_attention_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-    float* __restrict__ out, WinGeom G, int shifted, float scale) {
-  // double-buffered K and V tiles: [2][32 keys][128] each = 64 KiB per workgroup
-  extern __shared__ __attribute__((aligned(16))) float wa_smem[];
-#define WA_KBUF(i) (wa_smem + (i) * (WA_KT * WA_C))
-#define WA_VBUF(i) (wa_smem + (2 + (i)) * (WA_KT * WA_C))
+// ---- pieces shared by the kernels of this file
+// the eight operand values a lane supplies to one K16-step: two 16-byte reads
+__device__ __forceinline__ void wa_load8(float (&d)[8], const float* a, const float* c) {
+  const float4 x = *reinterpret_cast<const float4*>(a), y = *reinterpret_cast<const float4*>(c);
+  d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
+  d[4] = y.x; d[5] = y.y; d[6] = y.z; d[7] = y.w;
+}
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 31, hl = lane >> 5;
-  const int win = blockIdx.y, b = blockIdx.z;
-  const int wy = win / G.splits, wx = win - wy * G.splits;
-  const size_t seq_base = (size_t)b * G.h * G.w * WA_C;
+// gain exponent of a 32-key K or V tile from each lane's absolute maximum: the wave's 64 lanes hold the tile exactly once
+__device__ __forceinline__ int wa_tile_gain_exp(float lane_absmax) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lane_absmax = fmaxf(lane_absmax, __shfl_xor(lane_absmax, off, 64));
+  return gain_exp(lane_absmax);
+}
 
-  const int n_tiles = (G.Lw + WA_KT - 1) / WA_KT;
-  wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, 0, WA_KBUF(0), WA_VBUF(0), wave, lane);
+// a query row as the B operand of the split-fp16 score product (K16-step t holds channels 16t + 8 hl + j), split once
+// with one gain per query (both half-waves of the lane pair see all 128 channels) -> the gain exponent
+__device__ __forceinline__ int wa_query_split_h(const float* qrow, int hl, PartsH (&qp)[8]) {
+  const float* src = qrow + hl * 8;
+  float qv[8][8];
+  float qmax = 0.0f;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) wa_load8(qv[t], src + 16 * t, src + 16 * t + 4);
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qmax = fmaxf(qmax, fabsf(qv[t][j]));
+  qmax = fmaxf(qmax, __shfl_xor(qmax, 32, 64));
+  const int eq = gain_exp(qmax);
+  const float mq = pow2i(eq);
+#pragma unroll
+  for (int t = 0; t < 8; ++t) qp[t] = split8h(qv[t], mq);
+  return eq;
+}
 
-  // ---- this lane's query (half-wave hl holds channels [64 hl, 64 hl + 64))
-  const int qi_raw = (blockIdx.x * NQW + wave) * 32 + n;
-  const bool q_ok = qi_raw < G.Lw;
-  int q_region;
-  const int q_tok = win_token(G, wy, wx, q_ok ? qi_raw : (G.Lw - 1), q_region);
-  float qreg[64];
-  {
-    const float4* src = reinterpret_cast<const float4*>(q + seq_base + (size_t)q_tok * WA_C + hl * 64);
+// normalise and store a query's output row: register quad (4g..4g+3) of block m = channels m*32+8g+4hl+{0..3}
+__device__ __forceinline__ void wa_store_out(float* dst, const f32x16 (&o)[4], float inv_l, int hl) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const float4 t = make_float4(o[m][4 * g4] * inv_l, o[m][4 * g4 + 1] * inv_l,
+                                   o[m][4 * g4 + 2] * inv_l, o[m][4 * g4 + 3] * inv_l);
+      *reinterpret_cast<float4*>(dst + m * 32 + 8 * g4 + 4 * hl) = t;
+    }
+}
+
+// ---- the arithmetics of window_attention_kernel.  A policy holds the query operand and supplies
+//   load_query(qrow, hl)                     this lane's query row -> B operand of the score product
+//   scores(kbuf, n, hl, scale, s)            s = S^T = K Q^T of the tile in LDS; -> the factor that turns s into scaled scores
+//   accumulate(o, p, alpha, vbuf, n, hl)     O^T = O^T * (softmax correction alpha) + V^T P^T
+//   final_scale()                            what the accumulators are multiplied by besides 1 / (row sum)
+// Score register r of lane (n, hl) belongs to key (r & 3) + 8 (r >> 2) + 4 hl of the tile.
+template <int MATH>
+struct WaMath;
+
+// exact-f32 MFMA (v_mfma_f32_32x32x2_f32): the formulation of the file header
+template <>
+struct WaMath<MNERF_WA_EXACT_F32> {
+  float qreg[64];  // half-wave hl holds channels [64 hl, 64 hl + 64)
+
+  __device__ __forceinline__ void load_query(const float* qrow, int hl) {
+    const float4* src = reinterpret_cast<const float4*>(qrow + hl * 64);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const float4 t = src[i];
@@ -122,95 +131,41 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_kernel(
       qreg[4 * i + 3] = t.w;
     }
   }
-  f32x16 o[4];
+  // 64 K-steps over d on ONE accumulator; one swizzled ds_read_b128 feeds 4 steps
+  __device__ __forceinline__ float scores(const float* kbuf, int n, int hl, float scale, f32x16& s) const {
+    s = (f32x16)(0.0f);
+    const float* krow = kbuf + n * WA_C;
 #pragma unroll
-  for (int m = 0; m < 4; ++m) o[m] = (f32x16)(0.0f);
-  float m_run = -3.0e38f, l_run = 0.0f;
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < n_tiles; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < n_tiles)  // DMA of the next tile overlaps this tile's 128 MFMAs
-      wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, kt + 1, WA_KBUF(cur ^ 1), WA_VBUF(cur ^ 1), wave, lane);
-
-    // ---- S^T = K Q^T  (64 K-steps over d; one swizzled ds_read_b128 feeds 4 steps)
-    f32x16 s = (f32x16)(0.0f);
-    {
-      const float* krow = WA_KBUF(cur) + n * WA_C;
-#pragma unroll
-      for (int q4 = 0; q4 < 16; ++q4) {
-        const float4 ka = *reinterpret_cast<const float4*>(krow + (((hl * 16 + q4) ^ n) << 2));
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.x, qreg[4 * q4 + 0], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.y, qreg[4 * q4 + 1], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.z, qreg[4 * q4 + 2], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.w, qreg[4 * q4 + 3], s, 0, 0, 0);
-      }
+    for (int q4 = 0; q4 < 16; ++q4) {
+      const float4 ka = *reinterpret_cast<const float4*>(krow + (((hl * 16 + q4) ^ n) << 2));
+      s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.x, qreg[4 * q4 + 0], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.y, qreg[4 * q4 + 1], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.z, qreg[4 * q4 + 2], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.w, qreg[4 * q4 + 3], s, 0, 0, 0);
     }
-    // ---- scale, masks, online softmax
-    float tmax = -3.0e38f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
-      const int li = kt * WA_KT + key;
-      float sv = s[r] * scale;
-      if (shifted) {
-        int kreg;
-        (void)win_token(G, wy, wx, li < G.Lw ? li : (G.Lw - 1), kreg);
-        if (kreg != q_region) sv += -100.0f;
-      }
-      if (li >= G.Lw) sv = -3.0e38f;
-      s[r] = sv;
-      tmax = fmaxf(tmax, sv);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = __expf(m_run - m_new);
-    float psum = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float p = __expf(s[r] - m_new);
-      s[r] = p;
-      psum += p;
-    }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
+    return scale;
+  }
+  // 16 K-steps over the tile's keys, 4 M-blocks over d
+  __device__ __forceinline__ void accumulate(f32x16 (&o)[4], const f32x16& p, float alpha, const float* vbuf, int n, int hl) {
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[m][r] *= alpha;
-    // ---- O^T += V^T P^T  (16 K-steps over the tile's keys, 4 M-blocks over d)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
-      const float* va = WA_VBUF(cur) + key * WA_C + n;
-      o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[0], s[r], o[0], 0, 0, 0);
-      o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[32], s[r], o[1], 0, 0, 0);
-      o[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[64], s[r], o[2], 0, 0, 0);
-      o[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[96], s[r], o[3], 0, 0, 0);
+      const float* va = vbuf + key * WA_C + n;
+      o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[0], p[r], o[0], 0, 0, 0);
+      o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[32], p[r], o[1], 0, 0, 0);
+      o[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[64], p[r], o[2], 0, 0, 0);
+      o[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[96], p[r], o[3], 0, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // next tile landed (this wave's pieces)
-    __syncthreads();                                   // ... all waves' pieces; current tile consumed
   }
-  // ---- normalise and store: register quad (4g..4g+3) of block m = channels m*32+8g+4hl+{0..3}
-  if (q_ok) {
-    const float inv_l = 1.0f / l_run;
-    float* dst = out + seq_base + (size_t)q_tok * WA_C;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 t = make_float4(o[m][4 * g4] * inv_l, o[m][4 * g4 + 1] * inv_l,
-                                     o[m][4 * g4 + 2] * inv_l, o[m][4 * g4 + 3] * inv_l);
-        *reinterpret_cast<float4*>(dst + m * 32 + 8 * g4 + 4 * hl) = t;
-      }
-  }
-}
+  __device__ __forceinline__ float final_scale() const { return 1.0f; }
+};
 
-// ============================================================================ split-bf16 variant
-// Same flash-style loop with the products on v_mfma_f32_32x32x16_bf16: every fp32 operand is split into
+// ---- split-bf16
+// The products on v_mfma_f32_32x32x16_bf16: every fp32 operand is split into
 // three bf16 terms and a product is accumulated in fp32 from six terms (decoder_common.hpp, "split-bf16 matrix
 // path": fp32-grade results at 16/6 of the f32 matrix rate).  Q is split once per workgroup and kept in
 // 96 VGPRs; K and V fragments are split as they are read from the fp32 LDS tiles; P is split straight
@@ -268,105 +223,47 @@ __device__ __forceinline__ f32x16 wa_mac6(const WaParts& a, const WaParts& b, f3
   return acc;
 }
 
-template <int NQW>
-__global__ __launch_bounds__(NQW * 64, 2) void window_attention_bf16_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-    float* __restrict__ out, WinGeom G, int shifted, float scale) {
-  extern __shared__ __attribute__((aligned(16))) float wa_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 31, hl = lane >> 5;
-  const int win = blockIdx.y, b = blockIdx.z;
-  const int wy = win / G.splits, wx = win - wy * G.splits;
-  const size_t seq_base = (size_t)b * G.h * G.w * WA_C;
+template <>
+struct WaMath<MNERF_WA_SPLIT_BF16> {
+  WaParts qp[8];  // split once: K-step t holds channels 16t + 8 hl + j
 
-  const int n_tiles = (G.Lw + WA_KT - 1) / WA_KT;
-  wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, 0, WA_KBUF(0), WA_VBUF(0), wave, lane);
-
-  // ---- this lane's query, split once: K-step t holds channels 16t + 8 hl + j
-  const int qi_raw = (blockIdx.x * NQW + wave) * 32 + n;
-  const bool q_ok = qi_raw < G.Lw;
-  int q_region;
-  const int q_tok = win_token(G, wy, wx, q_ok ? qi_raw : (G.Lw - 1), q_region);
-  WaParts qp[8];
-  {
-    const float4* src = reinterpret_cast<const float4*>(q + seq_base + (size_t)q_tok * WA_C + hl * 8);
+  __device__ __forceinline__ void load_query(const float* qrow, int hl) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      const float4 a = src[4 * t], c = src[4 * t + 1];
-      const float qv[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+      float qv[8];
+      wa_load8(qv, qrow + 16 * t + 8 * hl, qrow + 16 * t + 8 * hl + 4);
       qp[t] = wa_split8(qv);
     }
   }
-  f32x16 o[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) o[m] = (f32x16)(0.0f);
-  float m_run = -3.0e38f, l_run = 0.0f;
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < n_tiles; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < n_tiles)
-      wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, kt + 1, WA_KBUF(cur ^ 1), WA_VBUF(cur ^ 1), wave, lane);
-    // ---- S^T = K Q^T: 8 K16-steps over d, two accumulators so that consecutive MFMA groups are independent
+  // 8 K16-steps over d, two accumulators so that consecutive MFMA groups are independent
+  __device__ __forceinline__ float scores(const float* kbuf, int n, int hl, float scale, f32x16& s) const {
     f32x16 s0 = (f32x16)(0.0f), s1 = (f32x16)(0.0f);
-    {
-      const float* krow = WA_KBUF(cur) + n * WA_C;
+    const float* krow = kbuf + n * WA_C;
 #pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int c4 = 4 * t + 2 * hl;  // 16-byte column groups of channels 16t + 8hl .. + 7 (swizzled by the key)
-        const float4 a = *reinterpret_cast<const float4*>(krow + ((c4 ^ n) << 2));
-        const float4 c = *reinterpret_cast<const float4*>(krow + (((c4 + 1) ^ n) << 2));
-        const float kv[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-        const WaParts kp = wa_split8(kv);
-        if (t & 1)
-          s1 = wa_mac6(kp, qp[t], s1);
-        else
-          s0 = wa_mac6(kp, qp[t], s0);
-      }
+    for (int t = 0; t < 8; ++t) {
+      const int c4 = 4 * t + 2 * hl;  // 16-byte column groups of channels 16t + 8hl .. + 7 (swizzled by the key)
+      float kv[8];
+      wa_load8(kv, krow + ((c4 ^ n) << 2), krow + (((c4 + 1) ^ n) << 2));
+      const WaParts kp = wa_split8(kv);
+      if (t & 1)
+        s1 = wa_mac6(kp, qp[t], s1);
+      else
+        s0 = wa_mac6(kp, qp[t], s0);
     }
-    f32x16 s = s0 + s1;
-    // ---- scale, masks, online softmax (as in the f32 kernel)
-    float tmax = -3.0e38f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
-      const int li = kt * WA_KT + key;
-      float sv = s[r] * scale;
-      if (shifted) {
-        int kreg;
-        (void)win_token(G, wy, wx, li < G.Lw ? li : (G.Lw - 1), kreg);
-        if (kreg != q_region) sv += -100.0f;
-      }
-      if (li >= G.Lw) sv = -3.0e38f;
-      s[r] = sv;
-      tmax = fmaxf(tmax, sv);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = __expf(m_run - m_new);
-    float psum = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float p = __expf(s[r] - m_new);
-      s[r] = p;
-      psum += p;
-    }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
+    s = s0 + s1;
+    return scale;
+  }
+  // 2 K16-steps over the tile's keys (score registers 8t..8t+7), 4 M-blocks over d
+  __device__ __forceinline__ void accumulate(f32x16 (&o)[4], const f32x16& p, float alpha, const float* vbuf, int n, int hl) {
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[m][r] *= alpha;
-    // ---- O^T += V^T P^T: 2 K16-steps over the tile's keys (score registers 8t..8t+7), 4 M-blocks over d
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       float pv[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pv[j] = s[8 * t + j];
+      for (int j = 0; j < 8; ++j) pv[j] = p[8 * t + j];
       const WaParts pp = wa_split8(pv);
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -375,30 +272,17 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_bf16_kernel(
         for (int j = 0; j < 8; ++j) {
           const int r = 8 * t + j;
           const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
-          vv[j] = WA_VBUF(cur)[key * WA_C + 32 * m + n];
+          vv[j] = vbuf[key * WA_C + 32 * m + n];
         }
         o[m] = wa_mac6(wa_split8(vv), pp, o[m]);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
   }
-  if (q_ok) {
-    const float inv_l = 1.0f / l_run;
-    float* dst = out + seq_base + (size_t)q_tok * WA_C;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 t = make_float4(o[m][4 * g4] * inv_l, o[m][4 * g4 + 1] * inv_l,
-                                     o[m][4 * g4 + 2] * inv_l, o[m][4 * g4 + 3] * inv_l);
-        *reinterpret_cast<float4*>(dst + m * 32 + 8 * g4 + 4 * hl) = t;
-      }
-  }
-}
+  __device__ __forceinline__ float final_scale() const { return 1.0f; }
+};
 
-// ============================================================================ split-fp16 variant
-// The same loop on v_mfma_f32_32x32x16_f16 with two range-managed fp16 terms per operand and three products per MAC
+// ---- split-fp16
+// The products on v_mfma_f32_32x32x16_f16 with two range-managed fp16 terms per operand and three products per MAC
 // (split_f16.hpp, "split-fp16 matrix path"): half the matrix instructions of the split-bf16 variant and
 // less than half of its operand-split VALU work.  NOT the default: the tile maxima have to be known before the first
 // product of a tile (read the whole tile, reduce across the wave, then split), which serialises a loop that is
@@ -410,11 +294,100 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_bf16_kernel(
 // The score accumulator is un-scaled per lane (2^-(eq + ek) folded into the softmax scale); the output accumulator
 // carries the V gain of the tile it was last updated with, and the change of gain from tile to tile rides in the
 // multiplication by the softmax correction factor that happens anyway.
-template <int NQW>
-__global__ __launch_bounds__(NQW * 64, 2) void window_attention_f16_kernel(
+template <>
+struct WaMath<MNERF_WA_SPLIT_F16> {
+  PartsH qp[8];
+  int eq;
+  int ev_run = 0;  // V gain exponent the output accumulator currently carries (irrelevant while o == 0)
+
+  __device__ __forceinline__ void load_query(const float* qrow, int hl) { eq = wa_query_split_h(qrow, hl, qp); }
+  // the wave's 64 lanes hold the 32 x 128 K tile exactly once (lane = key row, half = channel half of every K16-step):
+  // tile maximum -> one gain; then 8 K16-steps over d, products hi.lo, lo.hi, hi.hi on two alternating accumulators
+  __device__ __forceinline__ float scores(const float* kbuf, int n, int hl, float scale, f32x16& s) const {
+    f32x16 s0 = (f32x16)(0.0f), s1 = (f32x16)(0.0f);
+    const float* krow = kbuf + n * WA_C;
+    float kv[8][8];
+    float kmax = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int c4 = 4 * t + 2 * hl;  // 16-byte column groups of channels 16t + 8hl .. + 7 (swizzled by the key)
+      wa_load8(kv[t], krow + ((c4 ^ n) << 2), krow + (((c4 + 1) ^ n) << 2));
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) kmax = fmaxf(kmax, fabsf(kv[t][j]));
+    const int ek = wa_tile_gain_exp(kmax);
+    const float mk = pow2i(ek);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const PartsH kp = split8h(kv[t], mk);
+      if (t & 1) {
+        s1 = mfma16h(kp.hi, qp[t].lo, s1);
+        s1 = mfma16h(kp.lo, qp[t].hi, s1);
+        s1 = mfma16h(kp.hi, qp[t].hi, s1);
+      } else {
+        s0 = mfma16h(kp.hi, qp[t].lo, s0);
+        s0 = mfma16h(kp.lo, qp[t].hi, s0);
+        s0 = mfma16h(kp.hi, qp[t].hi, s0);
+      }
+    }
+    s = s0 + s1;
+    return scale * pow2i(-(ek + eq));
+  }
+  // the lanes' 2 x 4 x 8 V values are the whole tile once more -> tile maximum -> gain; the softmax correction and the
+  // change of V gain are one multiplication
+  __device__ __forceinline__ void accumulate(f32x16 (&o)[4], const f32x16& p, float alpha, const float* vbuf, int n, int hl) {
+    float vv[2][4][8];
+    float vmax = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int r = 8 * t + j;
+          const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
+          const float x = vbuf[key * WA_C + 32 * m + n];
+          vv[t][m][j] = x;
+          vmax = fmaxf(vmax, fabsf(x));
+        }
+    const int ev = wa_tile_gain_exp(vmax);
+    const float mv = pow2i(ev);
+    const float corr = alpha * pow2i(ev - ev_run);
+    ev_run = ev;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[m][r] *= corr;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float pv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = p[8 * t + j];
+      const PartsH pp = split8h(pv, 16384.0f);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const PartsH vp = split8h(vv[t][m], mv);
+        o[m] = mfma16h(vp.hi, pp.lo, o[m]);
+        o[m] = mfma16h(vp.lo, pp.hi, o[m]);
+        o[m] = mfma16h(vp.hi, pp.hi, o[m]);
+      }
+    }
+  }
+  __device__ __forceinline__ float final_scale() const { return pow2i(-(ev_run + 14)); }  // V gain of the last tile, P gain 2^14
+};
+
+// ---- the flash loop: K/V tiles double-buffered in LDS, one barrier per tile, online softmax per query lane pair
+template <int NQW, int MATH>
+__global__ __launch_bounds__(NQW * 64, 2) void window_attention_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     float* __restrict__ out, WinGeom G, int shifted, float scale) {
+  // double-buffered K and V tiles: [2][32 keys][128] each = 64 KiB per workgroup
   extern __shared__ __attribute__((aligned(16))) float wa_smem[];
+#define WA_KBUF(i) (wa_smem + (i) * (WA_KT * WA_C))
+#define WA_VBUF(i) (wa_smem + (2 + (i)) * (WA_KT * WA_C))
+
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 31, hl = lane >> 5;
@@ -425,91 +398,30 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_f16_kernel(
   const int n_tiles = (G.Lw + WA_KT - 1) / WA_KT;
   wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, 0, WA_KBUF(0), WA_VBUF(0), wave, lane);
 
-  // ---- this lane's query, split once: K-step t holds channels 16t + 8 hl + j
+  // ---- this lane's query
   const int qi_raw = (blockIdx.x * NQW + wave) * 32 + n;
   const bool q_ok = qi_raw < G.Lw;
   int q_region;
   const int q_tok = win_token(G, wy, wx, q_ok ? qi_raw : (G.Lw - 1), q_region);
-  PartsH qp[8];
-  int eq;
-  {
-    const float4* src = reinterpret_cast<const float4*>(q + seq_base + (size_t)q_tok * WA_C + hl * 8);
-    float qv[64];
-    float qmax = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 a = src[4 * t], c = src[4 * t + 1];
-      qv[8 * t + 0] = a.x; qv[8 * t + 1] = a.y; qv[8 * t + 2] = a.z; qv[8 * t + 3] = a.w;
-      qv[8 * t + 4] = c.x; qv[8 * t + 5] = c.y; qv[8 * t + 6] = c.z; qv[8 * t + 7] = c.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 64; ++i) qmax = fmaxf(qmax, fabsf(qv[i]));
-    qmax = fmaxf(qmax, __shfl_xor(qmax, 32, 64));
-    eq = gain_exp(qmax);
-    const float mq = pow2i(eq);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      float v8[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v8[j] = qv[8 * t + j];
-      qp[t] = split8h(v8, mq);
-    }
-  }
+  WaMath<MATH> M;
+  M.load_query(q + seq_base + (size_t)q_tok * WA_C, hl);
   f32x16 o[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) o[m] = (f32x16)(0.0f);
   float m_run = -3.0e38f, l_run = 0.0f;
-  int ev_run = 0;  // V gain exponent the output accumulator currently carries (irrelevant while o == 0)
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int kt = 0; kt < n_tiles; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < n_tiles)
+    if (kt + 1 < n_tiles)  // DMA of the next tile overlaps this tile's matrix instructions
       wa_stage_tile<NQW>(k, v, seq_base, G, wy, wx, kt + 1, WA_KBUF(cur ^ 1), WA_VBUF(cur ^ 1), wave, lane);
-    // ---- S^T = K Q^T: the wave's 64 lanes hold the 32 x 128 K tile exactly once (lane = key row, half = channel
-    // half of every K16-step): tile maximum -> one gain
-    f32x16 s0 = (f32x16)(0.0f), s1 = (f32x16)(0.0f);
-    int ek;
-    {
-      const float* krow = WA_KBUF(cur) + n * WA_C;
-      float kv[64];
-      float kmax = 0.0f;
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int c4 = 4 * t + 2 * hl;  // 16-byte column groups of channels 16t + 8hl .. + 7 (swizzled by the key)
-        const float4 a = *reinterpret_cast<const float4*>(krow + ((c4 ^ n) << 2));
-        const float4 c = *reinterpret_cast<const float4*>(krow + (((c4 + 1) ^ n) << 2));
-        kv[8 * t + 0] = a.x; kv[8 * t + 1] = a.y; kv[8 * t + 2] = a.z; kv[8 * t + 3] = a.w;
-        kv[8 * t + 4] = c.x; kv[8 * t + 5] = c.y; kv[8 * t + 6] = c.z; kv[8 * t + 7] = c.w;
-      }
-#pragma unroll
-      for (int i = 0; i < 64; ++i) kmax = fmaxf(kmax, fabsf(kv[i]));
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) kmax = fmaxf(kmax, __shfl_xor(kmax, off, 64));
-      ek = gain_exp(kmax);
-      const float mk = pow2i(ek);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        float v8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v8[j] = kv[8 * t + j];
-        const PartsH kp = split8h(v8, mk);
-        if (t & 1) {
-          s1 = mfma16h(kp.hi, qp[t].lo, s1);
-          s1 = mfma16h(kp.lo, qp[t].hi, s1);
-          s1 = mfma16h(kp.hi, qp[t].hi, s1);
-        } else {
-          s0 = mfma16h(kp.hi, qp[t].lo, s0);
-          s0 = mfma16h(kp.lo, qp[t].hi, s0);
-          s0 = mfma16h(kp.hi, qp[t].hi, s0);
-        }
-      }
-    }
-    f32x16 s = s0 + s1;
-    const float sscale = scale * pow2i(-(ek + eq));
-    // ---- scale, masks, online softmax (as in the f32 kernel)
+
+    // ---- S^T = K Q^T
+    f32x16 s;
+    const float sscale = M.scores(WA_KBUF(cur), n, hl, scale, s);
+    // ---- scale, masks, online softmax
     float tmax = -3.0e38f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -538,74 +450,28 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_f16_kernel(
     psum += __shfl_xor(psum, 32, 64);
     l_run = l_run * alpha + psum;
     m_run = m_new;
-    // ---- O^T += V^T P^T: the lanes' 2 x 4 x 8 V values are the whole tile once more -> tile maximum -> gain
-    float vv[2][4][8];
-    float vmax = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int r = 8 * t + j;
-          const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
-          const float x = WA_VBUF(cur)[key * WA_C + 32 * m + n];
-          vv[t][m][j] = x;
-          vmax = fmaxf(vmax, fabsf(x));
-        }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
-    const int ev = gain_exp(vmax);
-    const float mv = pow2i(ev);
-    const float corr = alpha * pow2i(ev - ev_run);  // softmax correction and change of V gain in one multiplication
-    ev_run = ev;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[m][r] *= corr;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float pv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pv[j] = s[8 * t + j];
-      const PartsH pp = split8h(pv, 16384.0f);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const PartsH vp = split8h(vv[t][m], mv);
-        o[m] = mfma16h(vp.hi, pp.lo, o[m]);
-        o[m] = mfma16h(vp.lo, pp.hi, o[m]);
-        o[m] = mfma16h(vp.hi, pp.hi, o[m]);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    // ---- O^T = alpha O^T + V^T P^T
+    M.accumulate(o, s, alpha, WA_VBUF(cur), n, hl);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // next tile landed (this wave's pieces)
+    __syncthreads();                                   // ... all waves' pieces; current tile consumed
   }
-  if (q_ok) {
-    const float inv_l = pow2i(-(ev_run + 14)) / l_run;
-    float* dst = out + seq_base + (size_t)q_tok * WA_C;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 t = make_float4(o[m][4 * g4] * inv_l, o[m][4 * g4 + 1] * inv_l,
-                                     o[m][4 * g4 + 2] * inv_l, o[m][4 * g4 + 3] * inv_l);
-        *reinterpret_cast<float4*>(dst + m * 32 + 8 * g4 + 4 * hl) = t;
-      }
-  }
+#undef WA_KBUF
+#undef WA_VBUF
+  if (q_ok) wa_store_out(out + seq_base + (size_t)q_tok * WA_C, o, M.final_scale() / l_run, hl);
 }
 
 // ============================================================================ pre-split fp16 variant
 // The split-fp16 arithmetic above with the K / V operand fragments produced ONCE per call instead of once per wave
-// and tile: in the kernels above every one of the Lw/32 query waves of a window converts the window's whole K and V
+// and tile: in window_attention_kernel every one of the Lw/32 query waves of a window converts the window's whole K and V
 // (Lw x 128 values each) to matrix operands again - 70 % of their VALU instructions.  wa_presplit_kernel (one wave per
 // 32-key tile) writes, per (batch, window, tile), a 32 KiB image that IS the LDS image the main loop wants:
 //   K part  [t = 0..7 ][term hi|lo][lane 0..63] x 16 B   A operand of K16-step t of S^T (lane = key n, half hl)
 //   V part  [t = 0..1 ][m = 0..3][term hi|lo][lane]  x 16 B   A operand of step t, output block m of O^T
 // plus a 32-byte side record: the two power-of-two gain exponents of the tile (ek, ev) and the wrap region of each of
-// its keys (shift mask, one nibble per key - the kernels above recompute them with an integer division per score).  The main kernel copies an image with
+// its keys (shift mask, one nibble per key - window_attention_kernel recomputes them with an integer division per score).  The main kernel copies an image with
 // 32 x 1 KiB LDS-DMA pieces and reads every fragment with one conflict-free ds_read_b128; the tile gains come from a
 // scalar load issued one tile ahead, so nothing in the loop waits for a reduction any more (what made the in-loop
-// split-fp16 variant slower than split-bf16).  Same products, same accumulation order as window_attention_f16_kernel.
+// split-fp16 variant slower than split-bf16).  Same products, same accumulation order as WaMath<MNERF_WA_SPLIT_F16>.
 
 __global__ __launch_bounds__(64) void wa_presplit_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                          u32x4* __restrict__ img, int* __restrict__ gains, WinGeom G) {
@@ -621,27 +487,20 @@ __global__ __launch_bounds__(64) void wa_presplit_kernel(const float* __restrict
     int li = kt * WA_KT + n;
     if (li >= G.Lw) li = G.Lw - 1;
     const int tok = win_token(G, wy, wx, li, reg_unused);
-    const float4* src = reinterpret_cast<const float4*>(k + seq_base + (size_t)tok * WA_C + hl * 8);
-    float kv[64];
+    const float* src = k + seq_base + (size_t)tok * WA_C + hl * 8;
+    float kv[8][8];
     float kmax = 0.0f;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 a = src[4 * t], c = src[4 * t + 1];
-      kv[8 * t + 0] = a.x; kv[8 * t + 1] = a.y; kv[8 * t + 2] = a.z; kv[8 * t + 3] = a.w;
-      kv[8 * t + 4] = c.x; kv[8 * t + 5] = c.y; kv[8 * t + 6] = c.z; kv[8 * t + 7] = c.w;
-    }
+    for (int t = 0; t < 8; ++t) wa_load8(kv[t], src + 16 * t, src + 16 * t + 4);
 #pragma unroll
-    for (int i = 0; i < 64; ++i) kmax = fmaxf(kmax, fabsf(kv[i]));
+    for (int t = 0; t < 8; ++t)
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kmax = fmaxf(kmax, __shfl_xor(kmax, off, 64));
-    ek = gain_exp(kmax);
+      for (int j = 0; j < 8; ++j) kmax = fmaxf(kmax, fabsf(kv[t][j]));
+    ek = wa_tile_gain_exp(kmax);
     const float mk = pow2i(ek);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      float v8[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v8[j] = kv[8 * t + j];
-      const PartsH kp = split8h(v8, mk);
+      const PartsH kp = split8h(kv[t], mk);
       dst[(2 * t) * 64] = __builtin_bit_cast(u32x4, kp.hi);
       dst[(2 * t + 1) * 64] = __builtin_bit_cast(u32x4, kp.lo);
     }
@@ -665,9 +524,7 @@ __global__ __launch_bounds__(64) void wa_presplit_kernel(const float* __restrict
           vmax = fmaxf(vmax, fabsf(x));
         }
       }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
-    ev = gain_exp(vmax);
+    ev = wa_tile_gain_exp(vmax);
     const float mv = pow2i(ev);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -699,7 +556,7 @@ __device__ __forceinline__ void wa_halves(float x, float& lo, float& hi) {
 template <int NQW>
 __device__ __forceinline__ void wa_stage_image(const u32x4* __restrict__ img_tile, unsigned lds_base, int wave, int lane) {
   for (int piece = wave; piece < WA_IMG_BYTES / 1024; piece += NQW)
-    wa_glds16(reinterpret_cast<const float*>(img_tile + piece * 64 + lane),
+    glds16(reinterpret_cast<const float*>(img_tile + piece * 64 + lane),
               __builtin_amdgcn_readfirstlane(lds_base + (unsigned)piece * 1024u));
 }
 
@@ -739,6 +596,8 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_pre_kernel(
   const bool q_ok = qi_raw < G.Lw;
   int q_region;
   const int q_tok = win_token(G, wy, wx, q_ok ? qi_raw : (G.Lw - 1), q_region);
+  // (wa_query_split_h written out: through the helper the compiler swaps the source operands of this block's 64 multiplications,
+  // and this kernel's code is kept instruction for instruction)
   PartsH qp[8];
   int eq;
   {
@@ -803,7 +662,7 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_pre_kernel(
     constexpr int PW_ = 8 * PPS, EVERY_ = 8 / (PW_ / 4);                                     \
     if ((slot) % EVERY_ == 0) {                                                              \
       const int piece = wave * PW_ + 4 * ((slot) / EVERY_);                                  \
-      wa_glds16x4(reinterpret_cast<const float*>(img_next + piece * 64),                     \
+      glds16x4(reinterpret_cast<const float*>(img_next + piece * 64),                     \
                   __builtin_amdgcn_readfirstlane(lds_next + (unsigned)piece * 1024u));       \
     }                                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                       \
@@ -963,15 +822,7 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_pre_kernel(
 #endif
   if (q_ok) {
     const float inv_l = pow2i(-(ev_run + 14)) / l_run;
-    float* dst = out + seq_base + (size_t)q_tok * WA_C;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 t = make_float4(o[m][4 * g4] * inv_l, o[m][4 * g4 + 1] * inv_l,
-                                     o[m][4 * g4 + 2] * inv_l, o[m][4 * g4 + 3] * inv_l);
-        *reinterpret_cast<float4*>(dst + m * 32 + 8 * g4 + 4 * hl) = t;
-      }
+    wa_store_out(out + seq_base + (size_t)q_tok * WA_C, o, inv_l, hl);
 #ifndef MNERF_TIMELINE
     if constexpr (STATS) {
       if (hl == 0) {  // both halves of a query's lane pair hold the same statistics
@@ -987,6 +838,17 @@ __global__ __launch_bounds__(NQW * 64, 2) void window_attention_pre_kernel(
 
 extern "C" size_t mnerf_window_attention_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t num_splits) {
   return wa_workspace_bytes(batch, h, w, num_splits);
+}
+
+// One forward kernel instance, `waves` query waves per workgroup.  Every instance of both kernels takes 64 KiB of dynamic LDS
+// (two operand images, or two K and two V tiles), allowed once per instance and device.
+template <auto KERNEL, class... Args>
+static void wa_launch(dim3 grid, int waves, hipStream_t st, Args... args) {
+  constexpr size_t lds = 2 * WA_IMG_BYTES;
+  static_assert(lds == 4 * WA_KT * WA_C * sizeof(float), "the fp32 K/V tiles and the operand images fill the same LDS");
+  static std::atomic<unsigned long long> attr{0};
+  if (mnerf_once_per_device(attr)) (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(64 * waves), lds, st, args...);
 }
 
 // 128-query workgroups (the <4> instances, four waves) once there are wa_min4 of them, 64-query ones (<2>) below that: both launch
@@ -1016,14 +878,6 @@ static int wa_launch_main(const char* who, const float* q, float* out, const Win
   const u32x4* img = reinterpret_cast<const u32x4*>(workspace);
   const int* gains = reinterpret_cast<const int*>(reinterpret_cast<const char*>(workspace) + (size_t)batch * n_win * n_tiles * WA_IMG_BYTES);
   const float scale = 1.0f / sqrtf((float)WA_C);
-  const size_t lds = 2 * WA_IMG_BYTES;
-  static std::atomic<unsigned long long> attr{0};
-  if (mnerf_once_per_device(attr)) {
-    (void)hipFuncSetAttribute((const void*)window_attention_pre_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_pre_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_pre_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_pre_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   unsigned long long* tl = nullptr;
 #ifdef MNERF_TIMELINE
   if (const char* e = getenv("MNERF_WA_TIMELINE_PTR")) tl = (unsigned long long*)strtoull(e, nullptr, 0);
@@ -1037,18 +891,18 @@ static int wa_launch_main(const char* who, const float* q, float* out, const Win
   if (row_stats) {
     unsigned long long* sp = reinterpret_cast<unsigned long long*>(row_stats);
     if (four)
-      hipLaunchKernelGGL((window_attention_pre_kernel<4, true>), grid, dim3(256), lds, st, q, img, gains, out, G, do_shift, scale, batch, xcd, sp);
+      wa_launch<window_attention_pre_kernel<4, true>>(grid, 4, st, q, img, gains, out, G, do_shift, scale, batch, xcd, sp);
     else
-      hipLaunchKernelGGL((window_attention_pre_kernel<2, true>), grid, dim3(128), lds, st, q, img, gains, out, G, do_shift, scale, batch, xcd, sp);
+      wa_launch<window_attention_pre_kernel<2, true>>(grid, 2, st, q, img, gains, out, G, do_shift, scale, batch, xcd, sp);
     return mnerf_check_launch(who);
   }
 #else
   MNERF_REQUIRE(!row_stats, MNERF_E_UNSUPPORTED, "%s: no row statistics in the timeline build", who);
 #endif
   if (four)
-    hipLaunchKernelGGL(window_attention_pre_kernel<4>, grid, dim3(256), lds, st, q, img, gains, out, G, do_shift, scale, batch, xcd, tl);
+    wa_launch<window_attention_pre_kernel<4>>(grid, 4, st, q, img, gains, out, G, do_shift, scale, batch, xcd, tl);
   else
-    hipLaunchKernelGGL(window_attention_pre_kernel<2>, grid, dim3(128), lds, st, q, img, gains, out, G, do_shift, scale, batch, xcd, tl);
+    wa_launch<window_attention_pre_kernel<2>>(grid, 2, st, q, img, gains, out, G, do_shift, scale, batch, xcd, tl);
   return mnerf_check_launch(who);
 }
 
@@ -1110,65 +964,38 @@ extern "C" int mnerf_window_attention_images(const float* q, float* out, int32_t
   return wa_launch_main(who, q, out, G, do_shift, batch, num_splits, const_cast<void*>(workspace), (hipStream_t)stream);
 }
 
+// the kernel over fp32 K / V tiles in one arithmetic: 128- or 64-query workgroups by the same rule as the images form
+template <int MATH>
+static void wa_launch_tiles(const float* q, const float* k, const float* v, float* out, const WinGeom& G, int do_shift, int32_t batch,
+                            hipStream_t st) {
+  const int n_win = G.splits * G.splits;
+  const float scale = 1.0f / sqrtf((float)WA_C);
+  if (wa_take_four(G.Lw, n_win, batch))
+    wa_launch<window_attention_kernel<4, MATH>>(dim3((G.Lw + 127) / 128, n_win, batch), 4, st, q, k, v, out, G, do_shift, scale);
+  else
+    wa_launch<window_attention_kernel<2, MATH>>(dim3((G.Lw + 63) / 64, n_win, batch), 2, st, q, k, v, out, G, do_shift, scale);
+}
+
 extern "C" int mnerf_window_attention(const float* q, const float* k, const float* v, float* out,
                                       int32_t batch, int32_t h, int32_t w, int32_t num_splits,
                                       int32_t shifted, int32_t math, void* stream) {
-  MNERF_REQUIRE(q && k && v && out, MNERF_E_NULL, "mnerf_window_attention: NULL buffer");
-  MNERF_REQUIRE(mnerf_aligned16(q) && mnerf_aligned16(k) && mnerf_aligned16(v) && mnerf_aligned16(out),
-                MNERF_E_ALIGN, "mnerf_window_attention: buffers must be 16-byte aligned");
-  MNERF_REQUIRE(batch >= 0 && h >= 1 && w >= 1 && num_splits >= 1, MNERF_E_RANGE,
-                "mnerf_window_attention: batch=%d h=%d w=%d splits=%d", batch, h, w, num_splits);
-  MNERF_REQUIRE(h % num_splits == 0 && w % num_splits == 0, MNERF_E_RANGE,
-                "mnerf_window_attention: %dx%d not divisible into %d splits", h, w, num_splits);
-  MNERF_REQUIRE(batch <= 65535 && num_splits * num_splits <= 65535, MNERF_E_RANGE,
-                "mnerf_window_attention: grid too large");
-  MNERF_REQUIRE(math == MNERF_WA_SPLIT_BF16 || math == MNERF_WA_EXACT_F32 || math == MNERF_WA_SPLIT_F16, MNERF_E_UNSUPPORTED,
-                "mnerf_window_attention: math=%d", math);
-  if (batch == 0) return MNERF_OK;
+  const char* who = "mnerf_window_attention";
+  MNERF_REQUIRE(q && k && v && out, MNERF_E_NULL, "%s: NULL buffer", who);
+  MNERF_REQUIRE(mnerf_aligned16(q) && mnerf_aligned16(k) && mnerf_aligned16(v) && mnerf_aligned16(out), MNERF_E_ALIGN,
+                "%s: buffers must be 16-byte aligned", who);
   WinGeom G;
-  G.h = h;
-  G.w = w;
-  G.splits = num_splits;
-  G.wh = h / num_splits;
-  G.ww = w / num_splits;
-  const int do_shift = (shifted && num_splits > 1) ? 1 : 0;
-  G.sh = do_shift ? G.wh / 2 : 0;
-  G.sw = do_shift ? G.ww / 2 : 0;
-  G.Lw = G.wh * G.ww;
-  const float scale = 1.0f / sqrtf((float)WA_C);
+  int do_shift;
+  if (const int rc = wa_geometry(who, batch, h, w, num_splits, shifted, G, do_shift)) return rc;
+  MNERF_REQUIRE(math == MNERF_WA_SPLIT_BF16 || math == MNERF_WA_EXACT_F32 || math == MNERF_WA_SPLIT_F16, MNERF_E_UNSUPPORTED,
+                "%s: math=%d", who, math);
+  if (batch == 0) return MNERF_OK;
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 4 * WA_KT * WA_C * sizeof(float);  // 64 KiB: K and V tiles, double buffered
-  const bool split = math == MNERF_WA_SPLIT_BF16;  // split-bf16 products (the host's default), split-fp16 products or the exact-f32 MFMA
-  const bool split_h = math == MNERF_WA_SPLIT_F16;
-  static std::atomic<unsigned long long> attr_f32{0}, attr_split{0}, attr_split_h{0};
-  if (split_h && mnerf_once_per_device(attr_split_h)) {
-    (void)hipFuncSetAttribute((const void*)window_attention_f16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_f16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  if (!split && !split_h && mnerf_once_per_device(attr_f32)) {
-    (void)hipFuncSetAttribute((const void*)window_attention_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  if (split && mnerf_once_per_device(attr_split)) {
-    (void)hipFuncSetAttribute((const void*)window_attention_bf16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)window_attention_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  if (wa_take_four(G.Lw, num_splits * num_splits, batch)) {
-    dim3 grid((G.Lw + 127) / 128, num_splits * num_splits, batch);
-    if (split_h)
-      hipLaunchKernelGGL(window_attention_f16_kernel<4>, grid, dim3(256), lds, st, q, k, v, out, G, do_shift, scale);
-    else if (split)
-      hipLaunchKernelGGL(window_attention_bf16_kernel<4>, grid, dim3(256), lds, st, q, k, v, out, G, do_shift, scale);
-    else
-      hipLaunchKernelGGL(window_attention_kernel<4>, grid, dim3(256), lds, st, q, k, v, out, G, do_shift, scale);
-  } else {
-    dim3 grid((G.Lw + 63) / 64, num_splits * num_splits, batch);
-    if (split_h)
-      hipLaunchKernelGGL(window_attention_f16_kernel<2>, grid, dim3(128), lds, st, q, k, v, out, G, do_shift, scale);
-    else if (split)
-      hipLaunchKernelGGL(window_attention_bf16_kernel<2>, grid, dim3(128), lds, st, q, k, v, out, G, do_shift, scale);
-    else
-      hipLaunchKernelGGL(window_attention_kernel<2>, grid, dim3(128), lds, st, q, k, v, out, G, do_shift, scale);
-  }
-  return mnerf_check_launch("mnerf_window_attention");
+  if (math == MNERF_WA_SPLIT_F16)
+    wa_launch_tiles<MNERF_WA_SPLIT_F16>(q, k, v, out, G, do_shift, batch, st);
+  else if (math == MNERF_WA_SPLIT_BF16)
+    wa_launch_tiles<MNERF_WA_SPLIT_BF16>(q, k, v, out, G, do_shift, batch, st);
+  else
+    wa_launch_tiles<MNERF_WA_EXACT_F32>(q, k, v, out, G, do_shift, batch, st);
+  return mnerf_check_launch(who);
 }
+

@@ -983,6 +983,23 @@ extern "C" int64_t mnerf_window_attention_backward_workspace_bytes(int32_t batch
   return ((int64_t)4 * batch * h * w + 4) * (int64_t)sizeof(float);
 }
 
+// the split 16-bit kernels with NT terms per operand (2: f16x3, 3: bf16x6): dQ (with or without the forward's row statistics), then
+// dK^T and dV^T; their dynamic LDS is allowed once per NT and device
+template <int NT>
+static void wa_bwd_launch_split(dim3 grid, hipStream_t st, const WaBwdArgs& A, bool have_stats) {
+  const size_t lds = WbsLds<NT>::BYTES;
+  static std::atomic<unsigned long long> attr_set{0};
+  if (mnerf_once_per_device(attr_set)) {
+    for (const void* kernel : {(const void*)wa_bwd_dq_split_kernel<false, NT>, (const void*)wa_bwd_dq_split_kernel<true, NT>,
+                               (const void*)wa_bwd_dkv_split_kernel<0, NT>, (const void*)wa_bwd_dkv_split_kernel<1, NT>})
+      (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  }
+  if (have_stats) hipLaunchKernelGGL((wa_bwd_dq_split_kernel<true, NT>), grid, dim3(256), lds, st, A);
+  else hipLaunchKernelGGL((wa_bwd_dq_split_kernel<false, NT>), grid, dim3(256), lds, st, A);
+  hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<0, NT>), grid, dim3(256), lds, st, A);
+  hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<1, NT>), grid, dim3(256), lds, st, A);
+}
+
 static int wa_backward_impl(const char* who, const float* q, const float* k, const float* v, const float* out, const float* g_out,
                             const float* row_stats, float* g_q, float* g_k, float* g_v, int32_t batch, int32_t h, int32_t w,
                             int32_t num_splits, int32_t shifted, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1022,19 +1039,6 @@ static int wa_backward_impl(const char* who, const float* q, const float* k, con
   hipLaunchKernelGGL(wa_bwd_rowdot_kernel, dim3((unsigned)((n_tok + 7) / 8)), dim3(256), 0, st, g_out, out, row_d,
                      math == 2 ? row_n2 : nullptr, n_tok);
   if (math) {
-    static std::atomic<unsigned long long> attr6_set{0};
-    if (mnerf_once_per_device(attr6_set)) {
-#define WBS_ATTR(K_, NT_) (void)hipFuncSetAttribute((const void*)K_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WbsLds<NT_>::BYTES)
-      WBS_ATTR((wa_bwd_dq_split_kernel<false, 3>), 3);
-      WBS_ATTR((wa_bwd_dq_split_kernel<true, 3>), 3);
-      WBS_ATTR((wa_bwd_dkv_split_kernel<0, 3>), 3);
-      WBS_ATTR((wa_bwd_dkv_split_kernel<1, 3>), 3);
-      WBS_ATTR((wa_bwd_dq_split_kernel<false, 2>), 2);
-      WBS_ATTR((wa_bwd_dq_split_kernel<true, 2>), 2);
-      WBS_ATTR((wa_bwd_dkv_split_kernel<0, 2>), 2);
-      WBS_ATTR((wa_bwd_dkv_split_kernel<1, 2>), 2);
-#undef WBS_ATTR
-    }
     const dim3 grid6((G.Lw + WB6_R - 1) / WB6_R, num_splits * num_splits, batch);
     if (row_stats) {  // the forward's statistics: read in place by all three kernels
       A.row_m = const_cast<float*>(row_stats);
@@ -1045,17 +1049,9 @@ static int wa_backward_impl(const char* who, const float* q, const float* k, con
       const long long n4 = n_tok * (WA_C / 4);
       const unsigned nblk = (unsigned)((n4 + 256 * 8 - 1) / (256 * 8) < 256 ? (n4 + 256 * 8 - 1) / (256 * 8) : 256);
       hipLaunchKernelGGL(wa_bwd_absmax4_kernel, dim3(nblk, 4), dim3(256), 0, st, q, k, v, g_out, n4, absmax);
-      const size_t lds2 = WbsLds<2>::BYTES;
-      if (row_stats) hipLaunchKernelGGL((wa_bwd_dq_split_kernel<true, 2>), grid6, dim3(256), lds2, st, A);
-      else hipLaunchKernelGGL((wa_bwd_dq_split_kernel<false, 2>), grid6, dim3(256), lds2, st, A);
-      hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<0, 2>), grid6, dim3(256), lds2, st, A);
-      hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<1, 2>), grid6, dim3(256), lds2, st, A);
+      wa_bwd_launch_split<2>(grid6, st, A, row_stats != nullptr);
     } else {
-      const size_t lds3 = WbsLds<3>::BYTES;
-      if (row_stats) hipLaunchKernelGGL((wa_bwd_dq_split_kernel<true, 3>), grid6, dim3(256), lds3, st, A);
-      else hipLaunchKernelGGL((wa_bwd_dq_split_kernel<false, 3>), grid6, dim3(256), lds3, st, A);
-      hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<0, 3>), grid6, dim3(256), lds3, st, A);
-      hipLaunchKernelGGL((wa_bwd_dkv_split_kernel<1, 3>), grid6, dim3(256), lds3, st, A);
+      wa_bwd_launch_split<3>(grid6, st, A, row_stats != nullptr);
     }
     return mnerf_check_launch(who);
   }

@@ -830,6 +830,21 @@ def wa_math():
     return table[m]
 
 
+def _wa_check_row_stats(what, row_stats, n_tokens):
+    import torch
+    if tuple(row_stats.shape) != (2, n_tokens) or row_stats.dtype != torch.float32 or not row_stats.is_contiguous():
+        raise MnerfError(f"{what}: row_stats must be a contiguous float32 [2, {n_tokens}] tensor")
+
+
+def _wa_workspace(nbytes, device, stream):
+    """scratch of one attention call, at least 16 bytes, in use on ``stream`` (the caching allocator's: no hipMalloc)"""
+    import torch
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+    if stream is not None:
+        ws.record_stream(stream)
+    return ws
+
+
 def window_attention(q, k, v, h, w, num_splits, shifted, out=None, math=None, stream=None, row_stats=None):
     """K6 (gmflow/transformer.py:8-105). q,k,v [B,h*w,128] -> [B,h*w,128].  ``row_stats`` (training forward, default arithmetic
     only): a float32 [2, B*h*w] tensor that receives the softmax's row statistics for ``window_attention_backward``."""
@@ -845,12 +860,9 @@ def window_attention(q, k, v, h, w, num_splits, shifted, out=None, math=None, st
     with _on(q.device, stream) as st:
         if math == WA_PRESPLIT_F16:
             nbytes = int(lib.mnerf_window_attention_workspace_bytes(b, h, w, int(num_splits)))
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)  # caching allocator: no hipMalloc
-            if stream is not None:
-                ws.record_stream(stream)
+            ws = _wa_workspace(nbytes, q.device, stream)
             if row_stats is not None:
-                if tuple(row_stats.shape) != (2, b * n) or row_stats.dtype != torch.float32 or not row_stats.is_contiguous():
-                    raise MnerfError(f"window_attention: row_stats must be a contiguous float32 [2, {b * n}] tensor")
+                _wa_check_row_stats("window_attention", row_stats, b * n)
                 check(lib.mnerf_window_attention_presplit_stats(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(row_stats), b, h, w,
                                                                 int(num_splits), int(bool(shifted)), _ptr(ws), nbytes, st),
                       "mnerf_window_attention_presplit_stats")
@@ -878,21 +890,17 @@ def window_attention_backward(q, k, v, out, g_out, h, w, num_splits, shifted, st
     if c != 128 or n != h * w or any(tuple(t.shape) != (b, n, c) for t in (k, v, out, g_out)):
         raise MnerfError(f"window_attention_backward: expected five [B,{h * w},128] tensors, got {tuple(q.shape)} ...")
     g_q, g_k, g_v = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-    nbytes = int(lib.mnerf_window_attention_backward_workspace_bytes(b, h, w))
-    ws = torch.empty(max(nbytes // 4, 4), device=q.device)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _wa_workspace(lib.mnerf_window_attention_backward_workspace_bytes(b, h, w), q.device, stream)
     with _on(q.device, stream) as st:
         if row_stats is not None:
-            if tuple(row_stats.shape) != (2, b * n) or row_stats.dtype != torch.float32 or not row_stats.is_contiguous():
-                raise MnerfError(f"window_attention_backward: row_stats must be a contiguous float32 [2, {b * n}] tensor")
+            _wa_check_row_stats("window_attention_backward", row_stats, b * n)
             check(lib.mnerf_window_attention_backward_stats(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(g_out), _ptr(row_stats), _ptr(g_q),
                                                             _ptr(g_k), _ptr(g_v), b, h, w, int(num_splits), int(bool(shifted)),
-                                                            _ptr(ws), ws.numel() * 4, st), "mnerf_window_attention_backward_stats")
+                                                            _ptr(ws), ws.numel(), st), "mnerf_window_attention_backward_stats")
             return g_q, g_k, g_v
         check(lib.mnerf_window_attention_backward(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(g_out), _ptr(g_q), _ptr(g_k), _ptr(g_v),
                                                   b, h, w, int(num_splits), int(bool(shifted)), _ptr(ws),
-                                                  ws.numel() * 4, st), "mnerf_window_attention_backward")
+                                                  ws.numel(), st), "mnerf_window_attention_backward")
     return g_q, g_k, g_v
 
 
@@ -930,9 +938,7 @@ def qkv_window_images(wstream, ews, x_q, x_kv, kv_swap, h, w, num_splits, shifte
         raise MnerfError(f"qkv_window_images: wstream has {wstream.numel()} floats, expected {lib.mnerf_qkv_wstream_floats()}")
     q = torch.empty_like(x_q)
     nbytes = int(lib.mnerf_window_attention_workspace_bytes(b, h, w, int(num_splits)))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x_q.device)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _wa_workspace(nbytes, x_q.device, stream)
     ew = (C.c_int32 * 3)(*[int(e) for e in ews])
     with _on(x_q.device, stream) as st:
         check(lib.mnerf_qkv_window_images(_ptr(wstream), ew, _ptr(x_q), _ptr(x_kv), int(bool(kv_swap)), _ptr(q),

@@ -193,6 +193,22 @@ def test_window_attention_128_query_instances_at_their_own_threshold(hip):
         assert torch.isfinite(out).all() and linf(out, ref) < 2e-5, shifted
 
 
+@pytest.mark.parametrize("math", ["f16x3", "bf16x6", "f32"])
+def test_window_attention_full_attention_in_every_tile_arithmetic(hip, math, monkeypatch):
+    """full attention (num_splits = 1), which the suite otherwise shows only to the default arithmetic, through the three
+    arithmetics of window_attention_kernel: 5 x 7 = 35 tokens are one query block with 35 live rows of 64 and two key tiles,
+    the second with 3 live keys.  `shifted` is a no-op at one split: both settings give the same bits."""
+    monkeypatch.setenv("MNERF_WA_MATH", math)
+    b, h, w, splits = 1, 5, 7, 1
+    gen = torch.Generator().manual_seed(13)
+    q, k, v = (torch.randn(b, h * w, 128, generator=gen) for _ in range(3))
+    ref = O.window_attention(q, k, v, h, w, splits, False)
+    out = {shifted: hip.window_attention(q.cuda(), k.cuda(), v.cuda(), h, w, splits, shifted) for shifted in (False, True)}
+    print(f"\nwindow attention full {math}: {linf(out[False], ref):.2e}")
+    assert torch.isfinite(out[False]).all() and linf(out[False], ref) < 2e-5
+    assert torch.equal(out[False], out[True])
+
+
 @pytest.mark.parametrize("name", ["c1_default", "rect_wide", "nonlegacy", "v4", "inverse_depth", "demo_own_small", "demo_own"])
 def test_ray_geometry_is_bit_exact(hip, name):
     """world points and ref-view-0 NDC coordinates: identical bits to the reference CPU path."""
