@@ -231,50 +231,7 @@ __device__ __forceinline__ f32x16 enc_block16_L10(const EncBase& b, int hl, floa
 }
 
 // ---------------------------------------------------------------- split-bf16 matrix path ("bf16x6")
-// Same transposed chain on v_mfma_f32_32x32x16_bf16 (32 cycles per SIMD for 16 K-elements: 16x the
-// K-rate of the f32 MFMA).  Each fp32 weight is stored as three bf16 terms (host,
-// cond_nerf.py:pack_wstream16) and each fp32 activation is split the same way right before it is
-// used; a product is accumulated in fp32 from six terms (hi.hi, hi.mid, mid.hi, hi.lo, lo.hi,
-// mid.mid) — what is dropped is < 2^-24 of the product, so results are fp32-grade (measured on
-// MI355X, tools/exp/bf16x6.hip: max error below that of an fp32 FMA chain) at 16/6 of the f32 rate.
-// Operand layout (verified by the same micro-test): lane (n, half) supplies k = 8*half + j, j < 8,
-// for A row / B column n; C/D as for the f32 32x32 MFMA.  So a 16-register accumulator block of
-// the previous layer is consumed as two K16-steps (registers 0-7, 8-15) with no data movement.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (RNE)
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-struct Parts {
-  bf16x8 hi, mid, lo;
-};
-
-__device__ __forceinline__ Parts split8(const float (&v)[8]) {
-  u32x4 H, M, L;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = v[2 * i], b = v[2 * i + 1];
-    const unsigned h = pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    const unsigned m = pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-    H[i] = h;
-    M[i] = m;
-    L[i] = pk_bf16(sa, sb);
-  }
-  Parts p;
-  p.hi = __builtin_bit_cast(bf16x8, H);
-  p.mid = __builtin_bit_cast(bf16x8, M);
-  p.lo = __builtin_bit_cast(bf16x8, L);
-  return p;
-}
-
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
+// bf16x8, pk_bf16, Parts, split8 and mfma16 (the three-term split and its matrix instruction) live in split_f16.hpp.
 
 // accumulators <- fp32 bias fragment [half][4][16] (exact fp32 biases, no K-step spent on them)
 // LDS operands of the split-bf16 path are addressed by LDS byte offset through explicit address_space(3)

@@ -8,11 +8,11 @@
 //
 // Like the decoder's backward (decoder_backward.hip) this is deliberately NOT one fused tile kernel: the chain is re-evaluated
 // from the layer's inputs with every pre-activation kept in a workspace (3 970 floats per token), then walked backwards.  Every
-// matrix product — Y = X W^T, dX = dY W, dW = dY^T X — is the strided MFMA GEMM of gemm_f32.hpp (fp32-grade split-bf16 by default for I, J >= 128, exact fp32 with MNERF_GEMM_MATH=f32; strided operands: the
+// matrix product — Y = X W^T, dX = dY W, dW = dY^T X — is the strided MFMA GEMM of gemm.hip (fp32-grade split-bf16 by default for I, J >= 128, exact fp32 with MNERF_GEMM_MATH=f32; strided operands: the
 // column halves of mlp.0's [1024, 256] weight cost nothing; split-K with float atomics for the weight gradients).  What is not a
 // matrix product: LayerNorm forward / backward (a half-wave per 128-feature row), exact-erf GELU and its derivative.
 // Parameters travel in torch's own layouts (mnerf_encoder_layer_train); parameter gradients are ACCUMULATED.
-#include "gemm_f32.hpp"
+#include "gemm.hpp"
 
 #define EB_C 128
 #define EB_H 1024
@@ -229,7 +229,7 @@ extern "C" int mnerf_qkv_backward(const float* w_q, const float* w_k, const floa
   return mnerf_check_launch(who);
 }
 
-// Test hook: the strided GEMM the backward kernels are built on (gemm_f32.hpp), so that its arithmetic can be pinned on its own.
+// Test hook: the strided GEMM the backward kernels are built on (gemm.hip), so that its arithmetic can be pinned on its own.
 extern "C" int mnerf_debug_gemm(const float* a, int64_t sa_i, int64_t sa_k, const float* b, int64_t sb_k, int64_t sb_j, float* c,
                                 int64_t sc_i, const float* bias, int32_t I, int32_t J, int32_t K, int32_t mode, int32_t math,
                                 void* stream) {

@@ -1,6 +1,9 @@
-// Split-fp16 MFMA building blocks (shared by the fused decoder, decoder.hip, and the encoder block kernel,
-// encoder_block.hip): fp32-grade matrix products on v_mfma_f32_32x32x16_f16 from two range-managed fp16 terms per
-// operand, the LDS-DMA weight-segment copy, and the LDS operand types.
+// Split-precision MFMA building blocks, the one home of the operand splits of every kernel family (decoder, window attention
+// forward and backward, convolutions, encoder block, training GEMM): fp32-grade matrix products on the 16-bit matrix pipe from
+//   "bf16x6"  three bf16 terms per operand, six term products (pk_bf16, Parts, split8, mfma16), and
+//   "f16x3"   two range-managed fp16 terms per operand, three term products (PartsH, split8h, mfma16h, gain_exp, pow2i);
+// the term-count policy over both (SplitFrag<NT>, split_frag8<NT>, SplitProducts<NT>, split_frag_mac<NT>); the LDS-DMA
+// weight-segment copy; and the LDS operand types.
 #pragma once
 #include "common.hpp"
 
@@ -171,6 +174,52 @@ __device__ __forceinline__ void wave_group_sync(unsigned ctr_lds_byte_addr, int 
   }
 }
 
+// ---------------------------------------------------------------- split-bf16 matrix path ("bf16x6")
+// Same transposed chain on v_mfma_f32_32x32x16_bf16 (32 cycles per SIMD for 16 K-elements: 16x the
+// K-rate of the f32 MFMA).  Each fp32 weight is stored as three bf16 terms (host,
+// cond_nerf.py:pack_wstream16) and each fp32 activation is split the same way right before it is
+// used; a product is accumulated in fp32 from six terms (hi.hi, hi.mid, mid.hi, hi.lo, lo.hi,
+// mid.mid) — what is dropped is < 2^-24 of the product, so results are fp32-grade (measured on
+// MI355X, tools/exp/bf16x6.hip: max error below that of an fp32 FMA chain) at 16/6 of the f32 rate.
+// Operand layout (verified by the same micro-test): lane (n, half) supplies k = 8*half + j, j < 8,
+// for A row / B column n; C/D as for the f32 32x32 MFMA.  So a 16-register accumulator block of
+// the previous layer is consumed as two K16-steps (registers 0-7, 8-15) with no data movement.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (RNE)
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+
+struct Parts {
+  bf16x8 hi, mid, lo;
+};
+
+__device__ __forceinline__ Parts split8(const float (&v)[8]) {
+  u32x4 H, M, L;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float a = v[2 * i], b = v[2 * i + 1];
+    const unsigned h = pk_bf16(a, b);
+    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
+    const unsigned m = pk_bf16(ra, rb);
+    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
+    H[i] = h;
+    M[i] = m;
+    L[i] = pk_bf16(sa, sb);
+  }
+  Parts p;
+  p.hi = __builtin_bit_cast(bf16x8, H);
+  p.mid = __builtin_bit_cast(bf16x8, M);
+  p.lo = __builtin_bit_cast(bf16x8, L);
+  return p;
+}
+
+__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
 // ---------------------------------------------------------------- split-fp16 matrix path ("f16x3", FMT = 2)
 // Same chain on v_mfma_f32_32x32x16_f16 with TWO fp16 terms per operand and THREE products per MAC
 // (hi.hi + hi.lo + lo.hi; the dropped lo.lo term is < 2^-22 of the product): half the matrix instructions of
@@ -236,6 +285,71 @@ __device__ __forceinline__ int gain_exp(float m) {
   return H16_TARGET_EXP - e;
 }
 __device__ __forceinline__ float pow2i(int e) { return ldexpf(1.0f, e); }
+
+// ---------------------------------------------------------------- either split behind a term count (NT = 3: bf16x6, NT = 2: f16x3)
+// For kernels that are written once for both splits (window_attention_backward.hip, gemm.hip): NT terms per operand as raw
+// 16-byte fragments, and the table of term products that are accumulated.
+template <int NT>
+struct SplitFrag {
+  u32x4 t[NT];  // NT = 3: hi | mid | lo, 8 bf16 each;  NT = 2: hi | lo, 8 fp16 each
+};
+// 8 values -> their terms.  mult: the operand's power-of-two gain (NT = 2 only; bf16 has fp32's exponent range)
+template <int NT>
+__device__ __forceinline__ SplitFrag<NT> split_frag8(const float (&v)[8], float mult) {
+  SplitFrag<NT> f;
+  if constexpr (NT == 3) {
+    const Parts p = split8(v);
+    f.t[0] = __builtin_bit_cast(u32x4, p.hi);
+    f.t[1] = __builtin_bit_cast(u32x4, p.mid);
+    f.t[2] = __builtin_bit_cast(u32x4, p.lo);
+  } else {
+    const PartsH p = split8h(v, mult);
+    f.t[0] = __builtin_bit_cast(u32x4, p.hi);
+    f.t[1] = __builtin_bit_cast(u32x4, p.lo);
+  }
+  return f;
+}
+// The term products that matter, smallest first: product p is term TA[p] of A times term TB[p] of B, one matrix instruction.
+// (The decoder's ksteps / ksteps_h and the attention forward's wa_mac6 spell their own sequences, hi.lo BEFORE lo.hi: the order
+// is part of their results.)
+template <int NT>
+struct SplitProducts;
+template <>
+struct SplitProducts<3> {  // lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi
+  static constexpr int N_PROD = 6;
+  static constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
+  static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 acc) {
+    return mfma16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc);
+  }
+};
+template <>
+struct SplitProducts<2> {  // lo.hi, hi.lo, hi.hi
+  static constexpr int N_PROD = 3;
+  static constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};
+  static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 acc) {
+    return mfma16h(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc);
+  }
+};
+// acc += A . B
+template <int NT>
+__device__ __forceinline__ f32x16 split_frag_mac(const SplitFrag<NT>& a, const SplitFrag<NT>& b, f32x16 acc) {
+  using P = SplitProducts<NT>;
+#pragma unroll
+  for (int p = 0; p < P::N_PROD; ++p) acc = P::mfma(a.t[P::TA[p]], b.t[P::TB[p]], acc);
+  return acc;
+}
+template <int NT>
+__device__ __forceinline__ SplitFrag<NT> split_frag_lds(const unsigned char* base, int term_stride) {
+  SplitFrag<NT> f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) f.t[t] = *reinterpret_cast<const u32x4*>(base + t * term_stride);
+  return f;
+}
+template <int NT>
+__device__ __forceinline__ void split_frag_pin(SplitFrag<NT>& f) {
+  if constexpr (NT == 3) asm volatile("" : "+v"(f.t[0]), "+v"(f.t[1]), "+v"(f.t[2]));
+  else asm volatile("" : "+v"(f.t[0]), "+v"(f.t[1]));
+}
 
 typedef const float __attribute__((address_space(3)))* lds_f32_cptr;
 // stage header (1 KiB): floats [0,128) bias in accumulator order, [128] 2^-ew, [129] (float)ew

@@ -166,7 +166,7 @@ struct WaMath<MNERF_WA_EXACT_F32> {
 
 // ---- split-bf16
 // The products on v_mfma_f32_32x32x16_bf16: every fp32 operand is split into
-// three bf16 terms and a product is accumulated in fp32 from six terms (decoder_common.hpp, "split-bf16 matrix
+// three bf16 terms and a product is accumulated in fp32 from six terms (split_f16.hpp, "split-bf16 matrix
 // path": fp32-grade results at 16/6 of the f32 matrix rate).  Q is split once per workgroup and kept in
 // 96 VGPRs; K and V fragments are split as they are read from the fp32 LDS tiles; P is split straight
 // out of the score accumulator, whose layout makes registers 8t..8t+7 the operands of K16-step t.
@@ -174,65 +174,27 @@ struct WaMath<MNERF_WA_EXACT_F32> {
 //   S^T: K-step t covers channels 16t..16t+15          (A = K row of key n, B = Q of query n)
 //   O^T: K-step t covers the keys held by score registers 8t..8t+7, i.e. key(t, half, j) =
 //        ((8t+j)&3) + 8((8t+j)>>2) + 4*half            (A = V^T rows d = 32m + n, B = P)
-typedef __bf16 wa_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wa_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wa_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wa_u32x4 __attribute__((ext_vector_type(4)));
-
-struct WaParts {
-  wa_bf16x8 hi, mid, lo;
-};
-
-__device__ __forceinline__ unsigned wa_pk_bf16(float a, float b) {
-  const wa_f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wa_bf16x2));
-}
-
-__device__ __forceinline__ WaParts wa_split8(const float (&v)[8]) {
-  wa_u32x4 H, M, L;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = v[2 * i], b = v[2 * i + 1];
-    const unsigned h = wa_pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    const unsigned m = wa_pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-    H[i] = h;
-    M[i] = m;
-    L[i] = wa_pk_bf16(sa, sb);
-  }
-  WaParts p;
-  p.hi = __builtin_bit_cast(wa_bf16x8, H);
-  p.mid = __builtin_bit_cast(wa_bf16x8, M);
-  p.lo = __builtin_bit_cast(wa_bf16x8, L);
-  return p;
-}
-
-__device__ __forceinline__ f32x16 wa_mfma16(wa_bf16x8 a, wa_bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // acc += A . B with both operands given as three bf16 terms (six product terms, small ones first)
-__device__ __forceinline__ f32x16 wa_mac6(const WaParts& a, const WaParts& b, f32x16 acc) {
-  acc = wa_mfma16(a.hi, b.lo, acc);
-  acc = wa_mfma16(a.lo, b.hi, acc);
-  acc = wa_mfma16(a.mid, b.mid, acc);
-  acc = wa_mfma16(a.hi, b.mid, acc);
-  acc = wa_mfma16(a.mid, b.hi, acc);
-  acc = wa_mfma16(a.hi, b.hi, acc);
+__device__ __forceinline__ f32x16 wa_mac6(const Parts& a, const Parts& b, f32x16 acc) {
+  acc = mfma16(a.hi, b.lo, acc);
+  acc = mfma16(a.lo, b.hi, acc);
+  acc = mfma16(a.mid, b.mid, acc);
+  acc = mfma16(a.hi, b.mid, acc);
+  acc = mfma16(a.mid, b.hi, acc);
+  acc = mfma16(a.hi, b.hi, acc);
   return acc;
 }
 
 template <>
 struct WaMath<MNERF_WA_SPLIT_BF16> {
-  WaParts qp[8];  // split once: K-step t holds channels 16t + 8 hl + j
+  Parts qp[8];  // split once: K-step t holds channels 16t + 8 hl + j
 
   __device__ __forceinline__ void load_query(const float* qrow, int hl) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       float qv[8];
       wa_load8(qv, qrow + 16 * t + 8 * hl, qrow + 16 * t + 8 * hl + 4);
-      qp[t] = wa_split8(qv);
+      qp[t] = split8(qv);
     }
   }
   // 8 K16-steps over d, two accumulators so that consecutive MFMA groups are independent
@@ -244,7 +206,7 @@ struct WaMath<MNERF_WA_SPLIT_BF16> {
       const int c4 = 4 * t + 2 * hl;  // 16-byte column groups of channels 16t + 8hl .. + 7 (swizzled by the key)
       float kv[8];
       wa_load8(kv, krow + ((c4 ^ n) << 2), krow + (((c4 + 1) ^ n) << 2));
-      const WaParts kp = wa_split8(kv);
+      const Parts kp = split8(kv);
       if (t & 1)
         s1 = wa_mac6(kp, qp[t], s1);
       else
@@ -264,7 +226,7 @@ struct WaMath<MNERF_WA_SPLIT_BF16> {
       float pv[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) pv[j] = p[8 * t + j];
-      const WaParts pp = wa_split8(pv);
+      const Parts pp = split8(pv);
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         float vv[8];
@@ -274,7 +236,7 @@ struct WaMath<MNERF_WA_SPLIT_BF16> {
           const int key = (r & 3) + 8 * (r >> 2) + 4 * hl;
           vv[j] = vbuf[key * WA_C + 32 * m + n];
         }
-        o[m] = wa_mac6(wa_split8(vv), pp, o[m]);
+        o[m] = wa_mac6(split8(vv), pp, o[m]);
       }
     }
   }

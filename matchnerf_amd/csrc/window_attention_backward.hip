@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dkv_kernel(WaBwdArgs A) {
 // The same two kernels with every product on the 16-bit matrix instructions, in two flavours of one template (NT = terms per
 // operand element):
 //   NT = 3  "bf16x6"  three bf16 terms per fp32 element (exact: 3 x 8 significand bits), a product from the six term products that
-//           are not below 2^-24 of it, fp32 accumulation — the scheme of gemm_b6_kernel (gemm_f32.hpp): fp32's exponent range, no
+//           are not below 2^-24 of it, fp32 accumulation — the scheme of gemm_split_kernel<3> (gemm.hip): fp32's exponent range, no
 //           gains to manage, 2.7 x the matrix rate of v_mfma_f32_32x32x2_f32.
 //   NT = 2  "f16x3"   two fp16 terms per element (22 significand bits), three term products hi.lo + lo.hi + hi.hi (the dropped
 //           lo.lo is below 2^-22 of the product) — the forward's and the decoder's scheme (split_f16.hpp): HALF the matrix
@@ -446,76 +446,6 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dkv_kernel(WaBwdArgs A) {
 #define WB6_ST_LD 132            // floats per row of the fp32 staging tile
 #define WB6_ST_BYTES (WB6_T * WB6_ST_LD * 4)
 
-typedef __bf16 wb6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wb6_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wb6_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned wb6_pk(float a, float b) {  // v_cvt_pk_bf16_f32, round to nearest even
-  const wb6_f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wb6_bf16x2));
-}
-template <int NT>
-struct WbsFrag {
-  u32x4 t[NT];  // NT = 3: hi | mid | lo, 8 bf16 each;  NT = 2: hi | lo, 8 fp16 each
-};
-// 8 values -> their terms.  mult: the operand's power-of-two gain (NT = 2 only; bf16 has fp32's exponent range)
-template <int NT>
-__device__ __forceinline__ WbsFrag<NT> wbs_split8(const float (&v)[8], float mult) {
-  WbsFrag<NT> f;
-  if constexpr (NT == 3) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float a = v[2 * i], b = v[2 * i + 1];
-      const unsigned h = wb6_pk(a, b);
-      const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-      const unsigned m = wb6_pk(ra, rb);
-      const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-      f.t[0][i] = h;
-      f.t[1][i] = m;
-      f.t[2][i] = wb6_pk(sa, sb);
-    }
-  } else {
-    const PartsH p = split8h(v, mult);
-    f.t[0] = __builtin_bit_cast(u32x4, p.hi);
-    f.t[1] = __builtin_bit_cast(u32x4, p.lo);
-  }
-  return f;
-}
-// acc += A . B from the term products that matter, smallest first
-template <int NT>
-__device__ __forceinline__ f32x16 wbs_mfma(const WbsFrag<NT>& a, const WbsFrag<NT>& b, f32x16 acc) {
-  if constexpr (NT == 3) {
-#define WB6_P(TA_, TB_) \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wb6_bf16x8, a.t[TA_]), __builtin_bit_cast(wb6_bf16x8, b.t[TB_]), acc, 0, 0, 0)
-    WB6_P(2, 0);
-    WB6_P(0, 2);
-    WB6_P(1, 1);
-    WB6_P(1, 0);
-    WB6_P(0, 1);
-    WB6_P(0, 0);
-#undef WB6_P
-  } else {
-#define WB6_P(TA_, TB_) acc = mfma16h(__builtin_bit_cast(f16x8, a.t[TA_]), __builtin_bit_cast(f16x8, b.t[TB_]), acc)
-    WB6_P(1, 0);
-    WB6_P(0, 1);
-    WB6_P(0, 0);
-#undef WB6_P
-  }
-  return acc;
-}
-template <int NT>
-__device__ __forceinline__ WbsFrag<NT> wbs_lds_frag(const unsigned char* base, int term_stride) {
-  WbsFrag<NT> f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) f.t[t] = *reinterpret_cast<const u32x4*>(base + t * term_stride);
-  return f;
-}
-template <int NT>
-__device__ __forceinline__ void wbs_pin(WbsFrag<NT>& f) {
-  if constexpr (NT == 3) asm volatile("" : "+v"(f.t[0]), "+v"(f.t[1]), "+v"(f.t[2]));
-  else asm volatile("" : "+v"(f.t[0]), "+v"(f.t[1]));
-}
-
 // ---- the gains of the f16x3 flavour
 // gain of a tensor from the bit pattern of its absolute maximum: max * gain in [2^14, 2^15) (2^15 for an all-zero tensor)
 __device__ __forceinline__ float wbs_tensor_gain(unsigned absmax_bits) { return pow2i(gain_exp(__uint_as_float(absmax_bits))); }
@@ -547,7 +477,7 @@ __global__ __launch_bounds__(256) void wa_bwd_absmax4_kernel(const float* __rest
 
 // the 8 K16-steps of one stationary row (window-local index li; zero beyond the window): lane (n, half) holds channels 16 u + 8 half ..
 template <int NT>
-__device__ __forceinline__ void wbs_stationary(WbsFrag<NT> (&f)[8], const float* __restrict__ src_seq, int tok, int half, float mult) {
+__device__ __forceinline__ void wbs_stationary(SplitFrag<NT> (&f)[8], const float* __restrict__ src_seq, int tok, int half, float mult) {
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -556,7 +486,7 @@ __device__ __forceinline__ void wbs_stationary(WbsFrag<NT> (&f)[8], const float*
       const float4 b = reinterpret_cast<const float4*>(src_seq + (size_t)tok * WA_C + 16 * u + 8 * half)[1];
       v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
     }
-    f[u] = wbs_split8<NT>(v, mult);
+    f[u] = split_frag8<NT>(v, mult);
   }
 }
 
@@ -583,7 +513,7 @@ __device__ __forceinline__ void wbs_store_r1(unsigned char* r1, float* st, const
   for (int q = 0; q < 2; ++q) {
     const float4 a = r.v[2 * q], b = r.v[2 * q + 1];
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const WbsFrag<NT> f = wbs_split8<NT>(v, mult);
+    const SplitFrag<NT> f = split_frag8<NT>(v, mult);
     const int ch0 = 8 * (c + 8 * q);
 #pragma unroll
     for (int t = 0; t < NT; ++t) *reinterpret_cast<u32x4*>(r1 + t * WB6_R1_TERM + row * WB6_R1_ROW + ch0 * 2) = f.t[t];
@@ -612,7 +542,7 @@ __device__ __forceinline__ void wbs_build_r2(unsigned char* r2, const float* st,
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = st[(16 * s + 8 * (j >> 2) + 4 * h + (j & 3)) * WB6_ST_LD + ch];
-    const WbsFrag<NT> f = wbs_split8<NT>(v, mult);
+    const SplitFrag<NT> f = split_frag8<NT>(v, mult);
 #pragma unroll
     for (int t = 0; t < NT; ++t) *reinterpret_cast<u32x4*>(r2 + t * WB6_R2_TERM + ch * WB6_R2_ROW + (16 * s + 8 * h) * 2) = f.t[t];
   }
@@ -620,17 +550,17 @@ __device__ __forceinline__ void wbs_build_r2(unsigned char* r2, const float* st,
 // S-type product: acc[rows = the tile's 32 rows][cols = this wave's stationary rows] over the 128 channels.  The fragments of
 // step u + 1 are requested before the matrix instructions of step u (one wave per SIMD: nothing else hides an LDS round trip).
 template <int NT>
-__device__ __forceinline__ f32x16 wbs_tile_product(const unsigned char* r1, const WbsFrag<NT> (&stat)[8], int n, int half) {
+__device__ __forceinline__ f32x16 wbs_tile_product(const unsigned char* r1, const SplitFrag<NT> (&stat)[8], int n, int half) {
   f32x16 acc = (f32x16)(0.0f);
   const unsigned char* base = r1 + n * WB6_R1_ROW + 16 * half;
-  WbsFrag<NT> cur = wbs_lds_frag<NT>(base, WB6_R1_TERM);
+  SplitFrag<NT> cur = split_frag_lds<NT>(base, WB6_R1_TERM);
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
-    WbsFrag<NT> nxt = cur;
-    if (u + 1 < 8) nxt = wbs_lds_frag<NT>(base + 32 * (u + 1), WB6_R1_TERM);
+    SplitFrag<NT> nxt = cur;
+    if (u + 1 < 8) nxt = split_frag_lds<NT>(base + 32 * (u + 1), WB6_R1_TERM);
     __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise sinks the reads to their use: read, wait, multiply, read, wait ...)
-    wbs_pin<NT>(cur);
-    acc = wbs_mfma<NT>(cur, stat[u], acc);
+    split_frag_pin<NT>(cur);
+    acc = split_frag_mac<NT>(cur, stat[u], acc);
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
   }
@@ -641,23 +571,23 @@ __device__ __forceinline__ f32x16 wbs_tile_product(const unsigned char* r1, cons
 template <int NT>
 __device__ __forceinline__ void wbs_chain_product(f32x16 (&out)[4], const unsigned char* r2, const f32x16& s, int n, int half, float mult) {
   const unsigned char* base = r2 + n * WB6_R2_ROW + 16 * half;
-  WbsFrag<NT> cur = wbs_lds_frag<NT>(base, WB6_R2_TERM);  // unit (st, mb) = (0, 0); in flight while s is split
-  WbsFrag<NT> b[2];
+  SplitFrag<NT> cur = split_frag_lds<NT>(base, WB6_R2_TERM);  // unit (st, mb) = (0, 0); in flight while s is split
+  SplitFrag<NT> b[2];
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = s[8 * st + j];
-    b[st] = wbs_split8<NT>(v, mult);
+    b[st] = split_frag8<NT>(v, mult);
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int st = i >> 2, mb = i & 3;
-    WbsFrag<NT> nxt = cur;
-    if (i + 1 < 8) nxt = wbs_lds_frag<NT>(base + 32 * ((i + 1) >> 2) + ((i + 1) & 3) * 32 * WB6_R2_ROW, WB6_R2_TERM);
+    SplitFrag<NT> nxt = cur;
+    if (i + 1 < 8) nxt = split_frag_lds<NT>(base + 32 * ((i + 1) >> 2) + ((i + 1) & 3) * 32 * WB6_R2_ROW, WB6_R2_TERM);
     __builtin_amdgcn_sched_barrier(0);
-    wbs_pin<NT>(cur);
-    out[mb] = wbs_mfma<NT>(cur, b[st], out[mb]);
+    split_frag_pin<NT>(cur);
+    out[mb] = split_frag_mac<NT>(cur, b[st], out[mb]);
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
   }
@@ -736,7 +666,7 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dkv_split_kernel(WaBwdArgs A) {
   int my_kreg = 0;
   const int my_ktok = my_li < G.Lw ? win_token(G, wy, wx, my_li, my_kreg) : -1;
   const bool k_ok = my_ktok >= 0;
-  WbsFrag<NT> kf[8], vf[WHICH ? 8 : 1];
+  SplitFrag<NT> kf[8], vf[WHICH ? 8 : 1];
   wbs_stationary<NT>(kf, ks, my_ktok, half, g_k);
   if constexpr (WHICH == 1) wbs_stationary<NT>(vf, vs, my_ktok, half, g_v);
 
@@ -848,7 +778,7 @@ __global__ __launch_bounds__(256, 1) void wa_bwd_dq_split_kernel(WaBwdArgs A) {
   const float s_scale = A.scale / (g_q * g_k);
   const float d_gain = g_do * g_v;
 
-  WbsFrag<NT> qf[8], dof[8];
+  SplitFrag<NT> qf[8], dof[8];
   wbs_stationary<NT>(qf, qs, my_qtok, half, g_q);
   wbs_stationary<NT>(dof, gos, my_qtok, half, g_do);
   const float row_d = (q_ok ? A.row_d[seq_off + my_qtok] : 0.0f) * d_gain;

@@ -1,4 +1,4 @@
-"""The strided GEMM under the HIP backward kernels (matchnerf_amd/csrc/gemm_f32.hpp) on its own: the split-bf16 form that products
+"""The strided GEMM under the HIP backward kernels (matchnerf_amd/csrc/gemm.hip) on its own: the split-bf16 form that products
 with I, J >= 128 take must be fp32-grade — judged against float64, next to the exact-f32 matrix instruction and torch's fp32 matmul
 on the same operands — for every operand layout the backward passes use (Linear forward / data gradient / weight gradient), ragged
 sizes, the three accumulation modes and operands of very different magnitude (the reason it is bf16 x 3 and not fp16 x 2: no
@@ -90,7 +90,7 @@ def test_small_products_keep_the_exact_f32_kernel():
 @pytest.mark.parametrize("layout", ["nt", "nn", "tn", "tt"])
 @pytest.mark.parametrize("shape", [(256, 128, 512), (300, 130, 77), (128, 640, 1281), (1280, 128, 128), (4096, 2048, 72), (4000, 2100, 40)])
 def test_split_fp16_gemm_with_row_gains_is_fp32_grade(layout, shape):
-    """round 6: three fp16 products per MAC, one power-of-two gain per A row / B column of the tile (gemm_h3_kernel)"""
+    """round 6: three fp16 products per MAC, one power-of-two gain per A row / B column of the tile (gemm_split_kernel<2, ..>)"""
     I, J, K = shape
     a, b = operands(I, J, K, layout, seed=I + K + 1)
     ref = a.double() @ b.double()

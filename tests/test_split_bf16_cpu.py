@@ -1,4 +1,4 @@
-"""The split-bf16 arithmetic of the backward kernels (gemm_b6_kernel, wa_bwd_*_split_kernel<.., 3>, and the f16x3 twin <.., 2>; matchnerf_amd/csrc/gemm_f32.hpp,
+"""The split-bf16 arithmetic of the backward kernels (gemm_split_kernel<3, ..>, wa_bwd_*_split_kernel<.., 3>, and the f16x3 twins <2, ..> / <.., 2>; matchnerf_amd/csrc/split_f16.hpp, gemm.hip,
 window_attention_backward.hip) restated in numpy — no GPU:
 * three round-to-nearest-even bf16 terms taken as the kernels take them (term, residual, term, residual, term) represent an fp32
   value EXACTLY for |x| >= 2^-100 (below that the third term drops into fp32's subnormals and loses bits; the value is then still
