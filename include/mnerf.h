@@ -974,6 +974,81 @@ int mnerf_tsdf_mesh(const float* sums, const float* weight, float origin_x, floa
                     int32_t ny, int32_t nz, float min_weight, float* vertices, int64_t vertex_capacity, int32_t* triangles,
                     int64_t triangle_capacity, int64_t* counts, void* workspace, void* stream);
 
+/* SPARSE TSDF VOLUME (MESH EXPORT, continued; added under v12 without a layout change; matchnerf_amd/csrc/tsdf_sparse.hip): the same
+ * volume and the same mesh, stored only where a surface can be, for grids past what the dense functions take.  The conventions are
+ * those of MESH EXPORT.  The grid nx x ny x nz above is VIRTUAL: it is covered by bricks of MNERF_TSDF_BRICK^3 = 8 x 8 x 8 voxels,
+ * bx = ceil(nx / 8) per axis and alike, partial bricks at the high faces.
+ *   marks          device uint8 [bz][by][bx], x fastest: non-zero = the brick is wanted
+ *   table          device int32 [bz][by][bx]: the brick's SLOT, or -1.  Slots ascend with the brick's linear index (k by + j) bx + i
+ *   bricks         device int32 [bx by bz]: the first n_bricks entries are the linear indices of the allocated bricks, ascending -
+ *                  the table's inverse
+ *   sums, weight   device [n_bricks][512][4] and [n_bricks][512] fp32, as in mnerf_tsdf_integrate, zeroed by the caller: voxel
+ *                  (i, j, k) of the brick in slot s is point s 512 + ((k & 7) 8 + (j & 7)) 8 + (i & 7).  Voxels of a partial brick
+ *                  outside the virtual grid are never updated and are never lattice points.
+ * The call order is mark (once per group of views), table, one device->host copy of the count, the caller's allocation,
+ * integrate_sparse (once per group), mesh_sparse.  A grid with nx ny nz == 0, or n_bricks == 0, is MNERF_OK and touches no buffer.
+ *
+ * mnerf_tsdf_bricks_mark - one workgroup per brick of the virtual grid, one thread per two voxels (so no linear voxel index over
+ * the virtual grid), one launch per 2^22 bricks.  A voxel is NEAR iff for at least one view mnerf_tsdf_integrate's update of that voxel happens
+ * with t < 1: the texel passes every test and -trunc <= sdf, sdf / trunc < 1.  The per-view step is the device function the
+ * integrators call, so the mark agrees with them bit for bit.  A NEAR voxel marks the brick of every voxel of its 3 x 3 x 3
+ * neighbourhood that lies inside the grid: that keeps every cell a triangle can come from, with the lattice points its vertices
+ * interpolate, inside allocated bricks, so the mesh is the dense one (see mnerf_tsdf_mesh_sparse).  The caller zeroes `marks`
+ * before the first call; calls OR into it (plain stores of 1, no atomic), which is how views beyond MNERF_MAX_VIEWS are added.
+ * MNERF_E_RANGE: as mnerf_tsdf_integrate, with bx by bz >= 2^31 in the place of nx ny nz >= 2^31.  MNERF_E_NULL: views, depth or
+ * marks missing. */
+#define MNERF_TSDF_BRICK 8
+int mnerf_tsdf_bricks_mark(const mnerf_view* views, int32_t n_views, int32_t height, int32_t width, int32_t legacy_coord,
+                           const float* depth, const float* opacity, const int32_t* n_consistent, int32_t min_consistent,
+                           float min_opacity, float trunc, float origin_x, float origin_y, float origin_z, float voxel, int32_t nx,
+                           int32_t ny, int32_t nz, uint8_t* marks, void* stream);
+
+/* mnerf_tsdf_bricks_table - marks -> table, bricks and count (device int64, 8-byte aligned: the number of marked bricks), by a
+ * count, the two-level scan and a scatter: four launches, the same bytes on every run.  Takes the BRICK grid (bx, by, bz).
+ *   workspace      device, 4-byte aligned, mnerf_tsdf_bricks_table_workspace_bytes(bx, by, bz) bytes: with N = bx by bz,
+ *                  B = ceil(N / 256), T = ceil(B / 1024): int32 [B] | int32 [T], 4 (B + T) bytes rounded up to 16
+ * With bx by bz == 0 the count, 0, is written all the same.  MNERF_E_RANGE: a size below 0, bx by bz >= 2^31.  MNERF_E_NULL: count
+ * missing; marks, table, bricks or workspace missing with bx by bz > 0.  MNERF_E_ALIGN: table, bricks or workspace not 4-byte, count
+ * not 8-byte aligned.  mnerf_tsdf_bricks_table_workspace_bytes: host only; -1 beyond the bounds. */
+int64_t mnerf_tsdf_bricks_table_workspace_bytes(int32_t bx, int32_t by, int32_t bz);
+int mnerf_tsdf_bricks_table(const uint8_t* marks, int32_t bx, int32_t by, int32_t bz, int32_t* table, int32_t* bricks, int64_t* count,
+                            void* workspace, void* stream);
+
+/* mnerf_tsdf_integrate_sparse - mnerf_tsdf_integrate on the allocated bricks: one workgroup per brick, the dense update on the
+ * voxel's GLOBAL index (centre = origin + (index + 0.5) voxel, one FMA per axis), so every allocated voxel ends with exactly the bits
+ * the dense volume has there.  Calls accumulate as the dense ones do.
+ * MNERF_E_RANGE: as mnerf_tsdf_bricks_mark; n_bricks below 0, above bx by bz or above 349 525 (see mnerf_tsdf_mesh_sparse).
+ * MNERF_E_NULL: views, depth, rgb, bricks, sums or weight missing.  MNERF_E_ALIGN: sums not 16-byte, weight or bricks not 4-byte
+ * aligned. */
+int mnerf_tsdf_integrate_sparse(const mnerf_view* views, int32_t n_views, int32_t height, int32_t width, int32_t legacy_coord,
+                                const float* depth, const float* opacity, const int32_t* n_consistent, int32_t min_consistent,
+                                const float* rgb, float min_opacity, float trunc, float origin_x, float origin_y, float origin_z,
+                                float voxel, int32_t nx, int32_t ny, int32_t nz, const int32_t* bricks, int64_t n_bricks, float* sums,
+                                float* weight, void* stream);
+
+/* mnerf_tsdf_mesh_sparse - mnerf_tsdf_mesh's nine launches over the n_bricks x 512 allocated points.  The neighbour p + e of a point
+ * is found through the table: the brick of its global index -> slot -> in-brick index.  A point of a brick without a slot, or
+ * outside the virtual grid, is not VALID.  Flags, edge masks, the owner rule, the 16 tet cases, the winding and the behaviour at a
+ * capacity (rows beyond it are dropped, the counts stay the totals) are those of mnerf_tsdf_mesh.
+ * ORDER: vertices ascend in (slot, in-brick index of the owner, direction index); triangles ascend in (slot of the cell's origin
+ * point, in-brick index, tet, triangle).
+ * GUARANTEE: with the marks of mnerf_tsdf_bricks_mark for the same views and grid (or any superset of them), the set of vertex rows
+ * and the triangles are exactly those of mnerf_tsdf_mesh on the dense volume, bit for bit, under that renumbering.
+ *   table, bricks  as mnerf_tsdf_bricks_table left them; table entries must lie in -1 .. n_bricks - 1 (they are not checked)
+ *   workspace      device, 4-byte aligned, mnerf_tsdf_mesh_sparse_workspace_bytes(n_bricks, bx, by, bz) bytes: the layout of
+ *                  mnerf_tsdf_mesh with N = 512 n_bricks
+ * MNERF_E_RANGE: a grid size below 0 (each of nx, ny, nz is an int32, so below 2^31), bx by bz >= 2^31, n_bricks below 0 or above
+ * bx by bz, 512 n_bricks > (2^31 - 1) / 12 - that is n_bricks > 349 525, the dense row bound on the allocated points -, a voxel not
+ * finite and positive, an origin not finite, min_weight not finite and positive, a negative capacity.  MNERF_E_NULL: sums, weight,
+ * table, bricks, counts or workspace missing, vertices or triangles missing with a capacity > 0.  MNERF_E_ALIGN: sums or vertices not
+ * 16-byte, counts not 8-byte, weight, triangles, table, bricks or workspace not 4-byte aligned.
+ * mnerf_tsdf_mesh_sparse_workspace_bytes: host only; 0 for n_bricks == 0, -1 beyond the bounds. */
+int64_t mnerf_tsdf_mesh_sparse_workspace_bytes(int64_t n_bricks, int32_t bx, int32_t by, int32_t bz);
+int mnerf_tsdf_mesh_sparse(const float* sums, const float* weight, const int32_t* table, const int32_t* bricks, int64_t n_bricks,
+                           float origin_x, float origin_y, float origin_z, float voxel, int32_t nx, int32_t ny, int32_t nz,
+                           float min_weight, float* vertices, int64_t vertex_capacity, int32_t* triangles, int64_t triangle_capacity,
+                           int64_t* counts, void* workspace, void* stream);
+
 /* MESH FINISHING (MESH EXPORT, continued; added under v12 without a layout change; matchnerf_amd/csrc/mesh_finish.hip): the clean-up
  * between the mesher's raw zero set and a mesh one can use - adjacency, removal of small connected components, Taubin smoothing,
  * vertex normals.  The functions take ANY indexed triangle mesh in the mesher's layout:

@@ -758,7 +758,9 @@ class Coach:
         (``fusion.mesh``: TSDF fusion + marching tetrahedra; float xyz + uchar rgb vertices and a face list), with nerf.mesh_resolution /
         mesh_voxel / mesh_trunc / mesh_min_weight where given, cleaned up by nerf.mesh_min_component / mesh_min_component_fraction
         (small connected components dropped), nerf.mesh_smooth (rounds of Taubin smoothing) and nerf.mesh_decimate (quadric
-        vertex clustering with cells of that many voxels, applied last) where given; with nerf.mesh_normals the vertices also carry
+        vertex clustering with cells of that many voxels, applied last) where given; with nerf.mesh_sparse the volume is
+        brick-sparse (``fusion.mesh(sparse=True)``: the same surface, the rows in brick order, for resolutions past the dense grid);
+        with nerf.mesh_normals the vertices also carry
         float nx ny nz (``fusion.vertex_normals`` of the mesh that is written).  With nerf.mesh_texture=B also <stem>_mesh.obj, .mtl and
         .png next to <stem>_mesh.ply: the same mesh with a texture atlas of B x B blocks baked from the views (``fusion.texture``;
         nerf.mesh_texture_best / mesh_texture_power / mesh_texture_rel_tol where given; nerf.mesh_texture_from = 'render' (default)
@@ -782,9 +784,11 @@ class Coach:
                                                                               ("trunc", "mesh_trunc"), ("min_weight", "mesh_min_weight"),
                                                                               ("min_component", "mesh_min_component"),
                                                                               ("min_component_fraction", "mesh_min_component_fraction"),
-                                                                              ("smooth", "mesh_smooth"), ("decimate", "mesh_decimate"))
+                                                                              ("smooth", "mesh_smooth"), ("decimate", "mesh_decimate"),
+                                                                              ("sparse", "mesh_sparse"))
                          if getattr(self.opts.nerf, name, None) is not None}
             fusion._decimate_cell("nerf.mesh_decimate", mesh_args.get("decimate", 0.0))  # refused before anything is rendered
+            fusion._sparse_flag("nerf.mesh_sparse", mesh_args.get("sparse", False))
             mesh_args.update({arg: getattr(self.opts.nerf, name) for arg, name in (("texture", "mesh_texture"), ("texture_best", "mesh_texture_best"),
                                                                                    ("texture_power", "mesh_texture_power"),
                                                                                    ("texture_vis_rel_tol", "mesh_texture_rel_tol"))

@@ -16,16 +16,7 @@
 #pragma clang fp contract(off)
 
 #include "fusion_common.hpp"
-
-struct TsdfGrid {
-  float ox, oy, oz, voxel;
-  int nx, ny, nz;
-};
-
-// the centre of voxel `index` along one axis: one FMA (index + 0.5 is exact)
-__device__ __forceinline__ float voxel_centre(int index, float voxel, float origin) {
-  return __builtin_fmaf((float)index + 0.5f, voxel, origin);
-}
+#include "tsdf_common.hpp"
 
 // ------------------------------------------------------------------------------------------------ integration
 __global__ __launch_bounds__(PC_BLOCK) void tsdf_integrate_kernel(FusionCams cams, int n_views, int height, int width, int legacy_coord,
@@ -38,24 +29,13 @@ __global__ __launch_bounds__(PC_BLOCK) void tsdf_integrate_kernel(FusionCams cam
   if (i >= n_voxels) return;
   const int ix = (int)(i % g.nx), iy = (int)((i / g.nx) % g.ny), iz = (int)(i / ((long long)g.nx * g.ny));
   const float px = voxel_centre(ix, g.voxel, g.ox), py = voxel_centre(iy, g.voxel, g.oy), pz = voxel_centre(iz, g.voxel, g.oz);
-  const float off = legacy_coord ? 0.0f : 0.5f;
-  const long long n = (long long)height * width;
+  const TsdfMaps maps = {height, width, legacy_coord, depth, opacity, n_consistent, min_consistent, min_opacity, trunc};
   float4 acc = reinterpret_cast<const float4*>(sums)[i];
   float wsum = weight[i];
   for (int j = 0; j < n_views; ++j) {  // (wave-uniform: the cameras are read through scalar loads)
-    const FusionCam& J = cams.cam[j];
-    float u, v, zc;
-    fusion_project(J, px, py, pz, u, v, zc);
-    if (!(zc > 0.0f)) continue;
-    const float fx = floorf((u - off) + 0.5f), fy = floorf((v - off) + 0.5f);
-    if (!(fx >= 0.0f && fx < (float)width && fy >= 0.0f && fy < (float)height)) continue;
-    const size_t texel = (size_t)j * n + (size_t)((int)fy) * width + (int)fx;
-    float z;
-    if (!fusion_value(depth, opacity, texel, min_opacity, J.v.near_, J.v.far_, z)) continue;
-    if (n_consistent && n_consistent[texel] < min_consistent) continue;
-    const float sdf = z - zc;
-    if (sdf < -trunc) continue;  // hidden behind the surface
-    const float t = fminf(1.0f, sdf / trunc);
+    size_t texel;
+    float t;
+    if (!tsdf_view_step(cams.cam[j], j, maps, px, py, pz, texel, t)) continue;
     acc.x = acc.x + t;
     acc.y = acc.y + rgb[texel * 3 + 0];
     acc.z = acc.z + rgb[texel * 3 + 1];
@@ -64,11 +44,6 @@ __global__ __launch_bounds__(PC_BLOCK) void tsdf_integrate_kernel(FusionCams cam
   }
   reinterpret_cast<float4*>(sums)[i] = acc;
   weight[i] = wsum;
-}
-
-static bool grid_ok(float ox, float oy, float oz, float voxel, int nx, int ny, int nz) {
-  return std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz) && std::isfinite(voxel) && voxel > 0.0f && nx >= 0 && ny >= 0 &&
-         nz >= 0;
 }
 
 extern "C" int mnerf_tsdf_integrate(const mnerf_view* views, int32_t n_views, int32_t height, int32_t width, int32_t legacy_coord,
@@ -103,68 +78,7 @@ extern "C" int mnerf_tsdf_integrate(const mnerf_view* views, int32_t n_views, in
   return mnerf_check_launch("mnerf_tsdf_integrate");
 }
 
-// ------------------------------------------------------------------------------------------------ the tetrahedron table
-// A cell's corner c = x | y << 1 | z << 2.  Tet t of a cell is 000 -> +e_a -> +e_a + e_b -> 111 with (a, b) the first two axes of
-// the permutations xyz xzy yxz yzx zxy zyx; the even permutations (tets 0, 3, 4) are positively oriented.  An edge direction is
-// e - 1 for e = the (non-zero) corner difference.
-constexpr int TET_A[6] = {0, 0, 1, 1, 2, 2};
-constexpr int TET_B[6] = {1, 2, 0, 2, 0, 1};
-constexpr int TET_ODD[6] = {0, 1, 1, 0, 0, 1};
-
-__host__ __device__ constexpr int tet_corner(int t, int k) {  // corner code of vertex k of tet t
-  return k == 0 ? 0 : k == 1 ? (1 << TET_A[t]) : k == 2 ? ((1 << TET_A[t]) | (1 << TET_B[t])) : 7;
-}
-
-// Case `code` (bit k: vertex k inside) of a POSITIVELY oriented tet -> bits 0-1 the triangle count, then six 4-bit polygon vertices
-// (lo << 2 | hi: the tet edge between vertices lo < hi), three per triangle.  With I the inside and O the outside vertices, both
-// ascending:  |I| = 1, I = {a}: the edges from a to the others ascending;  |I| = 3, O = {a}: the same;  |I| = 2, I = {a, b},
-// O = {c, d}: the quad ac ad bd bc as the triangles (ac ad bd) (ac bd bc) - the diagonal ac-bd.  That order has its normal from the
-// inside to the outside iff the permutation (I, O) of 0123 is even; an odd one swaps the last two vertices of every triangle (and so
-// does an odd tet, at the use).
-struct TetTable {
-  unsigned int row[16];
-};
-constexpr unsigned int tet_edge(int p, int q) { return (unsigned int)(p < q ? (p << 2 | q) : (q << 2 | p)); }
-constexpr TetTable make_tet_table() {
-  TetTable t = {};
-  for (int code = 0; code < 16; ++code) {
-    int in[4] = {}, out[4] = {}, n_in = 0, n_out = 0, inversions = 0;
-    for (int k = 0; k < 4; ++k) {
-      if (code >> k & 1) in[n_in++] = k;
-      else out[n_out++] = k;
-    }
-    for (int i = 0; i < n_in; ++i)
-      for (int o = 0; o < n_out; ++o) inversions += in[i] > out[o];
-    unsigned int poly[6] = {};
-    int n_tri = 0;
-    if (n_in == 1 || n_in == 3) {
-      const int a = n_in == 1 ? in[0] : out[0];
-      const int* rest = n_in == 1 ? out : in;
-      n_tri = 1;
-      for (int k = 0; k < 3; ++k) poly[k] = tet_edge(a, rest[k]);
-    } else if (n_in == 2) {
-      n_tri = 2;
-      const unsigned int ac = tet_edge(in[0], out[0]), ad = tet_edge(in[0], out[1]), bd = tet_edge(in[1], out[1]),
-                         bc = tet_edge(in[1], out[0]);
-      poly[0] = ac, poly[1] = ad, poly[2] = bd, poly[3] = ac, poly[4] = bd, poly[5] = bc;
-    }
-    if (inversions & 1)
-      for (int k = 0; k < n_tri; ++k) {
-        const unsigned int s = poly[3 * k + 1];
-        poly[3 * k + 1] = poly[3 * k + 2];
-        poly[3 * k + 2] = s;
-      }
-    unsigned int row = (unsigned int)n_tri;
-    for (int k = 0; k < 6; ++k) row |= poly[k] << (2 + 4 * k);
-    t.row[code] = row;
-  }
-  return t;
-}
-__constant__ const TetTable TET_TABLE = make_tet_table();
-
 // ------------------------------------------------------------------------------------------------ mesher
-constexpr unsigned char MF_VALID = 1, MF_INSIDE = 2, MF_CELL = 4;
-
 __global__ __launch_bounds__(PC_BLOCK) void mesh_flags_kernel(const float* __restrict__ sums, const float* __restrict__ weight,
                                                               float min_weight, int nx, int ny, int nz,
                                                               unsigned char* __restrict__ flags) {
@@ -279,26 +193,10 @@ __device__ __forceinline__ int cell_code(const unsigned char* __restrict__ flags
   return code;
 }
 
-__device__ __forceinline__ int tet_code(int cell, int t) {
-  return (cell >> tet_corner(t, 0) & 1) | (cell >> tet_corner(t, 1) & 1) << 1 | (cell >> tet_corner(t, 2) & 1) << 2 |
-         (cell >> tet_corner(t, 3) & 1) << 3;
-}
-
 // the table rows of the six tets of the cell at i (0: the tet emits nothing); returns the triangles the cell emits, their counts' sum
 __device__ __forceinline__ int cell_triangles(const unsigned char* __restrict__ flags, long long i, long long n, int nx, int ny,
                                               int rows[6]) {
-  const int cell = cell_code(flags, i, n, nx, ny);
-  int mine = 0;
-#pragma unroll
-  for (int t = 0; t < 6; ++t) rows[t] = 0;
-  if (cell > 0 && cell < 255) {  // (a branch, not six selects: most cells are empty or full, and whole waves skip the table)
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      rows[t] = (int)TET_TABLE.row[tet_code(cell, t)];
-      mine += rows[t] & 3;
-    }
-  }
-  return mine;
+  return cell_rows(cell_code(flags, i, n, nx, ny), rows);
 }
 
 __global__ __launch_bounds__(PC_BLOCK) void mesh_tcount_kernel(const unsigned char* __restrict__ flags, int nx, int ny, int nz,
@@ -334,16 +232,9 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_tscatter_kernel(const unsigned 
       int index[3];
 #pragma unroll
       for (int m = 0; m < 3; ++m) {
-        const int edge = rows[t] >> (2 + 4 * (3 * k + m)) & 15;
-        const int lo = edge >> 2, hi = edge & 3;
-        int c_lo = 0, c_hi = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // (selects instead of an indexed table: tet_corner(t, q) is a constant here)
-          c_lo = lo == q ? tet_corner(t, q) : c_lo;
-          c_hi = hi == q ? tet_corner(t, q) : c_hi;
-        }
+        int c_lo, dir;
+        tet_row_edge(rows[t], t, k, m, c_lo, dir);
         const long long owner = i + (c_lo & 1) + (long long)(c_lo >> 1 & 1) * nx + (long long)(c_lo >> 2) * nx * ny;
-        const int dir = (c_hi ^ c_lo) - 1;
         index[m] = vbase[owner] + __popc(masks[owner] & ((1 << dir) - 1));
       }
       const bool swap = TET_ODD[t];
@@ -352,27 +243,6 @@ __global__ __launch_bounds__(PC_BLOCK) void mesh_tscatter_kernel(const unsigned 
       triangles[row * 3 + 2] = swap ? index[1] : index[2];
     }
   }
-}
-
-// what bounds every index of the mesher below 2^31: at most 7 vertices per lattice point and 12 triangles per cell
-constexpr long long MESH_MAX_POINTS = ((1ll << 31) - 1) / 12;
-
-struct MeshWorkspace {
-  long long bytes;
-  int* vbase;                   // int32 [n]: the first vertex row of every lattice point
-  ScanScratch vscan, tscan;     // the scans over the points' vertices and the cells' triangles
-  unsigned char *flags, *masks;  // uint8 [n] each
-};
-static MeshWorkspace mesh_workspace(void* workspace, long long n) {
-  Carve c(workspace);
-  MeshWorkspace w;
-  w.vbase = c.array<int>((size_t)n);
-  w.vscan = c.scan(n);
-  w.tscan = c.scan(n);
-  w.flags = c.array<unsigned char>((size_t)n);
-  w.masks = c.array<unsigned char>((size_t)n);
-  w.bytes = c.bytes();
-  return w;
 }
 
 extern "C" int64_t mnerf_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {

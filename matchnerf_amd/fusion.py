@@ -27,6 +27,7 @@ from . import hip
 
 MAX_PARTNERS = hip.MNERF_MAX_VIEWS - 1  # a launch takes the reference and up to 15 partners
 MESH_GUESS_ROWS = 16  # the mesher's first buffers: vertex rows per voxel of the grid's three faces (twice as many triangles)
+SPARSE_GUESS_ROWS = 256  # the sparse mesher's: vertex rows per allocated brick - four per voxel of a brick's face
 
 
 def camera_centres(views):
@@ -200,7 +201,7 @@ def texture(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, bloc
 def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
          consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None, min_component=0,
          min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, decimate=0.0, texture=0, texture_vis_rel_tol=0.02,
-         texture_power=2, texture_best=False, texture_rgbs=None):
+         texture_power=2, texture_best=False, texture_rgbs=None, sparse=False):
     """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
     fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
     (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
@@ -220,10 +221,18 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
       texture       B > 0: -> (vertices, faces, uv, atlas), the FINISHED mesh textured (``texture`` below) with blocks of B texels from
                     the maps this call selected - the fused depths and counts are computed once - and ``texture_vis_rel_tol``,
                     ``texture_power``, ``texture_best``; ``texture_rgbs`` [K, h*w, 3]: colours to bake instead of ``rgbs`` (the vertex
-                    colours stay those of ``rgbs``).  No further copy.  0: nothing is launched and the pair is returned"""
+                    colours stay those of ``rgbs``).  No further copy.  0: nothing is launched and the pair is returned
+      sparse        True: the volume is stored in bricks of 8^3 voxels, only where a view saw a surface within ``trunc``
+                    (include/mnerf.h "SPARSE TSDF VOLUME": ``hip.tsdf_bricks_mark``, ``tsdf_bricks_table``, ``tsdf_integrate_sparse``,
+                    ``tsdf_mesh_sparse``), so memory follows the surface and grids the dense path refuses can be meshed.  The mesh is
+                    the dense one bit for bit - the same vertex rows and triangles - in another order: bricks ascending, then the
+                    in-brick index.  One more copy (the brick count); the first guess is a few hundred rows per brick.  ``decimate``
+                    keeps the grid aligned with the virtual volume and is refused, before the volume is allocated, when that grid
+                    has more cells than ``hip.mesh_decimate`` takes"""
     h, w = int(hw[0]), int(hw[1])
     n, k_views = h * w, len(views)
     decimate = _decimate_cell("mesh", decimate)
+    sparse = _sparse_flag("mesh", sparse)
     texture, texture_power = _texture_block("mesh", texture, texture_power)
     if k_views < 1 or (consistency and k_views < 2):
         raise ValueError(f"mesh: {k_views} view(s); cross-view consistency needs at least 2")
@@ -261,29 +270,17 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
         box = np.stack([box[0] - trunc, box[1] + trunc])
     dims = tuple(max(1, int(np.ceil((box[1, a] - box[0, a]) / voxel - 1e-9))) for a in range(3))
     origin = tuple(float(x) for x in box[0])
-    need = hip.tsdf_mesh_workspace_bytes(dims)
-    if need < 0:
-        raise ValueError(f"mesh: a grid of {dims} voxels is too large; raise voxel or lower resolution")
-    nx, ny, nz = dims
-    sums = torch.zeros(nz, ny, nx, 4, device=dev)
-    weight = torch.zeros(nz, ny, nx, device=dev)
+    if sparse and decimate > 0:
+        _decimate_grid_fits("mesh", dims, decimate)
+    groups = []  # the integrator's arguments per group of 16 views
     for first in range(0, k_views, hip.MNERF_MAX_VIEWS):
         group = slice(first, min(first + hip.MNERF_MAX_VIEWS, k_views))
-        hip.tsdf_integrate(views[group], maps[group], rgbs[group], origin, voxel, dims, trunc, sums, weight,
-                           opacity=None if map_opacity is None else map_opacity[group],
-                           n_consistent=None if counts is None else counts[group], min_consistent=min_consistent, legacy=legacy,
-                           min_opacity=min_opacity)
-    workspace = hip.export_workspace("tsdf_mesh", None, need, dev)
-    guess = min(7 * nx * ny * nz, max(1024, MESH_GUESS_ROWS * (nx * ny + ny * nz + nz * nx)))
-    vertices = torch.empty(guess, hip.VERTEX_FLOATS, device=dev)
-    faces = torch.empty(2 * guess, 3, dtype=torch.int32, device=dev)
-    _, _, totals = hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, workspace=workspace)
-    n_vertices, n_faces = (int(c) for c in totals.cpu())  # the one copy after the launch
-    if n_vertices > vertices.shape[0] or n_faces > faces.shape[0]:
-        vertices = torch.empty(n_vertices, hip.VERTEX_FLOATS, device=dev)
-        faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
-        hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces, counts=totals, workspace=workspace)
-    result = finish(vertices[:n_vertices], faces[:n_faces], min_component=min_component, min_component_fraction=min_component_fraction,
+        groups.append((views[group], maps[group], rgbs[group],
+                       dict(opacity=None if map_opacity is None else map_opacity[group],
+                            n_consistent=None if counts is None else counts[group], min_consistent=min_consistent, legacy=legacy,
+                            min_opacity=min_opacity)))
+    vertices, faces = (_sparse_volume_mesh if sparse else _dense_volume_mesh)(groups, origin, voxel, dims, trunc, min_weight, dev)
+    result = finish(vertices, faces, min_component=min_component, min_component_fraction=min_component_fraction,
                     smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, decimate_cell=decimate * voxel, decimate_origin=origin,
                     decimate_dims=tuple(int(np.ceil(d / decimate)) for d in dims) if decimate > 0 else None)
     if texture == 0:
@@ -291,6 +288,84 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
     colours = rgbs if texture_rgbs is None else texture_rgbs.reshape(k_views, n, 3)
     return result + _bake(*result, views, maps, map_opacity, counts, min_consistent, colours, legacy, min_opacity, texture,
                           texture_vis_rel_tol, texture_power, texture_best)
+
+
+def _run_mesher(run, guess, dev):
+    """``run(vertices, faces, counts)`` = one run of a mesher on buffers of a first guess of ``guess`` vertex rows (twice as many
+    triangles); the ONE copy of the two counts; a second run with exact sizes when they exceed the guess -> (vertices, faces)"""
+    vertices = torch.empty(guess, hip.VERTEX_FLOATS, device=dev)
+    faces = torch.empty(2 * guess, 3, dtype=torch.int32, device=dev)
+    _, _, totals = run(vertices, faces, None)
+    n_vertices, n_faces = (int(c) for c in totals.cpu())  # the one copy after the launch
+    if n_vertices > vertices.shape[0] or n_faces > faces.shape[0]:
+        vertices = torch.empty(n_vertices, hip.VERTEX_FLOATS, device=dev)
+        faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+        run(vertices, faces, totals)
+    return vertices[:n_vertices], faces[:n_faces]
+
+
+def _dense_volume_mesh(groups, origin, voxel, dims, trunc, min_weight, dev):
+    """the dense volume of ``mesh``: integrate every group, mesh -> (vertices, faces)"""
+    need = hip.tsdf_mesh_workspace_bytes(dims)
+    if need < 0:
+        raise ValueError(f"mesh: a grid of {dims} voxels is too large; raise voxel or lower resolution, or pass sparse=True")
+    nx, ny, nz = dims
+    sums = torch.zeros(nz, ny, nx, 4, device=dev)
+    weight = torch.zeros(nz, ny, nx, device=dev)
+    for group_views, group_maps, group_rgbs, args in groups:
+        hip.tsdf_integrate(group_views, group_maps, group_rgbs, origin, voxel, dims, trunc, sums, weight, **args)
+    workspace = hip.export_workspace("tsdf_mesh", None, need, dev)
+    guess = min(7 * nx * ny * nz, max(1024, MESH_GUESS_ROWS * (nx * ny + ny * nz + nz * nx)))
+    return _run_mesher(lambda vertices, faces, totals: hip.tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, faces,
+                                                                      counts=totals, workspace=workspace), guess, dev)
+
+
+def _sparse_volume_mesh(groups, origin, voxel, dims, trunc, min_weight, dev):
+    """the brick-sparse volume of ``mesh(sparse=True)``: mark the bricks every group of views can put a surface in, build the table,
+    copy the brick count (the ONE copy the dense path does not make), allocate, integrate, mesh -> (vertices, faces)"""
+    bdims = hip.brick_dims(dims)
+    if hip.tsdf_bricks_table_workspace_bytes(bdims) < 0:
+        raise ValueError(f"mesh: a grid of {dims} voxels has 2^31 bricks or more; raise voxel or lower resolution")
+    marks = torch.zeros(bdims[2], bdims[1], bdims[0], dtype=torch.uint8, device=dev)
+    for group_views, group_maps, _, args in groups:
+        hip.tsdf_bricks_mark(group_views, group_maps, origin, voxel, dims, trunc, marks, **args)
+    table, bricks, count = hip.tsdf_bricks_table(marks, bdims)
+    n_bricks = int(count.cpu())  # the copy
+    if n_bricks > hip.MAX_BRICKS:
+        raise ValueError(f"mesh: the surface touches {n_bricks} bricks of {hip.TSDF_BRICK}^3 voxels, more than the {hip.MAX_BRICKS} the "
+                         f"sparse mesher takes; raise voxel or lower resolution")
+    if n_bricks == 0:
+        return torch.empty(0, hip.VERTEX_FLOATS, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev)
+    sums = torch.zeros(n_bricks, hip.BRICK_POINTS, 4, device=dev)
+    weight = torch.zeros(n_bricks, hip.BRICK_POINTS, device=dev)
+    for group_views, group_maps, group_rgbs, args in groups:
+        hip.tsdf_integrate_sparse(group_views, group_maps, group_rgbs, origin, voxel, dims, trunc, bricks, n_bricks, sums, weight, **args)
+    workspace = hip.export_workspace("tsdf_mesh_sparse", None, hip.tsdf_mesh_sparse_workspace_bytes(n_bricks, bdims), dev)
+    guess = min(7 * hip.BRICK_POINTS * n_bricks, max(1024, SPARSE_GUESS_ROWS * n_bricks))
+    return _run_mesher(lambda vertices, faces, totals: hip.tsdf_mesh_sparse(sums, weight, table, bricks, n_bricks, origin, voxel, dims,
+                                                                             min_weight, vertices, faces, counts=totals,
+                                                                             workspace=workspace), guess, dev)
+
+
+def _decimate_grid_fits(what, dims, cell):
+    """refuse a decimation grid of ceil(n / cell) cells per axis that ``hip.mesh_decimate`` does not take, naming the smallest whole
+    number of voxels per cell that fits; host arithmetic only"""
+    cells = lambda k: tuple(int(np.ceil(d / k)) for d in dims)
+    fits = lambda g: g[0] * g[1] < 2 ** 31 and g[0] * g[1] * g[2] < 2 ** 31
+    if fits(cells(cell)):
+        return
+    k = max(1, int(np.ceil(cell)))
+    while not fits(cells(k)):
+        k += 1
+    raise ValueError(f"{what}: decimate={cell:g} lays {cells(cell)} cells over the grid of {dims} voxels, more than the decimation takes; "
+                     f"the smallest decimate that fits is {k}")
+
+
+def _sparse_flag(what, flag):
+    """the sparse switch of a mesh, checked before anything is launched: a bool (or 0 / 1), nothing else"""
+    if not isinstance(flag, (bool, int, np.bool_)) or int(flag) not in (0, 1):
+        raise ValueError(f"{what}: sparse={flag!r}; it is a switch: true or false")
+    return bool(flag)
 
 
 def _decimate_cell(what, cell):

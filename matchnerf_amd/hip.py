@@ -233,6 +233,14 @@ SIGNATURES = {
     "mnerf_tsdf_integrate": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3 + [_vp] * 3),
     "mnerf_tsdf_mesh_workspace_bytes": (_i64, [_i32] * 3),
     "mnerf_tsdf_mesh": (_int, [_vp] * 2 + [_f32] * 4 + [_i32] * 3 + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
+    "mnerf_tsdf_bricks_mark": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32] + [_f32] * 6 + [_i32] * 3 + [_vp] * 2),
+    "mnerf_tsdf_bricks_table_workspace_bytes": (_i64, [_i32] * 3),
+    "mnerf_tsdf_bricks_table": (_int, [_vp] + [_i32] * 3 + [_P(_i32), _P(_i32)] + [_vp] * 3),
+    "mnerf_tsdf_integrate_sparse": (_int, [_P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp] + [_f32] * 6 + [_i32] * 3
+                                    + [_P(_i32), _i64] + [_vp] * 3),
+    "mnerf_tsdf_mesh_sparse_workspace_bytes": (_i64, [_i64] + [_i32] * 3),
+    "mnerf_tsdf_mesh_sparse": (_int, [_vp] * 2 + [_P(_i32), _P(_i32), _i64] + [_f32] * 4 + [_i32] * 3
+                               + [_f32, _vp, _i64, _P(_i32), _i64] + [_vp] * 3),
     # (the rows of MESH TEXTURE and the two of the decimation: the header declares them after MESH FINISHING's first six; here they
     # stand in front of those, which tests/test_mesh_finish_cpu.py expects to be the table's last rows)
     "mnerf_mesh_texture_atlas": (_int, [_i64, _i32, _P(_i32)]),  # size: a host array
@@ -1762,6 +1770,153 @@ def tsdf_mesh(sums, weight, origin, voxel, dims, min_weight, vertices, triangles
     with _on(dev, stream) as st:
         check(lib.mnerf_tsdf_mesh(_ptr(sums), _ptr(weight), *grid, float(min_weight), _ptr(vertices), vertices.numel() // VERTEX_FLOATS,
                                   _ptr_i32(triangles), triangles.numel() // 3, _ptr(counts), _ptr(workspace), st), "mnerf_tsdf_mesh")
+    return vertices, triangles, counts
+
+
+# ----------------------------------------------------------------------- sparse TSDF volume (matchnerf_amd/csrc/tsdf_sparse.hip)
+
+TSDF_BRICK = 8  # MNERF_TSDF_BRICK: voxels per side of a brick
+BRICK_POINTS = TSDF_BRICK ** 3
+MAX_BRICKS = ((1 << 31) - 1) // 12 // BRICK_POINTS  # what mnerf_tsdf_mesh_sparse takes: 349 525
+
+
+def brick_dims(dims):
+    """(nx, ny, nz) -> (bx, by, bz), the bricks that cover the virtual grid"""
+    return tuple(-(-int(d) // TSDF_BRICK) for d in dims)
+
+
+def _sparse_maps(what, views, depth, opacity, n_consistent):
+    """the checks of ``tsdf_integrate`` on the maps -> (device, K, h, w)"""
+    import torch
+    _f32c(depth, "depth")
+    dev = depth.device
+    if depth.dim() != 3 or depth.shape[0] != len(views):
+        raise MnerfError(f"{what}: depth {tuple(depth.shape)} is not [{len(views)}, h, w]")
+    if opacity is not None and (_f32c(opacity, "opacity").shape != depth.shape or opacity.device != dev):
+        raise MnerfError(f"{what}: opacity {tuple(opacity.shape)} on {opacity.device} does not match depth {tuple(depth.shape)}")
+    if n_consistent is not None and (n_consistent.dtype != torch.int32 or n_consistent.numel() != depth.numel()
+                                     or not n_consistent.is_contiguous() or n_consistent.device != dev):
+        raise MnerfError(f"{what}: n_consistent must be a contiguous int32 tensor of {depth.numel()} elements on {dev}")
+    return (dev,) + tuple(int(x) for x in depth.shape)
+
+
+def _brick_tables(what, grid, table, bricks, n_bricks, dev):
+    """``table`` / ``bricks`` of the grid's bricks and ``n_bricks`` within them -> the number of bricks of the virtual grid"""
+    import torch
+    bx, by, bz = brick_dims(grid[4:])
+    for name, t in (("table", table), ("bricks", bricks)):
+        if t is not None:
+            _mesh_buffer(what, name, t, torch.int32, bx * by * bz, dev)
+    if not 0 <= int(n_bricks) <= bx * by * bz:
+        raise MnerfError(f"{what}: n_bricks={n_bricks} outside 0..{bx * by * bz}, the bricks of the grid {tuple(grid[4:])}")
+    return bx * by * bz
+
+
+def tsdf_bricks_mark(views, depth, origin, voxel, dims, trunc, marks, opacity=None, n_consistent=None, min_consistent=0, legacy=True,
+                     min_opacity=0.5, stream=None):
+    """Mark the 8^3-voxel bricks of the virtual grid that a surface of the maps can touch (mnerf_tsdf_bricks_mark; the rule is stated
+    in include/mnerf.h).  Maps and grid as for ``tsdf_integrate``; ``marks`` uint8 [bz, by, bx] (``brick_dims(dims)``) is the
+    caller's, zeroed before the first call; calls OR into it.  Enqueue only: -> marks."""
+    import torch
+    lib = load()
+    dev, k, h, w = _sparse_maps("tsdf_bricks_mark", views, depth, opacity, n_consistent)
+    grid = _grid(origin, voxel, dims)
+    bx, by, bz = brick_dims(grid[4:])
+    _mesh_buffer("tsdf_bricks_mark", "marks", marks, torch.uint8, bx * by * bz, dev)
+    arr = views if isinstance(views, C.Array) else view_array(views)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_bricks_mark(arr, k, h, w, int(bool(legacy)), _ptr(depth), _ptr(opacity), _ptr_i32(n_consistent),
+                                         int(min_consistent), float(min_opacity), float(trunc), *grid, _ptr(marks), st),
+              "mnerf_tsdf_bricks_mark")
+    return marks
+
+
+def tsdf_bricks_table_workspace_bytes(bdims):
+    return int(load().mnerf_tsdf_bricks_table_workspace_bytes(int(bdims[0]), int(bdims[1]), int(bdims[2])))
+
+
+def tsdf_bricks_table(marks, bdims, table=None, bricks=None, count=None, workspace=None, stream=None):
+    """Marks -> (table int32 [bz, by, bx]: every marked brick's slot, ascending with its linear index, -1 elsewhere; bricks int32
+    [bx by bz]: the marked bricks' linear indices in its first ``count`` entries; count: a 1-element int64 tensor) on the device
+    (mnerf_tsdf_bricks_table).  ``bdims`` = (bx, by, bz).  Enqueue only: the caller copies the count."""
+    import torch
+    lib = load()
+    bx, by, bz = (int(b) for b in bdims)
+    dev = marks.device
+    need = tsdf_bricks_table_workspace_bytes((bx, by, bz))
+    if need < 0:
+        raise MnerfError(f"tsdf_bricks_table: {bx}x{by}x{bz} bricks are out of range")
+    n = bx * by * bz
+    _mesh_buffer("tsdf_bricks_table", "marks", marks, torch.uint8, n, dev)
+    table = _mesh_buffer("tsdf_bricks_table", "table", table, torch.int32, n, dev).view(bz, by, bx)
+    bricks = _mesh_buffer("tsdf_bricks_table", "bricks", bricks, torch.int32, n, dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev) if count is None else _mesh_buffer("tsdf_bricks_table", "count", count, torch.int64, 1, dev)
+    workspace = export_workspace("tsdf_bricks_table", workspace, need, dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_bricks_table(_ptr(marks), bx, by, bz, _ptr_i32(table), _ptr_i32(bricks), _ptr(count), _ptr(workspace), st),
+              "mnerf_tsdf_bricks_table")
+    return table, bricks, count
+
+
+def tsdf_integrate_sparse(views, depth, rgb, origin, voxel, dims, trunc, bricks, n_bricks, sums, weight, opacity=None, n_consistent=None,
+                          min_consistent=0, legacy=True, min_opacity=0.5, stream=None):
+    """``tsdf_integrate`` on the allocated bricks of a sparse volume (mnerf_tsdf_integrate_sparse): ``bricks`` and ``n_bricks`` from
+    ``tsdf_bricks_table``; ``sums`` [n_bricks, 512, 4] and ``weight`` [n_bricks, 512] float32 are the caller's, zeroed before the
+    first call; calls accumulate.  Every allocated voxel gets the bits of the dense volume.  Enqueue only: -> (sums, weight)."""
+    lib = load()
+    what = "tsdf_integrate_sparse"
+    dev, k, h, w = _sparse_maps(what, views, depth, opacity, n_consistent)
+    _f32c(rgb, "rgb"), _f32c(sums, "sums"), _f32c(weight, "weight")
+    if rgb.numel() != 3 * depth.numel() or rgb.device != dev:
+        raise MnerfError(f"{what}: rgb {tuple(rgb.shape)} on {rgb.device} is not [{k}, {h * w}, 3] on {dev}")
+    grid = _grid(origin, voxel, dims)
+    n_bricks = int(n_bricks)
+    _brick_tables(what, grid, None, bricks, n_bricks, dev)
+    if sums.numel() != 4 * BRICK_POINTS * n_bricks or weight.numel() != BRICK_POINTS * n_bricks or sums.device != dev or weight.device != dev:
+        raise MnerfError(f"{what}: sums {tuple(sums.shape)} / weight {tuple(weight.shape)} are not [{n_bricks}, {BRICK_POINTS}, 4] / "
+                         f"[{n_bricks}, {BRICK_POINTS}] on {dev}")
+    arr = views if isinstance(views, C.Array) else view_array(views)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_integrate_sparse(arr, k, h, w, int(bool(legacy)), _ptr(depth), _ptr(opacity), _ptr_i32(n_consistent),
+                                              int(min_consistent), _ptr(rgb), float(min_opacity), float(trunc), *grid, _ptr_i32(bricks),
+                                              n_bricks, _ptr(sums), _ptr(weight), st), "mnerf_tsdf_integrate_sparse")
+    return sums, weight
+
+
+def tsdf_mesh_sparse_workspace_bytes(n_bricks, bdims):
+    return int(load().mnerf_tsdf_mesh_sparse_workspace_bytes(int(n_bricks), int(bdims[0]), int(bdims[1]), int(bdims[2])))
+
+
+def tsdf_mesh_sparse(sums, weight, table, bricks, n_bricks, origin, voxel, dims, min_weight, vertices, triangles, counts=None,
+                     workspace=None, stream=None):
+    """The triangle mesh of a sparse TSDF volume (mnerf_tsdf_mesh_sparse): the mesh of ``tsdf_mesh`` on the dense volume, bit for
+    bit, with the vertices in the order (slot, in-brick index, direction) and the triangles in (slot, in-brick index, tet, triangle).
+    Volume and tables as for ``tsdf_integrate_sparse``; the other arguments as for ``tsdf_mesh``, ``workspace`` of
+    ``tsdf_mesh_sparse_workspace_bytes(n_bricks, brick_dims(dims))`` bytes.  Enqueue only: -> (vertices, triangles, counts)."""
+    import torch
+    lib = load()
+    what = "tsdf_mesh_sparse"
+    _f32c(sums, "sums"), _f32c(weight, "weight"), _f32c(vertices, "vertices")
+    dev = sums.device
+    grid = _grid(origin, voxel, dims)
+    n_bricks = int(n_bricks)
+    _brick_tables(what, grid, table, bricks, n_bricks, dev)
+    if sums.numel() != 4 * BRICK_POINTS * n_bricks or weight.numel() != BRICK_POINTS * n_bricks or weight.device != dev:
+        raise MnerfError(f"{what}: sums {tuple(sums.shape)} / weight {tuple(weight.shape)} are not [{n_bricks}, {BRICK_POINTS}, 4] / "
+                         f"[{n_bricks}, {BRICK_POINTS}] on {dev}")
+    if vertices.device != dev or vertices.numel() % VERTEX_FLOATS:
+        raise MnerfError(f"{what}: vertices {tuple(vertices.shape)} on {vertices.device} is no [capacity, {VERTEX_FLOATS}] buffer on {dev}")
+    if triangles.dtype != torch.int32 or not triangles.is_contiguous() or triangles.device != dev or triangles.numel() % 3:
+        raise MnerfError(f"{what}: triangles must be a contiguous int32 [capacity, 3] tensor on {dev}")
+    counts = torch.zeros(2, dtype=torch.int64, device=dev) if counts is None else _mesh_buffer(what, "counts", counts, torch.int64, 2, dev)
+    need = tsdf_mesh_sparse_workspace_bytes(n_bricks, brick_dims(grid[4:]))
+    if need < 0:
+        raise MnerfError(f"{what}: {n_bricks} bricks of the grid {tuple(grid[4:])} are too many to mesh (at most {MAX_BRICKS})")
+    workspace = export_workspace(what, workspace, need, dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_tsdf_mesh_sparse(_ptr(sums), _ptr(weight), _ptr_i32(table), _ptr_i32(bricks), n_bricks, *grid, float(min_weight),
+                                         _ptr(vertices), vertices.numel() // VERTEX_FLOATS, _ptr_i32(triangles), triangles.numel() // 3,
+                                         _ptr(counts), _ptr(workspace), st), "mnerf_tsdf_mesh_sparse")
     return vertices, triangles, counts
 
 

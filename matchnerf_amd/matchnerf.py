@@ -551,7 +551,7 @@ class MatchNeRF(torch.nn.Module):
         return clouds
 
     MESH_ARGS = ("bounds", "resolution", "voxel", "trunc", "min_weight", "consistency", "min_component", "min_component_fraction", "smooth",
-                 "smooth_lambda", "smooth_mu", "decimate")
+                 "smooth_lambda", "smooth_mu", "decimate", "sparse")
 
     @staticmethod
     def check_texture(who, block, power, source, views):
@@ -577,7 +577,8 @@ class MatchNeRF(torch.nn.Module):
         truncated-signed-distance volume, its zero surface extracted by marching tetrahedra).  ``views`` and the one encoder pass as
         in ``export_points``; ``mesh_args``: bounds, resolution, voxel, trunc, min_weight, consistency, the clean-up of
         ``fusion.finish`` (min_component, min_component_fraction, smooth, smooth_lambda, smooth_mu), ``decimate`` (the cell of
-        ``fusion.decimate`` in voxels, applied last; 0: none) and the thresholds of ``export_points``.  ``normals=True``: triples (vertices, faces, normals [V, 4] float32 rows ``nx ny nz a``,
+        ``fusion.decimate`` in voxels, applied last; 0: none), ``sparse`` (True: the brick-sparse volume of ``fusion.mesh(sparse=True)`` -
+        the same mesh in another order, for resolutions past the dense grid) and the thresholds of ``export_points``.  ``normals=True``: triples (vertices, faces, normals [V, 4] float32 rows ``nx ny nz a``,
         ``fusion.vertex_normals`` of the finished mesh).  ``texture=B`` (4..64): the tuples grow by (uv [T, 3, 2], atlas [H, W, 4]) at
         the end - the finished mesh textured with blocks of B texels (``fusion.texture``; ``texture_best``, ``texture_power``,
         ``texture_vis_rel_tol``).  ``texture_from``: "render" bakes the frames rendered at the fusion poses, "images" - with
@@ -586,6 +587,7 @@ class MatchNeRF(torch.nn.Module):
         from . import fusion
         unknown = set(mesh_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"} - set(self.MESH_ARGS)
         fusion._decimate_cell("export_mesh", mesh_args.get("decimate", 0.0))
+        fusion._sparse_flag("export_mesh", mesh_args.get("sparse", False))
         texture, texture_power = self.check_texture("export_mesh", texture, texture_power, texture_from, views)
         maps, cams_of = self._fusion_maps("export_mesh", batch, views, render_path_mode, unknown)
         legacy = bool(self.opts.nerf.legacy_coord)

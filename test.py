@@ -29,7 +29,9 @@ path, kept where the other poses confirm them), with ``--vis_depth`` also the co
 ``--nerf.fuse_min_views=<confirming views>`` (min(2, K - 1)).  With ``--nerf.export_mesh`` also a coloured triangle mesh of the same
 maps, ``<stem>_mesh.ply`` (TSDF fusion, marching tetrahedra): ``--nerf.mesh_resolution=<voxels along the longest side>`` (256),
 ``--nerf.mesh_voxel=<world units>`` (instead of the resolution), ``--nerf.mesh_trunc=<world units>`` (4 voxels),
-``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)).  The mesh is cleaned up by
+``--nerf.mesh_min_weight=<views per lattice point>`` (min(2, K - 1)); ``--nerf.mesh_sparse`` stores the volume in bricks of 8^3
+voxels only where a surface can be - the same mesh in another row order, for resolutions (512, 1024) past the dense grid's limit of
+about 560 voxels a side.  The mesh is cleaned up by
 ``--nerf.mesh_min_component=<triangles>`` / ``--nerf.mesh_min_component_fraction=<of the largest component>`` (smaller connected
 components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, then reduced by ``--nerf.mesh_decimate=<cell in voxels>``
 (quadric vertex clustering: one vertex per occupied cell), and ``--nerf.mesh_normals`` adds ``nx ny nz`` per vertex.
@@ -42,7 +44,8 @@ re-renderings; with ``--nerf.export_geometry=sources`` only).
 
     python test.py --yaml=demo_own --nerf.export_geometry=sources
     python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192
-    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_decimate=4 --nerf.mesh_texture=8"""
+    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_decimate=4 --nerf.mesh_texture=8
+    python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_sparse --nerf.mesh_resolution=1024"""
 import os
 import sys
 
