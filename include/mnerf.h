@@ -1282,6 +1282,88 @@ int mnerf_mesh_texture_accumulate(const float* vertices, const int32_t* triangle
 int mnerf_mesh_texture_resolve(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, int32_t block,
                                int32_t best, const float* accum, float* atlas, void* stream);
 
+/* MESH RASTER (added under v12 without a layout change; matchnerf_amd/csrc/mesh_raster.hip): the indexed mesh seen from one pinhole
+ * camera - which triangle every pixel sees, at which depth and where on it - and the shading of that frame from the vertex colours or
+ * from the atlas of MESH TEXTURE.  It is what a report on the mesh, a preview and the texture's visibility test against the mesh
+ * itself are built from.  The conventions are those of MESH TEXTURE: pinhole camera-z depth, ONE mnerf_view HOST struct read during
+ * the call (by value in the kernel arguments), proj() and the pixel centres by legacy_coord as stated under GEOMETRY EXPORT, fp32
+ * with every operation rounded on its own and one FMA where the text says fma(), enqueue-only on `stream`, nothing allocated or
+ * copied, every argument check before any HIP call (MNERF_E_RANGE, then _NULL, then _ALIGN), no kernel reads or writes outside a
+ * buffer for ANY index value in `triangles`.  The mesh is any [V][8] / [T][3] mesh with 0 <= V < 2^31, 0 <= 3 T < 2^31; T == 0 is
+ * MNERF_OK and yields the empty frame.  Two runs give the same bytes.
+ *
+ * DETERMINISM.  The raster uses ONE kind of atomic, a 64-bit UNSIGNED INTEGER minimum, where the texture kernels use none.  The key
+ * of a covered pixel is (bits(z) << 32) | triangle: the bits of a positive float are monotone in its value, so keys order by depth
+ * and then by triangle index, and equal depths go to the lower index.  The minimum of a set of integers does not depend on the order
+ * in which its members arrive, so the key a pixel ends with is a function of the mesh and the camera alone.  No floating-point
+ * atomic, no scan, no expansion of work.
+ *
+ * A triangle is DROPPED unless its three indices lie in [0, V), its three positions are finite, and (u_k, v_k, z_k) = proj(view,
+ * p_k) are finite with z_k > 0 for k = 0, 1, 2.  LIMITATION: a triangle that crosses the camera plane is dropped, not clipped.
+ *
+ * COVERAGE of the pixel centre P = (px, py) = (x, y) + (0 with legacy_coord, 0.5 otherwise), two-sided (front and back faces both
+ * cover).  Edge k runs from vertex a = (k + 1) mod 3 to vertex b = (k + 2) mod 3, opposite vertex k.  For an edge a -> b:
+ *   swap = u_b < u_a or (u_b == u_a and v_b < v_a);  F = the first endpoint in that (u, then v) order, S = the other
+ *   dx = u_S - u_F;  dy = v_S - v_F;  e = fma(dx, py - v_F, -(dy * (px - u_F)));  e = 0 when P equals F or S bit for bit (at S the
+ *   fma would leave the rounding error of dy * dx);  value(a -> b, P) = -e with swap, e without
+ * so two triangles that traverse one edge in opposite directions get bitwise opposite values at every pixel, whatever the rounding.
+ *   area = value(1 -> 2, (u_0, v_0));  area == 0 (or a NaN): no coverage;  s = +1 for area > 0, -1 otherwise
+ *   E_k = s * value(a -> b, P);  the gradient of E_k is (gx, gy) = s * (-dy, dx) without swap, s * (dy, -dx) with it (signs only)
+ *   the triangle OWNS edge k iff gx > 0, or gx == 0 and gy > 0: its interior lies on the +x side of the edge, or the edge is
+ *   horizontal and the interior lies on the +y side - the top-left rule
+ *   P is covered iff for k = 0, 1, 2: E_k > 0, or E_k == 0 and the triangle owns edge k
+ *   sum = (E_0 + E_1) + E_2, and the pixel is not covered unless sum > 0;  l_k = E_k / sum;  q_k = l_k / z_k;  w = (q_0 + q_1) + q_2;
+ *   z = 1 / w;  b_1 = q_1 / w;  b_2 = q_2 / w - perspective-correct weights of the vertices 1 and 2
+ * GUARANTEE: a pixel centre on an edge or a vertex shared by triangles on both sides is covered by exactly one of them; a welded
+ * closed mesh has neither pinholes nor doubly claimed centres along its edges.
+ *
+ * mnerf_mesh_raster - three launches on a workspace of uint64 [height][width] keys, 8-byte aligned, mnerf_mesh_raster_workspace_bytes
+ * (host only: 8 height width; -1 for a side below 1 or height x width >= 2^31):
+ *   clear          one thread per pixel: the key becomes all ones
+ *   raster         one wave64 per triangle, four triangles per workgroup of 256: the wave projects the vertices, drops the triangle
+ *                  as above, and walks the 8 x 8-pixel blocks (aligned to multiples of 8) that meet the pixels from
+ *                  floor(min u - offset) - 1 to ceil(max u - offset) + 1, rows alike, clamped to the frame, lane = pixel.  A covered
+ *                  pixel with z > 0 and view.near_ <= z <= view.far_ issues one atomic minimum of its key
+ *   resolve        one thread per pixel: the winner's coverage quantities recomputed by the same arithmetic
+ *   face           device int32 [height][width]: the triangle, -1 where nothing was hit
+ *   depth          device fp32 [height][width]: z, 0 where nothing was hit - not VALID for any consumer with near_ > 0
+ *   bary           device fp32 [height][width][2]: (b_1, b_2), 0 where nothing was hit
+ * MNERF_E_RANGE: the bounds of the mesh, a side below 1 or height x width >= 2^31, workspace_bytes below the need, a singular intr or
+ * extr.  MNERF_E_NULL: view, face, depth, bary or workspace missing; with T > 0 triangles or (with V > 0) vertices missing.
+ * MNERF_E_ALIGN: vertices not 16-byte, workspace not 8-byte, any other pointer not 4-byte aligned.
+ *
+ * mnerf_mesh_shade - one thread per pixel of a rastered frame (face, bary as written above; a face outside [0, T) or with an index
+ * outside [0, V) is no hit):
+ *   rgba           device fp32 [height][width][4], 16-byte aligned: a = 1 on a hit, 0 0 0 0 elsewhere
+ *   atlas == NULL  rgb = fma(b_2, q2 - q0, fma(b_1, q1 - q0, q0)) per channel of the three VERTEX colours (block and the atlas sides
+ *                  are not read)
+ *   atlas          device fp32 [atlas_height][atlas_width][4], 16-byte aligned, the sides of mnerf_mesh_texture_atlas(T, block): the
+ *                  corners' texel coordinates (block origin + corner, the numerators of mnerf_mesh_texture_uv) are blended by
+ *                  (b_1, b_2) in the same fma form, per coordinate; rgb = the bilinear value at that point with texel centres at
+ *                  + 0.5: the taps and weights of mnerf_depth_consistency over the atlas (x0 = max(min(floor(fx), W - 2), 0), ...),
+ *                  top + ay (bot - top) in the a + t b form.  A tap of weight zero is not read (x1 = x0 where ax == 0, rows alike),
+ *                  and a tap the triangle does not own is read at the innermost tap instead - (x0, y0) for a lower triangle,
+ *                  (x1, y1) for an upper one; only rounding puts a tap there, with a weight below 1e-5.  The rgb therefore depends on
+ *                  the triangle's own texels alone (the atlas GUARANTEE)
+ *   normal         NULL, or device fp32 [height][width][4], 16-byte aligned: n = (p1 - p0) x (p2 - p0) in the fma form of
+ *                  mnerf_mesh_normals, divided by |n| = sqrt(fma(n_z, n_z, fma(n_y, n_y, n_x n_x))) per component, negated when
+ *                  fma(n_z, e_z, fma(n_y, e_y, n_x e_x)) < 0 for e = the camera centre (the translation column of the host-inverted
+ *                  extr) - p0;  the fourth float is 0;  0 0 0 0 where there is no hit or |n| is not positive and finite
+ * MNERF_E_RANGE: the bounds of the mesh, a side below 1 or height x width >= 2^31, with an atlas a block outside 4..64 or sides above
+ * 16384 or other than mnerf_mesh_texture_atlas(T, block), a singular intr or extr.  MNERF_E_NULL: view, face, bary or rgba missing;
+ * with T > 0 triangles or (with V > 0) vertices missing.  MNERF_E_ALIGN: vertices, atlas, rgba or normal not 16-byte, any other
+ * pointer not 4-byte aligned.
+ *
+ * One wave walks all blocks of its triangle: a triangle that fills the frame costs height x width / 64 steps of one wave.  There is
+ * no anti-aliasing and no mip-mapping. */
+int64_t mnerf_mesh_raster_workspace_bytes(int32_t height, int32_t width);
+int mnerf_mesh_raster(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, const mnerf_view* view,
+                      int32_t height, int32_t width, int32_t legacy_coord, int32_t* face, float* depth, float* bary, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+int mnerf_mesh_shade(const float* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, const int32_t* face,
+                     const float* bary, int32_t height, int32_t width, const float* atlas, int32_t atlas_height, int32_t atlas_width,
+                     int32_t block, const mnerf_view* view, float* rgba, float* normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -765,8 +765,14 @@ class Coach:
         .png next to <stem>_mesh.ply: the same mesh with a texture atlas of B x B blocks baked from the views (``fusion.texture``;
         nerf.mesh_texture_best / mesh_texture_power / mesh_texture_rel_tol where given; nerf.mesh_texture_from = 'render' (default)
         | 'images': the source photographs instead of their re-renderings, with 'sources' views only); <stem>_mesh.ply is the same
-        bytes with or without it.  One process (not sharded).
-        Returns {set: [path of every .ply, and of every .obj after its mesh's .ply]}."""
+        bytes with or without it; nerf.mesh_texture_visibility = 'views' (default) | 'mesh': test a texel's visibility against the
+        mesh's own depth.  With nerf.mesh_report also <stem>_mesh_report.json: ``fusion.mesh_report`` of the written mesh against the
+        maps it was fused from (per view and pooled: coverage, spurious, relative depth error, PSNR); with nerf.mesh_preview also
+        <stem>_mesh_preview_<k>.png per fusion view, the shaded mesh next to the field's frame (``mesh | render``, 2 w x h).  Both
+        shade from the atlas when one was baked, from the vertex colours otherwise.  One process (not sharded).
+        Returns {set: [path of every .ply, of every .obj after its mesh's .ply, then the report and the previews of that mesh]}."""
+        import json
+
         from PIL import Image
 
         from . import fusion
@@ -791,11 +797,15 @@ class Coach:
             fusion._sparse_flag("nerf.mesh_sparse", mesh_args.get("sparse", False))
             mesh_args.update({arg: getattr(self.opts.nerf, name) for arg, name in (("texture", "mesh_texture"), ("texture_best", "mesh_texture_best"),
                                                                                    ("texture_power", "mesh_texture_power"),
-                                                                                   ("texture_vis_rel_tol", "mesh_texture_rel_tol"))
+                                                                                   ("texture_vis_rel_tol", "mesh_texture_rel_tol"),
+                                                                                   ("texture_visibility", "mesh_texture_visibility"))
                               if getattr(self.opts.nerf, name, None) is not None})
+            fusion._visibility("nerf.mesh_texture_visibility", mesh_args.get("texture_visibility", "views"))
             texture_from = getattr(self.opts.nerf, "mesh_texture_from", None) or "render"
             self.model.check_texture("nerf.mesh_texture", mesh_args.get("texture", 0), mesh_args.get("texture_power", 2), texture_from, views)
         mesh_normals = bool(getattr(self.opts.nerf, "mesh_normals", None))
+        mesh_report = mesh_args is not None and bool(getattr(self.opts.nerf, "mesh_report", None))
+        mesh_preview = mesh_args is not None and bool(getattr(self.opts.nerf, "mesh_preview", None))
         out_root = os.path.join(self.opts.output_path, "geometry")
         written = {}
         for loader in self.test_loaders:
@@ -829,6 +839,28 @@ class Coach:
                             fusion.write_obj(path, vertices, faces, *textured, vertex_normals)
                             written[name].append(path)
                             self.say(f"[coach] {name}: a {textured[1].shape[1]} x {textured[1].shape[0]} atlas -> {path}")
+                        if mesh_report or mesh_preview:
+                            shading = dict(atlas=textured[1] if textured else None, block=mesh_args.get("texture", 0) if textured else 0)
+                            legacy = bool(self.opts.nerf.legacy_coord)
+                        if mesh_report:
+                            report = fusion.mesh_report(vertices, faces, maps.views[bi], maps.depth[bi], maps.opacity[bi], maps.rgb[bi],
+                                                        maps.hw, legacy, min_opacity=fuse_args.get("min_opacity", 0.5), **shading)
+                            path = os.path.join(out_dir, f"{stem}_mesh_report.json")
+                            with open(path, "w") as f:
+                                json.dump(report, f, indent=1)
+                            written[name].append(path)
+                            pooled = report["pooled"]
+                            self.say(f"[coach] {name}: the mesh covers {pooled['coverage']:.3f} of the field, {pooled['spurious']:.3f} of it "
+                                     f"is spurious, depth within {pooled['depth_rel_mean']:.4f}, {pooled['psnr']:.2f} dB -> {path}")
+                        if mesh_preview:
+                            h, w = maps.hw
+                            rgba = fusion.render_mesh(vertices, faces, fusion._open_views(maps.views[bi]), maps.hw, legacy, **shading)[0]
+                            both = torch.cat([rgba[..., :3], maps.rgb[bi].reshape(-1, h, w, 3)], 2)  # mesh | render
+                            both = (both.nan_to_num().clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
+                            for k, panel in enumerate(both):
+                                path = os.path.join(out_dir, f"{stem}_mesh_preview_{k}.png")
+                                Image.fromarray(panel).save(path)
+                                written[name].append(path)
                     for k in range(panels.shape[1] if panels is not None else 0):
                         Image.fromarray(panels[bi, k]).save(os.path.join(out_dir, f"{stem}_depth{k}.png"))
             self.model.nerf_setbg_opaque = False

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libmnerf_hip.so")
 SOURCES = ["api.cpp", "backward.hip", "composite.hip", "conv.hip", "conv_backward.hip", "cost_volume.hip", "cost_volume_mm.hip", "decoder.hip", "decoder_backward.hip", "decoder_fused.hip", "encoder_backward.hip", "encoder_block.hip",
-           "free_rays.hip", "fusion.hip", "gemm.hip", "geometry.hip", "instance_norm.hip", "lpips.hip", "mesh.hip", "mesh_finish.hip", "mesh_texture.hip", "metrics.hip", "optim.hip", "qkv.hip", "render_chunk.hip", "scan.hip", "tsdf_sparse.hip", "window_attention.hip", "window_attention_backward.hip"]
+           "free_rays.hip", "fusion.hip", "gemm.hip", "geometry.hip", "instance_norm.hip", "lpips.hip", "mesh.hip", "mesh_finish.hip", "mesh_raster.hip", "mesh_texture.hip", "metrics.hip", "optim.hip", "qkv.hip", "render_chunk.hip", "scan.hip", "tsdf_sparse.hip", "window_attention.hip", "window_attention_backward.hip"]
 # per-source extra flags.
 # decoder_fused.hip: the one-launch ray chunk.  Its workgroups run the cost-volume walk on SIMDs where another workgroup issues
 # 16-bit 32x32x16 matrix instructions; packed-fp32 vector instructions lose results in lanes 48-63 there, so

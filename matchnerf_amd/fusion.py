@@ -19,6 +19,10 @@ grid (``hip.mesh_decimate``): one vertex per occupied cell, the same bytes on ev
 ``texture`` bakes the views' colours onto such a mesh (include/mnerf.h "MESH TEXTURE", matchnerf_amd/csrc/mesh_texture.hip): a
 per-triangle atlas whose layout is a function of the triangle count, filled from every view that sees a texel's surface point;
 ``write_obj`` writes the result with its material and image.
+
+``render_mesh`` looks at such a mesh (include/mnerf.h "MESH RASTER", matchnerf_amd/csrc/mesh_raster.hip): a deterministic rasterizer
+gives, per pose, the triangle, depth and colour of every pixel.  ``mesh_report`` compares those frames with the field's own maps,
+and ``texture(visibility="mesh")`` tests a texel's visibility against the mesh's depth instead of the views'.
 """
 import numpy as np
 import torch
@@ -127,6 +131,13 @@ def _texture_block(what, block, power):
     return int(block), int(power)
 
 
+def _visibility(what, visibility):
+    """the depth a texture's visibility test reads, checked before anything is launched"""
+    if visibility not in ("views", "mesh"):
+        raise ValueError(f"{what}: a texture visibility of {visibility!r}; it is 'views' or 'mesh'")
+    return visibility
+
+
 def _consistent_maps(views, depths, opacities, legacy, px_tol, rel_tol, min_opacity):
     """``hip.depth_consistency`` with every view as the reference once -> (fused [K, h, w] float32, counts [K, h, w] int32): what the
     integrator and the texture read instead of the raw maps.  Beyond 16 views a reference is checked against its 15 nearest partners."""
@@ -167,7 +178,7 @@ def _bake(vertices, faces, views, maps, map_opacity, counts, min_consistent, rgb
 
 
 def texture(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, block=8, consistency=True, px_tol=1.0, rel_tol=0.01,
-            min_opacity=0.5, min_consistent=None, vis_rel_tol=0.02, power=2, best=False):
+            min_opacity=0.5, min_consistent=None, vis_rel_tol=0.02, power=2, best=False, visibility="views"):
     """Bake a texture atlas for an indexed mesh from K views of its scene (include/mnerf.h "MESH TEXTURE") -> (uv [T, 3, 2] float32: the
     texture coordinates of every triangle's corners, origin top-left; atlas [H, W, 4] float32 ``r g b a``) on the device.  Every
     triangle owns a right-triangle patch of a ``block`` x ``block`` square it shares with one other triangle, so the atlas's size is a
@@ -176,12 +187,23 @@ def texture(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, bloc
     angle between the view and the normal (``best``: the single view of the largest weight); where no view sees the surface it falls
     back to the triangle's vertex colours, with a = 0.  The maps are selected as in ``mesh`` (``consistency``, ``px_tol``, ``rel_tol``,
     ``min_opacity``, ``min_consistent``); views beyond 16 are accumulated in groups of 16, in order.  No device->host copy; the same
-    bytes on every run."""
+    bytes on every run.
+      visibility    "views" (the default): as above.  "mesh": the depth a texel is tested against is the MESH's own, rasterized at
+                    every view (``mesh_depths``), so a surface that decimation or smoothing moved away from the views' depth maps
+                    still takes their colours; the maps' selection (``consistency`` ...) then plays no part and nothing of it is
+                    launched"""
     h, w = int(hw[0]), int(hw[1])
     n, k_views = h * w, len(views)
     block, power = _texture_block("texture", block, power)
+    visibility = _visibility("texture", visibility)
     if block == 0:
         raise ValueError("texture: a block of 0")
+    if visibility == "mesh":
+        if k_views < 1:
+            raise ValueError("texture: no view")
+        mesh_views, maps = mesh_depths(vertices, faces, views, (h, w), legacy)
+        return _bake(vertices, faces, mesh_views, maps, None, None, 0, rgbs.reshape(k_views, n, 3), legacy, min_opacity, block, vis_rel_tol,
+                     power, best)
     if k_views < 1 or (consistency and k_views < 2):
         raise ValueError(f"texture: {k_views} view(s); cross-view consistency needs at least 2")
     if min_consistent is None:
@@ -201,7 +223,7 @@ def texture(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, bloc
 def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=256, voxel=None, trunc=None, min_weight=None,
          consistency=True, px_tol=1.0, rel_tol=0.01, min_opacity=0.5, min_consistent=None, min_component=0,
          min_component_fraction=0.0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, decimate=0.0, texture=0, texture_vis_rel_tol=0.02,
-         texture_power=2, texture_best=False, texture_rgbs=None, sparse=False):
+         texture_power=2, texture_best=False, texture_rgbs=None, sparse=False, texture_visibility="views"):
     """K views of one scene -> (vertices [V, 8] float32 rows ``x y z w | r g b 0``, faces [T, 3] int32) on the device: the depth maps
     fused into a truncated-signed-distance volume (``hip.tsdf_integrate``) and its zero surface extracted by marching tetrahedra
     (``hip.tsdf_mesh``: welded vertices, vertices and faces in a defined order, the same bytes on every run).  Arguments as ``fuse``.
@@ -222,6 +244,8 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
                     the maps this call selected - the fused depths and counts are computed once - and ``texture_vis_rel_tol``,
                     ``texture_power``, ``texture_best``; ``texture_rgbs`` [K, h*w, 3]: colours to bake instead of ``rgbs`` (the vertex
                     colours stay those of ``rgbs``).  No further copy.  0: nothing is launched and the pair is returned
+      texture_visibility   "views", or "mesh": the texels' visibility is tested against the finished mesh rasterized at every view
+                    (``texture`` below) - what a decimated mesh wants
       sparse        True: the volume is stored in bricks of 8^3 voxels, only where a view saw a surface within ``trunc``
                     (include/mnerf.h "SPARSE TSDF VOLUME": ``hip.tsdf_bricks_mark``, ``tsdf_bricks_table``, ``tsdf_integrate_sparse``,
                     ``tsdf_mesh_sparse``), so memory follows the surface and grids the dense path refuses can be meshed.  The mesh is
@@ -234,6 +258,7 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
     decimate = _decimate_cell("mesh", decimate)
     sparse = _sparse_flag("mesh", sparse)
     texture, texture_power = _texture_block("mesh", texture, texture_power)
+    texture_visibility = _visibility("mesh", texture_visibility)
     if k_views < 1 or (consistency and k_views < 2):
         raise ValueError(f"mesh: {k_views} view(s); cross-view consistency needs at least 2")
     if min_consistent is None:
@@ -286,6 +311,10 @@ def mesh(views, depths, opacities, rgbs, hw, legacy, *, bounds=None, resolution=
     if texture == 0:
         return result
     colours = rgbs if texture_rgbs is None else texture_rgbs.reshape(k_views, n, 3)
+    if texture_visibility == "mesh":
+        mesh_views, mesh_maps = mesh_depths(*result, views, (h, w), legacy)
+        return result + _bake(*result, mesh_views, mesh_maps, None, None, 0, colours, legacy, min_opacity, texture, texture_vis_rel_tol,
+                              texture_power, texture_best)
     return result + _bake(*result, views, maps, map_opacity, counts, min_consistent, colours, legacy, min_opacity, texture,
                           texture_vis_rel_tol, texture_power, texture_best)
 
@@ -453,6 +482,122 @@ def vertex_normals(vertices, faces):
     vertices, faces = vertices.contiguous(), faces.contiguous()
     adjacency = hip.mesh_adjacency(faces, vertices.shape[0])
     return hip.mesh_normals(vertices, faces, adjacency)
+
+
+# ------------------------------------------------------------------------------------------------ looking at the mesh
+MESH_FAR = 3.0e38  # the far_ of a view that clips no mesh depth (any finite fp32 depth is below it)
+
+
+def _open_views(views):
+    """the views with a depth range that clips nothing: near_ = 0 (a rastered depth is > 0), far_ = MESH_FAR"""
+    return [hip.make_view(list(v.extr), list(v.intr), 0.0, MESH_FAR) for v in views]
+
+
+def _frame_size(what, hw):
+    """the frame of a raster, checked before anything is allocated or launched -> (h, w)"""
+    h, w = int(hw[0]), int(hw[1])
+    if hip.mesh_raster_workspace_bytes(h, w) < 0:
+        raise ValueError(f"{what}: a frame of {h}x{w}; both sides must be at least 1 and h w below 2^31")
+    return h, w
+
+
+def render_mesh(vertices, faces, views, hw, legacy, *, atlas=None, block=0, normals=False):
+    """Rasterize and shade an indexed mesh at K poses (include/mnerf.h "MESH RASTER") -> (rgba [K, h, w, 4] float32, depth [K, h, w]
+    float32, face [K, h, w] int32) on the device, and normals [K, h, w, 4] as a fourth with ``normals``.
+      views      [hip.View] * K, any K >= 0: extr, the intr of the (h, w) grid; only depths in near_ .. far_ are drawn
+      face       the triangle a pixel sees (the nearest; equal depths go to the lower index), -1 where none
+      depth      its camera-z there, 0 where none;  rgba: a = 1 on a hit and 0 0 0 0 elsewhere
+      atlas, block   shade from the atlas of ``texture`` instead of the vertex colours
+    Two-sided; triangles that cross the camera plane are dropped, not clipped.  One key buffer of 8 h w bytes serves all poses.  No
+    device->host copy; the same bytes on every run."""
+    h, w = _frame_size("render_mesh", hw)
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    dev, k_views = faces.device, len(views)
+    if atlas is not None:
+        atlas = atlas.contiguous()
+    rgba = torch.empty(k_views, h, w, hip.RGBA_FLOATS, device=dev)
+    depth = torch.empty(k_views, h, w, device=dev)
+    face = torch.empty(k_views, h, w, dtype=torch.int32, device=dev)
+    normal = torch.empty(k_views, h, w, hip.RGBA_FLOATS, device=dev) if normals else None
+    workspace = hip.export_workspace("mesh_raster", None, hip.mesh_raster_workspace_bytes(h, w), dev)
+    bary = torch.empty(h, w, 2, device=dev)
+    for k, view in enumerate(views):
+        hip.mesh_raster(vertices, faces, view, (h, w), legacy=legacy, out=(face[k], depth[k], bary), workspace=workspace)
+        hip.mesh_shade(vertices, faces, face[k], bary, view, atlas=atlas, block=block, normals=normals,
+                       out=(rgba[k], normal[k]) if normals else rgba[k])
+    return (rgba, depth, face, normal) if normals else (rgba, depth, face)
+
+
+def mesh_depths(vertices, faces, views, hw, legacy):
+    """The mesh's own depth maps at the views -> (views with near_ / far_ so wide that no mesh depth is clipped, depth [K, h, w]
+    float32).  What ``texture(visibility="mesh")`` hands to the accumulation as its depth maps.  Rasterized only: nothing is shaded.
+    A pixel that sees no triangle takes the SMALLEST depth its eight neighbours see, and 0 - not VALID: near_ is the smallest positive
+    float - if none sees one.  The accumulation wants all four taps of a projection VALID, and without that rim every texel within
+    a pixel of the mesh's silhouette would lose its view; the smallest neighbour is the conservative choice next to an occluder."""
+    h, w = _frame_size("mesh_depths", hw)
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    dev = faces.device
+    open_views = _open_views(views)
+    depth = torch.empty(len(views), h, w, device=dev)
+    face, bary = torch.empty(h, w, dtype=torch.int32, device=dev), torch.empty(h, w, 2, device=dev)
+    workspace = hip.export_workspace("mesh_raster", None, hip.mesh_raster_workspace_bytes(h, w), dev)
+    for k, view in enumerate(open_views):
+        hip.mesh_raster(vertices, faces, view, (h, w), legacy=legacy, out=(face, depth[k], bary), workspace=workspace)
+    if len(views):  # the rim: a min-pool over the hit depths (no arithmetic on them - the same bytes on every run)
+        hit = depth > 0
+        nearest = -torch.nn.functional.max_pool2d(-torch.where(hit, depth, torch.full_like(depth, float("inf")))[:, None], 3, 1, 1)[:, 0]
+        depth = torch.where(hit, depth, torch.where(torch.isfinite(nearest), nearest, torch.zeros_like(depth))).contiguous()
+    tiny = float(np.finfo(np.float32).tiny)  # the accumulation's VALID test: near_ <= z, and z == 0 where nothing was hit
+    return [hip.make_view(list(v.extr), list(v.intr), tiny, MESH_FAR) for v in views], depth
+
+
+REPORT_KEYS = ("coverage", "spurious", "depth_rel_mean", "depth_rel_median", "psnr", "field_pixels", "mesh_pixels", "common_pixels")
+
+
+def mesh_report(vertices, faces, views, depths, opacities, rgbs, hw, legacy, *, atlas=None, block=0, min_opacity=0.5):
+    """Compare an indexed mesh with the field it was made from: the mesh rendered at the K fusion views (``render_mesh``, no depth
+    clipped) against the field's own maps -> dict(views=[row] * K, pooled=row), a row being a dict of
+      coverage           the share of the pixels with field opacity >= ``min_opacity`` that the mesh covers
+      spurious           the share of the mesh's pixels where the field is below ``min_opacity``
+      depth_rel_mean, depth_rel_median    of |z_mesh - z_field| / z_field on the COMMON pixels (both of the above), z_field = depth /
+                         opacity as in ``fuse``
+      psnr               of the mesh's colour (``atlas`` / ``block``: shaded from the atlas) against ``rgbs`` on the common pixels, dB
+      field_pixels, mesh_pixels, common_pixels   the counts
+    ``opacities`` None: every pixel with a finite depth > 0 is the field's.  A share or a mean over no pixel is NaN.  The reductions
+    are plain tensor operations on the device; the table reaches the host in ONE copy."""
+    h, w = int(hw[0]), int(hw[1])
+    n, k_views = h * w, len(views)
+    if k_views < 1:
+        raise ValueError("mesh_report: no view")
+    depths = depths.reshape(k_views, n)
+    colours = rgbs.reshape(k_views, n, 3)
+    rgba, z_mesh, face = render_mesh(vertices, faces, _open_views(views), (h, w), legacy, atlas=atlas, block=block)
+    z_mesh, rgba = z_mesh.reshape(k_views, n), rgba.reshape(k_views, n, 4)
+    if opacities is None:
+        z_field = depths
+        field = torch.isfinite(depths) & (depths > 0)
+    else:
+        opacities = opacities.reshape(k_views, n)
+        field = opacities >= min_opacity
+        z_field = depths / torch.where(field, opacities, torch.ones_like(opacities))
+        field = field & torch.isfinite(z_field) & (z_field > 0)
+    on_mesh = face.reshape(k_views, n) >= 0
+    common = field & on_mesh
+    rel = torch.where(common, (z_mesh - z_field).abs() / torch.where(common, z_field, torch.ones_like(z_field)), torch.zeros_like(z_field))
+    err = torch.where(common[..., None], rgba[..., :3] - colours, torch.zeros_like(colours)).double().square().sum(-1)
+
+    def rows(field, on_mesh, common, rel, err):  # over the last axis
+        nf, nm, nc = field.sum(-1).double(), on_mesh.sum(-1).double(), common.sum(-1).double()
+        nan = torch.full_like(rel, float("nan"))
+        median = torch.where(common, rel, nan).nanmedian(-1).values.double()
+        mse = err.sum(-1) / (3.0 * nc)
+        return torch.stack([nc / nf, (nm - nc) / nm, rel.double().sum(-1) / nc, median, -10.0 * torch.log10(mse), nf, nm, nc], -1)
+
+    table = torch.cat([rows(field, on_mesh, common, rel, err),
+                       rows(field.reshape(1, -1), on_mesh.reshape(1, -1), common.reshape(1, -1), rel.reshape(1, -1), err.reshape(1, -1))], 0)
+    table = table.cpu().numpy()  # the one copy
+    as_row = lambda r: {key: (int(x) if key.endswith("_pixels") else float(x)) for key, x in zip(REPORT_KEYS, r)}
+    return dict(views=[as_row(r) for r in table[:-1]], pooled=as_row(table[-1]))
 
 
 def write_ply(path, points, faces=None, normals=None):

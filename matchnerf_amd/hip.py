@@ -248,6 +248,9 @@ SIGNATURES = {
     "mnerf_mesh_texture_accumulate": (_int, [_vp, _P(_i32), _i64, _i64, _i32, _P(View)] + [_i32] * 4 + [_vp] * 2 + [_P(_i32), _i32, _vp]
                                       + [_f32] * 2 + [_i32] * 2 + [_vp] * 2),
     "mnerf_mesh_texture_resolve": (_int, [_vp, _P(_i32), _i64, _i64, _i32, _i32] + [_vp] * 3),
+    "mnerf_mesh_raster_workspace_bytes": (_i64, [_i32] * 2),
+    "mnerf_mesh_raster": (_int, [_vp, _P(_i32), _i64, _i64, _P(View)] + [_i32] * 3 + [_P(_i32)] + [_vp] * 3 + [_i64, _vp]),  # view: one host View
+    "mnerf_mesh_shade": (_int, [_vp, _P(_i32), _i64, _i64, _P(_i32), _vp, _i32, _i32, _vp] + [_i32] * 3 + [_P(View)] + [_vp] * 3),
     "mnerf_mesh_decimate_workspace_bytes": (_i64, [_i64] * 2 + [_i32] * 3),
     "mnerf_mesh_decimate": (_int, [_vp, _P(_i32), _i64, _i64, _P(_i32), _P(_i32)] + [_f32] * 4 + [_i32] * 3
                             + [_vp, _i64, _P(_i32), _i64, _P(_i32)] + [_vp] * 3),
@@ -2192,3 +2195,71 @@ def mesh_texture_resolve(vertices, triangles, block, accum, best=False, out=None
         check(lib.mnerf_mesh_texture_resolve(_ptr(vertices), _ptr_i32(triangles), nv, nt, int(block), int(bool(best)), _ptr(accum),
                                              _ptr(out), st), "mnerf_mesh_texture_resolve")
     return out.view(height, width, ATLAS_FLOATS)
+
+
+# ----------------------------------------------------------------------- mesh raster (matchnerf_amd/csrc/mesh_raster.hip)
+
+RGBA_FLOATS = 4  # floats of one pixel of a shaded frame (r g b a) or of a normal frame (nx ny nz 0)
+
+
+def mesh_raster_workspace_bytes(height, width):
+    """The bytes of the key buffer of a ``height`` x ``width`` frame (mnerf_mesh_raster_workspace_bytes: 8 per pixel); -1 for a frame
+    the rasterizer does not take.  Host only."""
+    return int(load().mnerf_mesh_raster_workspace_bytes(int(height), int(width)))
+
+
+def _frame(what, hw):
+    h, w = int(hw[0]), int(hw[1])
+    if mesh_raster_workspace_bytes(h, w) < 0:
+        raise MnerfError(f"{what}: a frame of {h}x{w} is out of range")
+    return h, w
+
+
+def mesh_raster(vertices, triangles, view, hw, legacy=True, out=None, workspace=None, stream=None):
+    """The mesh seen from one camera (mnerf_mesh_raster; include/mnerf.h "MESH RASTER" states the coverage rule) -> (face int32
+    [h, w]: the triangle every pixel sees, -1 where none; depth float32 [h, w]: its camera-z, 0 where none; bary float32 [h, w, 2]:
+    the perspective-correct weights of the triangle's vertices 1 and 2).  ``vertices`` [V, 8] / ``triangles`` [T, 3] as for
+    ``mesh_normals``; ``view``: one ``View`` - extr, the intr of the (h, w) grid, near_ / far_ = the depths that may win a pixel.
+    ``out``: the three tensors to write into; ``workspace``: ``mesh_raster_workspace_bytes(h, w)`` bytes, reused across views.
+    Enqueue only; the same bytes on every run."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_raster", vertices, triangles)
+    h, w = _frame("mesh_raster", hw)
+    out = (None, None, None) if out is None else out
+    face = _mesh_buffer("mesh_raster", "face", out[0], torch.int32, h * w, dev).view(h, w)
+    depth = _mesh_buffer("mesh_raster", "depth", out[1], torch.float32, h * w, dev).view(h, w)
+    bary = _mesh_buffer("mesh_raster", "bary", out[2], torch.float32, 2 * h * w, dev).view(h, w, 2)
+    workspace = export_workspace("mesh_raster", workspace, mesh_raster_workspace_bytes(h, w), dev)
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_raster(_ptr(vertices), _ptr_i32(triangles), nv, nt, C.byref(view), h, w, int(bool(legacy)), _ptr_i32(face),
+                                    _ptr(depth), _ptr(bary), _ptr(workspace), workspace.numel() * workspace.element_size(), st),
+              "mnerf_mesh_raster")
+    return face, depth, bary
+
+
+def mesh_shade(vertices, triangles, face, bary, view, atlas=None, block=0, normals=False, out=None, stream=None):
+    """Shade a rastered frame (mnerf_mesh_shade) -> rgba float32 [h, w, 4], or (rgba, normal [h, w, 4]) with ``normals``: the blend of
+    the hit triangle's vertex colours, or - with ``atlas`` [H, W, 4] of ``mesh_texture_atlas(T, block)`` - the bilinear value of the
+    atlas at the hit point; a = 1 on a hit and 0 0 0 0 elsewhere; the normal is the face's, unit length, turned towards the camera.
+    ``face`` [h, w] / ``bary`` [h, w, 2] as ``mesh_raster`` wrote them for ``view``.  ``out``: rgba, or the pair, to write into.
+    Enqueue only."""
+    import torch
+    lib = load()
+    dev, nv, nt = _mesh_args("mesh_shade", vertices, triangles)
+    if face.dim() != 2:
+        raise MnerfError(f"mesh_shade: face {tuple(face.shape)} is no [h, w] frame")
+    h, w = _frame("mesh_shade", face.shape)
+    face = _mesh_buffer("mesh_shade", "face", face, torch.int32, h * w, dev)
+    bary = _mesh_buffer("mesh_shade", "bary", bary, torch.float32, 2 * h * w, dev)
+    width = height = 0
+    if atlas is not None:
+        width, height = mesh_texture_atlas(nt, block)
+        atlas = _mesh_buffer("mesh_shade", "atlas", atlas, torch.float32, height * width * ATLAS_FLOATS, dev)
+    out = out if isinstance(out, (tuple, list)) else (out, None)
+    rgba = _mesh_buffer("mesh_shade", "rgba", out[0], torch.float32, h * w * RGBA_FLOATS, dev).view(h, w, RGBA_FLOATS)
+    normal = _mesh_buffer("mesh_shade", "normal", out[1], torch.float32, h * w * RGBA_FLOATS, dev).view(h, w, RGBA_FLOATS) if normals else None
+    with _on(dev, stream) as st:
+        check(lib.mnerf_mesh_shade(_ptr(vertices), _ptr_i32(triangles), nv, nt, _ptr_i32(face), _ptr(bary), h, w, _ptr(atlas), height, width,
+                                   int(block), C.byref(view), _ptr(rgba), _ptr(normal), st), "mnerf_mesh_shade")
+    return (rgba, normal) if normals else rgba

@@ -571,7 +571,7 @@ class MatchNeRF(torch.nn.Module):
         return images.permute(0, 1, 3, 4, 2).reshape(b, k, -1, 3).float().contiguous()
 
     def export_mesh(self, batch, views="sources", render_path_mode="interpolate", normals=False, texture=0, texture_best=False,
-                    texture_power=2, texture_vis_rel_tol=0.02, texture_from="render", **mesh_args):
+                    texture_power=2, texture_vis_rel_tol=0.02, texture_from="render", texture_visibility="views", report=False, **mesh_args):
         """The scene of ``batch`` as coloured triangle meshes -> a list over the batch of (vertices [V, 8] float32 rows
         ``x y z w | r g b 0``, faces [T, 3] int32) on the device (``fusion.mesh``: the depth maps of ``export_points`` fused into a
         truncated-signed-distance volume, its zero surface extracted by marching tetrahedra).  ``views`` and the one encoder pass as
@@ -583,21 +583,32 @@ class MatchNeRF(torch.nn.Module):
         the end - the finished mesh textured with blocks of B texels (``fusion.texture``; ``texture_best``, ``texture_power``,
         ``texture_vis_rel_tol``).  ``texture_from``: "render" bakes the frames rendered at the fusion poses, "images" - with
         ``views="sources"`` only - the source photographs ``batch.images`` instead of their re-renderings; the visibility test uses
-        the rendered depth either way.  The same refusals, and those of a bad block, power or source, before the first launch."""
+        the rendered depth either way - or, with ``texture_visibility="mesh"``, the finished mesh's own depth rasterized at the
+        fusion poses (``fusion.texture``).  ``report=True``: -> (meshes, [``fusion.mesh_report`` of every mesh against the maps it
+        was fused from, shaded with its atlas when it has one]).  The same refusals, and those of a bad block, power, source or
+        visibility, before the first launch."""
         from . import fusion
         unknown = set(mesh_args) - {"px_tol", "rel_tol", "min_opacity", "min_consistent"} - set(self.MESH_ARGS)
         fusion._decimate_cell("export_mesh", mesh_args.get("decimate", 0.0))
         fusion._sparse_flag("export_mesh", mesh_args.get("sparse", False))
         texture, texture_power = self.check_texture("export_mesh", texture, texture_power, texture_from, views)
+        fusion._visibility("export_mesh", texture_visibility)
         maps, cams_of = self._fusion_maps("export_mesh", batch, views, render_path_mode, unknown)
         legacy = bool(self.opts.nerf.legacy_coord)
         photos = self.source_colours(batch) if texture and texture_from == "images" else None
         meshes = [fusion.mesh(cams, maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy, texture=texture, texture_best=texture_best,
                               texture_power=texture_power, texture_vis_rel_tol=texture_vis_rel_tol,
-                              texture_rgbs=None if photos is None else photos[b], **mesh_args) for b, cams in enumerate(cams_of)]
+                              texture_rgbs=None if photos is None else photos[b], texture_visibility=texture_visibility, **mesh_args)
+                  for b, cams in enumerate(cams_of)]
+        reports = None
+        if report:
+            min_opacity = mesh_args.get("min_opacity", 0.5)
+            reports = [fusion.mesh_report(vertices, faces, cams_of[b], maps.depth[b], maps.opacity[b], maps.rgb[b], maps.hw, legacy,
+                                          atlas=textured[1] if textured else None, block=texture, min_opacity=min_opacity)
+                       for b, (vertices, faces, *textured) in enumerate(meshes)]
         if normals:
-            return [(vertices, faces, fusion.vertex_normals(vertices, faces), *textured) for vertices, faces, *textured in meshes]
-        return meshes
+            meshes = [(vertices, faces, fusion.vertex_normals(vertices, faces), *textured) for vertices, faces, *textured in meshes]
+        return (meshes, reports) if report else meshes
 
     def _fusion_maps(self, who, batch, views, render_path_mode, unknown):
         """What ``export_points`` and ``export_mesh`` share: the refusals, ONE encoder pass, a render at each fusion pose ->

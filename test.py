@@ -40,7 +40,11 @@ components are dropped), ``--nerf.mesh_smooth=<rounds of Taubin smoothing>``, th
 cos^power of its angle to the surface normal), ``--nerf.mesh_texture_best`` (the single best view per texel instead of the
 weighted mean), ``--nerf.mesh_texture_rel_tol=<relative depth>`` (0.02: how closely a view's depth map must agree with a surface
 point to count as seeing it), ``--nerf.mesh_texture_from=render|images`` (``images``: the source photographs instead of their
-re-renderings; with ``--nerf.export_geometry=sources`` only).
+re-renderings; with ``--nerf.export_geometry=sources`` only), ``--nerf.mesh_texture_visibility=views|mesh`` (``mesh``: a texel's
+visibility is tested against the mesh's own depth, rasterized at each view - what a decimated mesh wants).
+``--nerf.mesh_report`` writes ``<stem>_mesh_report.json`` (the mesh rendered at the fusion views against the field's maps: coverage,
+spurious pixels, relative depth error, PSNR, per view and pooled) and ``--nerf.mesh_preview`` writes ``<stem>_mesh_preview_<k>.png``
+per fusion view, the shaded mesh next to the field's frame.
 
     python test.py --yaml=demo_own --nerf.export_geometry=sources
     python test.py --yaml=demo_own --nerf.export_geometry=sources --nerf.export_mesh --nerf.mesh_resolution=192
